@@ -3,11 +3,16 @@
 litehandnet (MSRB hourglass = variant B by default), synthetic inputs resident in HBM, random-init weights.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR   (+ the last timed step's outputs as DIR/*.npy)
+    python bench.py --gpus 1 --full         (+ forward roofline, variants A / H / L, per-kernel rooflines, CPU oracle)
     python bench.py --gpus N ...            (no WORLD_SIZE in the environment: starts its own N ranks, see spawn_ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` (HBM, measured live with
-events on the launch stream) and `cpu_baseline` (the CPU oracle = port of the reference's path, bounded sample).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps training steps and reports them
+(`value`, `ms_per_step`, and `roofline_train_step`, which is arithmetic on the step time).  `--full` adds what takes
+runs of its own: `roofline` (forward plan, HBM, timed with events on the launch stream, against the copy rate measured
+in the same process), the other model variants, the per-kernel rooflines and `cpu_baseline` (the CPU oracle = port of
+the reference's path, bounded sample).
 """
 import argparse
 import json
@@ -20,6 +25,8 @@ import torch.distributed as dist
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+
+DUMP_BUDGET = 15_000_000     # float32 elements over all --dump-outputs files: 60 MB, .npy headers aside
 
 # algorithmic HBM bytes per image, fp32: 4 B x sum over convs of (in + out) elements
 ALG_FWD_BYTES = {"B": 76.42e6, "A": 98.07e6, "M": 82.59e6,   # M = `mynet` (pose_hg_ms_att.py), scripts/dump_plan.py M
@@ -164,8 +171,56 @@ def kernel_rooflines(B, dev):
     return out
 
 
-def measure_variant(variant, args, dev, world, rank):
-    """Train-step time and forward-plan time of one model variant at batch B (synthetic inputs resident in HBM)."""
+def _dump_sample(t, cap):
+    """t as float32, or a fixed seeded sample of `cap` of its elements (ascending flat index) when it is larger."""
+    t = t.detach().float().cpu().reshape(t.shape if t.numel() <= cap else (-1,))
+    if t.numel() <= cap:
+        return t
+    idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:cap].sort().values
+    return t[idx]
+
+
+def dump_outputs(out_dir, trainer, loss, heatmaps):
+    """What the last timed step computed: the loss it returned, the heatmaps of its forward, the flat gradient, Adam's two
+    moments and the BatchNorm running statistics -- as float32 .npy files, at most DUMP_BUDGET elements in all (smallest
+    array first, each taking at most an equal share of what is left).  The step they come from started from the seeded
+    initial state (restore_seeded_state), so two runs' files differ by the rounding of the atomically summed gradients
+    only; with LHN_DETERMINISTIC=1 they are bit-identical.  The parameters Adam wrote are not among them: its first step
+    moves a parameter by lr times the sign of its gradient, and gradients that are 0 in exact arithmetic (a bias in front
+    of a BatchNorm) are rounding noise in fp32 whose sign varies, so those parameters differ between runs by 2 lr."""
+    import numpy as np
+    stats = [b.reshape(-1).float() for _, b in trainer.model.named_buffers() if b.is_floating_point()]
+    adam = trainer.opt.state[trainer.fp.leaf]
+    arrays = {"loss": loss, "heatmaps": heatmaps, "grads": trainer.fp.leaf.grad, "adam_exp_avg": adam["exp_avg"],
+              "adam_exp_avg_sq": adam["exp_avg_sq"], "bn_running_stats": torch.cat(stats) if stats else torch.zeros(0)}
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BUDGET
+    for i, (name, t) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].numel())):
+        a = _dump_sample(t, left // (len(arrays) - i)).numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        left -= a.size
+
+
+def restore_seeded_state(trainer, seeded):
+    """Parameters and buffers back to `seeded` (their values before the first step), optimizer state back to empty.
+    With --dump-outputs the last timed step starts from here, so that its inputs are the seeded ones in every run: steps
+    carry their results into the next, their gradients are summed with atomics in the default mode (last bits vary from
+    run to run), and this training run from random weights diverges, which amplifies those bits within a few steps."""
+    from litehandnet_amd import invalidate_tables
+    with torch.no_grad():
+        for t, s in zip([trainer.fp.flat] + list(trainer.model.buffers()), seeded):
+            t.copy_(s)
+        for st in trainer.opt.state.values():
+            for v in st.values():
+                if torch.is_tensor(v):
+                    v.zero_()
+    invalidate_tables()
+
+
+def measure_variant(variant, args, dev, world, rank, forward=True, dump_dir=None):
+    """Train-step time of one model variant at batch B (synthetic inputs resident in HBM) and, with `forward`, the time
+    of its forward plan (else None).  `dump_dir`: the last timed step starts from the seeded initial state and its
+    outputs are written there (restore_seeded_state, dump_outputs); without it the timed steps only chain."""
     from litehandnet_amd import get_loss, get_model, heatmap
     from litehandnet_amd.config import litehandnet_cfg
     from litehandnet_amd.train import Trainer
@@ -193,19 +248,32 @@ def measure_variant(variant, args, dev, world, rank):
             dist.barrier()
             torch.cuda.synchronize()
 
+    heat, seeded = [None], None
+    if dump_dir is not None:           # keeps (a reference to) each forward's heatmaps; the last one is the timed step's
+
+        def keep(mod, inp, out):
+            heat[0] = out
+        model.register_forward_hook(keep)
+        seeded = [t.detach().clone() for t in [trainer.fp.flat] + list(model.buffers())]
     for _ in range(args.warmup):
         trainer.step(img, meta)
     sync()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        trainer.step(img, meta)
+    for i in range(args.steps):
+        if seeded is not None and i == args.steps - 1:
+            restore_seeded_state(trainer, seeded)
+        loss = trainer.step(img, meta)
     sync()
     el = time.perf_counter() - t0
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, trainer, loss, heat[0])
     # max over ranks (RCCL reduces device tensors; the gloo rehearsal backend, LHN_DIST_BACKEND=gloo, takes host tensors)
     tmax = torch.tensor([el], dtype=torch.float64, device=dev if world > 1 and dist.get_backend() == "nccl" else "cpu")
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     el = float(tmax.item())
+    if not forward:
+        return el, None
     # ---- forward-only launch duration with events on the launch stream (roofline of the forward plan run)
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     with torch.no_grad():
@@ -284,13 +352,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--variant", default="B", choices=["A", "B", "M", "H", "L"])
     ap.add_argument("--batch", type=int, default=64, help="per-GPU batch")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline variant only (skip variant A and the per-kernel rooflines)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the forward roofline, variants A / H / L, per-kernel rooflines and the CPU oracle baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: headline variant only (skip variants A / H / L and the per-kernel rooflines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (float32); "
+                    "that step starts from the seeded initial state")
     ap.add_argument("--sync-bn", action="store_true", help="cfg.TRAIN.syncBN: SyncBatchNorm over the process group (N > 1)")
     ap.add_argument("--dropout", type=float, default=0.3, help="Dropout2d p inside channel attention (reference: 0.3)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus, sys.argv[1:]))
 
@@ -303,15 +378,14 @@ def main():
         raise SystemExit("bench.py needs a GPU (no CPU fallback)")
     dev = torch.device("cuda", torch.cuda.current_device())
     B = args.batch
-    el, fwd_ms = measure_variant(args.variant, args, dev, world, rank)
-    extras = world == 1 and not args.no_extras
+    el, fwd_ms = measure_variant(args.variant, args, dev, world, rank, forward=args.full, dump_dir=args.dump_outputs)
+    extras = args.full and world == 1 and not args.no_extras
     # variant A is the model the reference registers as `litehandnet` (models/__init__.py:11): timed in the same run
     a_el, a_fwd = measure_variant("A", args, dev, world, rank) if (extras and args.variant == "B") else (None, None)
-    # BASELINE config 5 (stacked hourglass, Lite-HRNet-18): same batch / steps, so that the driver's own run times them too
+    # BASELINE config 5 (stacked hourglass, Lite-HRNet-18): same batch / steps, so that a --full run times them too
     others = {v: measure_variant(v, args, dev, world, rank) for v in ("H", "L")} if (extras and args.variant == "B") else {}
     if rank != 0:
         return
-    copy_gbs = copy_bandwidth(dev)
     value = world * B * args.steps / el
     step_ms = el / args.steps * 1e3
     train_alg = (3 * ALG_FWD_BYTES[args.variant] + LOSS_BYTES) * B
@@ -322,11 +396,16 @@ def main():
         "config": {"workload": f"litehandnet variant {args.variant} ({VARIANT_NAME[args.variant]}) "
                                f"C={ {'H': 256, 'L': '40..320'}.get(args.variant, 128) }, 256x256x3 -> 21x64x64, per-GPU batch {B}, train-mode BN, fwd + TopdownHeatmapLoss + bwd + fused Adam",
                    "global_batch": world * B, "parallelism": f"dp{world}", "ca_dropout": args.dropout},
-        "roofline": forward_roofline(args.variant, B, fwd_ms, copy_gbs),
-        "roofline_train_step": {"bound": "hbm", "achieved": round(train_alg / (step_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS,
-                                "unit": "GB/s", "frac": round(train_alg / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
-        "forward_images_per_s": round(B / (fwd_ms * 1e-3), 1),
     }
+    if args.full:
+        copy_gbs = copy_bandwidth(dev)
+        out["roofline"] = forward_roofline(args.variant, B, fwd_ms, copy_gbs)
+    out["roofline_train_step"] = {"bound": "hbm", "achieved": round(train_alg / (step_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS,
+                                  "unit": "GB/s", "frac": round(train_alg / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        return
+    out["forward_images_per_s"] = round(B / (fwd_ms * 1e-3), 1)
     if a_el is not None:
         # the model the reference REGISTERS as `litehandnet` (models/__init__.py:11) is variant A; `value` is the MSRB hourglass
         # (variant B) that north_star's roofline target names -- both at the top level so that neither reads as the other
