@@ -1471,6 +1471,214 @@ __global__ void __launch_bounds__(256) k_dwk_bwd_lds(lhn_view x, const float* __
   }
 }
 
+// Row-streaming fused backward of the 3x3 depthwise convolution (dgrad + wgrad, the fusions of k_dwk_bwd_lds with the same
+// meaning).  A work item is a strip of 32 output columns x CH rows x 32 channels of one (image, parity sub-lattice); the
+// workgroup walks down it ONE halo row per step.  LDS keeps a ring of R = 2*DIL + 2 rows of dy and of x (the 2*DIL + 1 rows
+// the taps read plus the row being written); each step
+//   issue the gradient addends of the output row -> commit the halo row loaded one step earlier (dy / x transforms, ring
+//   slot q % R) -> issue the next halo row's global loads -> barrier -> taps of the output row -> store dx,
+// so a row's loads are in flight while the previous row's taps run, and one barrier per row is the only synchronisation
+// (the slot written at step q + 1 is the one the taps of step q - 1 read last).  The last step of an item issues the first
+// halo row of the workgroup's next item.  Halo overhead is (32 + 2*DIL) / 32 x (CH + 2*DIL) / CH (1.20 at CH = 16) instead of
+// 1.41 for the 8 x 16 tile; per-channel constants and weights are read from LDS, so the kernel fits 4 waves per SIMD.
+template <int DIL, bool BNS = false>
+__global__ void __launch_bounds__(256, (BNS || DIL > 1) ? 2 : 3) k_dw3_bwd_rows(lhn_view x, const float* __restrict__ w, lhn_view y, lhn_gradview gy,
+                                                         float* __restrict__ dx, int dx_acc, float* __restrict__ dw, int nstrips,
+                                                         int nchunks, int CH, int cgroups, int nrep, int64_t rep_stride, int ps,
+                                                         DwBnSum bs) {
+  constexpr int P = DIL, R = 2 * P + 2, WW = 32 + 2 * P, KK = 9;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  f4* tdy = reinterpret_cast<f4*>(smem);        // [R][WW][8] dy ring
+  f4* tx = tdy + R * WW * 8;                    // [R][WW][8] x ring (consumed value)
+  f4* wl = tx + R * WW * 8;                     // [9][8] weights of this block's channel group
+  f4* cst = wl + KK * 8;                        // [9][8] x scale | shift | slope, y scale | shift | slope, A | B | C
+  f4* tmi = cst + KK * 8;                       // [2][8] mean | invstd of the producer (BNS only)
+  f4* traw = tmi + 16;                          // [R][32][8] raw x of the strip's columns (BNS only)
+  const int tid = threadIdx.x, c4 = tid & 7, pl = tid >> 3;
+  const int ntile = y.N * ps * ps * nchunks * nstrips * cgroups;
+  const int cg = blockIdx.x % cgroups;                      // grid % cgroups == 0 (host): fixed per block
+  const int cvalid = min(8, (x.C - cg * 32) >> 2);          // see k_dwk_fwd_lds
+  const bool cok = c4 < cvalid;
+  const int c4e = cok ? c4 : 0;
+  const int cx = x.coff + cg * 32 + 4 * c4e, cy = y.coff + cg * 32 + 4 * c4e;
+  // every thread loads halo column pl + P of a row (its own output column); threads 0 .. 16*P-1 also load one of the 2*P
+  // edge columns 0 .. P-1, 32+P .. 32+2P-1
+  const bool edge = tid < 16 * P;
+  const int ecol = (pl < P) ? pl : 32 + pl;
+  const f4 z = (f4){0.f, 0.f, 0.f, 0.f}, one = (f4){1.f, 1.f, 1.f, 1.f};
+  if (tid < KK * 8) {
+    const int k = tid >> 3, cc = cg * 32 + 4 * min(tid & 7, cvalid - 1);
+    wl[tid] = (f4){w[(cc + 0) * KK + k], w[(cc + 1) * KK + k], w[(cc + 2) * KK + k], w[(cc + 3) * KK + k]};
+  } else if (tid < 2 * KK * 8) {
+    const int i = tid - KK * 8, kind = i >> 3, ca = cg * 32 + 4 * min(i & 7, cvalid - 1), j = kind % 3;
+    const float* tab = kind < 3 ? x.table : kind < 6 ? y.table : gy.coef;
+    const int cs = kind < 3 ? x.cstride : y.cstride, co = kind < 3 ? x.coff : y.coff;
+    cst[i] = tab ? *reinterpret_cast<const f4*>(tab + j * cs + co + ca) : ((kind < 6 ? j != 1 : j == 0) ? one : z);
+  } else if (BNS && tid < 2 * KK * 8 + 16) {
+    const int i = tid - 2 * KK * 8, kind = i >> 3, cc = i & 7;
+    tmi[i] = *reinterpret_cast<const f4*>(bs.save + kind * bs.C + bs.coff + cg * 32 + 4 * cc);
+  }
+  f4 accw[KK];
+#pragma unroll
+  for (int k = 0; k < KK; ++k) accw[k] = z;
+  f4 sdu = z, sdux = z;
+  // item t -> channel group (fastest: fixed per block), strip, row chunk, parity sub-lattice, image
+  struct Item {
+    int n, pa, pb, SH, SW, wb, h0, nrows;
+  };
+  auto decode = [&](int t) __attribute__((always_inline)) {
+    Item it;
+    int r = t / cgroups;
+    const int st = r % nstrips;
+    r /= nstrips;
+    const int ch = r % nchunks;
+    r /= nchunks;
+    const int par = r % (ps * ps);
+    it.n = r / (ps * ps);
+    it.pa = par / ps;
+    it.pb = par % ps;
+    it.SH = (x.H - it.pa + ps - 1) / ps;
+    it.SW = (x.W - it.pb + ps - 1) / ps;
+    it.wb = st * 32;
+    it.h0 = ch * CH;
+    it.nrows = max(0, min(CH, it.SH - it.h0));
+    return it;
+  };
+  // one halo row into registers: raw x, raw y, dz, pooled gradient (main column; edge column), zero outside the map
+  f4 mx = z, my = z, mz = z, mp = z, ex = z, ey = z, ez = z, ep = z;
+  bool okm = false, oke = false;
+  auto issue = [&](const Item& it, int hr) __attribute__((always_inline)) {
+    const bool rok = hr >= 0 && hr < it.SH && cok;
+    const int ih = it.pa + ps * hr;
+    const int cm = it.wb + pl, ce = it.wb - P + ecol;
+    okm = rok && cm < it.SW;
+    oke = rok && edge && ce >= 0 && ce < it.SW;
+    mx = my = mz = mp = ex = ey = ez = ep = z;
+    if (okm) {
+      const size_t pix = (size_t)(it.n * x.H + ih) * x.W + it.pb + ps * cm;
+      mx = *reinterpret_cast<const f4*>(x.data + pix * x.cstride + cx);
+      my = *reinterpret_cast<const f4*>(y.data + pix * y.cstride + cy);
+      mz = *reinterpret_cast<const f4*>(gy.dz + pix * y.cstride + cy);
+      if (gy.dpool) mp = lhn_dpool_sum(gy, y, it.n, ih, it.pb + ps * cm, cy);
+    }
+    if (oke) {
+      const size_t pix = (size_t)(it.n * x.H + ih) * x.W + it.pb + ps * ce;
+      ex = *reinterpret_cast<const f4*>(x.data + pix * x.cstride + cx);
+      ey = *reinterpret_cast<const f4*>(y.data + pix * y.cstride + cy);
+      ez = *reinterpret_cast<const f4*>(gy.dz + pix * y.cstride + cy);
+      if (gy.dpool) ep = lhn_dpool_sum(gy, y, it.n, ih, it.pb + ps * ce, cy);
+    }
+  };
+  // transformed values (as k_dwk_bwd_lds) into ring slot s
+  auto put = [&](int s, int col, bool ok, f4 rx, f4 ry, f4 rz, f4 rp, f4 xg, f4 yg) __attribute__((always_inline)) {
+    const f4 xsc = cst[c4], xsh = cst[8 + c4], xsl = cst[16 + c4];
+    const f4 ysc = cst[24 + c4], ysh = cst[32 + c4], ysl = cst[40 + c4];
+    const f4 gA = cst[48 + c4], gB = cst[56 + c4], gC = cst[64 + c4];
+    const f4 ux = rx * xsc + xsh;
+    const f4 vx = (f4){lhn_lrelu(ux.x, xsl.x), lhn_lrelu(ux.y, xsl.y), lhn_lrelu(ux.z, xsl.z), lhn_lrelu(ux.w, xsl.w)} * xg;
+    const f4 e = rz * yg + rp;
+    const f4 u = ry * ysc + ysh;
+    const f4 dl = (f4){u.x > 0.f ? 1.f : ysl.x, u.y > 0.f ? 1.f : ysl.y, u.z > 0.f ? 1.f : ysl.z, u.w > 0.f ? 1.f : ysl.w};
+    const f4 vy = gA * (e * dl) + gB * ry + gC;
+    tx[(s * WW + col) * 8 + c4] = ok ? vx : z;
+    tdy[(s * WW + col) * 8 + c4] = ok ? vy : z;
+    if (BNS && col >= P && col < 32 + P) traw[(s * 32 + col - P) * 8 + c4] = rx;
+  };
+  int t = blockIdx.x;
+  if (t < ntile) {
+    const Item nx = decode(t);
+    issue(nx, nx.h0 - P);
+  }
+#pragma unroll 1
+  for (; t < ntile; t += gridDim.x) {
+    const Item it = decode(t);
+    const f4 xg = x.gate ? *reinterpret_cast<const f4*>(x.gate + (size_t)it.n * x.cstride + cx) : one;
+    const f4 yg = y.gate ? *reinterpret_cast<const f4*>(y.gate + (size_t)it.n * y.cstride + cy) : one;
+    const int wcol = it.wb + pl, nload = it.nrows + 2 * P;
+    const bool ocol = wcol < it.SW;
+    __syncthreads();     // the previous item's taps are done with the ring (and the constants are visible)
+#pragma unroll 1
+    for (int q = 0; q < nload; ++q) {
+      const bool orow = q >= 2 * P;
+      const int hh = it.h0 + max(q - 2 * P, 0);          // output row of this step (q >= 2P)
+      float* o = dx + ((size_t)(it.n * x.H + it.pa + ps * hh) * x.W + it.pb + ps * wcol) * x.cstride + cx;
+      const bool st = orow && dx && cok && ocol;
+      const int s = q % R;
+      put(s, pl + P, okm, mx, my, mz, mp, xg, yg);
+      if (edge) put(s, ecol, oke, ex, ey, ez, ep, xg, yg);
+      if (q + 1 < nload) issue(it, it.h0 - P + q + 1);
+      else if (t + (int)gridDim.x < ntile) {
+        const Item nx = decode(t + gridDim.x);
+        issue(nx, nx.h0 - P);
+      }
+      __syncthreads();
+      if (!orow || !ocol) continue;
+      // rows hh - P .. hh + P sit in slots (q - 2P .. q) % R; centre hh in slot (q - P) % R
+      int sr[3];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) sr[a] = (q - 2 * P + a * DIL) % R;
+      const int centre = (sr[1] * WW + pl + P) * 8 + c4;
+      const f4 dyc = tdy[centre];
+      f4 accx = z;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+          // dx[h,w] += dy[h+P-a*DIL, w+P-b*DIL] * wgt[a][b] ;  dW[a][b] += dy[h,w] * x[h-P+a*DIL, w-P+b*DIL]
+          accx += tdy[(sr[2 - a] * WW + pl + 2 * P - b * DIL) * 8 + c4] * wl[(a * 3 + b) * 8 + c4];
+          accw[a * 3 + b] += dyc * tx[(sr[a] * WW + pl + b * DIL) * 8 + c4];
+        }
+      }
+      if (BNS) {          // accx is the complete d(value of x): this kernel is x's only reader (host-checked, dx_acc == 0)
+        const f4 raw = traw[(sr[1] * 32 + pl) * 8 + c4];
+        const f4 xsc = cst[c4], xsh = cst[8 + c4], xsl = cst[16 + c4];
+        const f4 u = raw * xsc + xsh;
+        const f4 du = accx * (f4){u.x > 0.f ? 1.f : xsl.x, u.y > 0.f ? 1.f : xsl.y, u.z > 0.f ? 1.f : xsl.z, u.w > 0.f ? 1.f : xsl.w};
+        sdu += du;
+        sdux += du * ((raw - tmi[c4]) * tmi[8 + c4]);
+      }
+      if (st) {
+        if (dx_acc) accx += *reinterpret_cast<const f4*>(o);
+        if (bs.add[0]) accx += *reinterpret_cast<const f4*>(bs.add[0] + (o - dx));
+        if (bs.add[1]) accx += *reinterpret_cast<const f4*>(bs.add[1] + (o - dx));
+        *reinterpret_cast<f4*>(o) = accx;
+      }
+    }
+  }
+  f4* red = tdy;         // the rings are dead after the last item
+  if (BNS) {
+    double* sts = bs.sums + (size_t)((blockIdx.x / cgroups) % LHN_STAT_REPLICAS) * 2 * bs.C + bs.coff + cg * 32;
+    lhn_block_stat_atomics(sdu, sdux, 8, red, sts, sts + bs.C);
+  }
+  // ---- flush dW (as k_dwk_bwd_lds)
+  float* dwr = dw + (size_t)((blockIdx.x / cgroups) % nrep) * rep_stride;
+#pragma unroll
+  for (int k = 0; k < KK; ++k)
+#pragma unroll
+    for (int o = 8; o < 64; o <<= 1) {
+      accw[k].x += __shfl_xor(accw[k].x, o, 64);
+      accw[k].y += __shfl_xor(accw[k].y, o, 64);
+      accw[k].z += __shfl_xor(accw[k].z, o, 64);
+      accw[k].w += __shfl_xor(accw[k].w, o, 64);
+    }
+  __syncthreads();
+  if ((tid & 63) < 8)
+#pragma unroll
+    for (int k = 0; k < KK; ++k) red[(k * 4 + (tid >> 6)) * 8 + c4] = accw[k];
+  __syncthreads();
+  if (tid < KK * 8) {
+    const int k = tid >> 3, cc = tid & 7;
+    const f4 sacc = red[(k * 4 + 0) * 8 + cc] + red[(k * 4 + 1) * 8 + cc] + red[(k * 4 + 2) * 8 + cc] + red[(k * 4 + 3) * 8 + cc];
+    const int cb = cg * 32 + 4 * cc;
+    if (cc < cvalid) {
+      atomicAdd(dwr + (cb + 0) * KK + k, sacc.x);
+      atomicAdd(dwr + (cb + 1) * KK + k, sacc.y);
+      atomicAdd(dwr + (cb + 2) * KK + k, sacc.z);
+      atomicAdd(dwr + (cb + 3) * KK + k, sacc.w);
+    }
+  }
+}
+
 // blocks per XCD when the XCD-aware tile order applies (grid a multiple of 8 and of 8 * cgroups), else 0 = plain order.
 // Measured on MI355X (variant B, bs64 256x256): giving each XCD a contiguous run of tiles is SLOWER than the plain
 // round-robin order -- forward 3.08 vs 2.93 ms, train step 9.66 vs 9.55 ms: the halo re-reads already hit the Infinity
@@ -1522,6 +1730,39 @@ static void launch_dwk_bwd(const lhn_view* x, const float* w, const lhn_view* y,
   const int grid = dw3_grid(ntile, cg, 4);
   hipLaunchKernelGGL((k_dwk_bwd_lds<K, DIL, BNS>), dim3(grid), dim3(256), lds, s, *x, w, *y, *gy, dx, dx_acc, dw, th, tw,
                      cg, nrep, rep_stride, ps, bs, dw3_xchunk(grid, cg));
+}
+template <int DIL, bool BNS = false>
+static void launch_dw3_bwd_rows(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc,
+                                float* dw, int nrep, int64_t rep_stride, hipStream_t s, int ps = 1, const DwBnSum* bsp = nullptr) {
+  constexpr int P = DIL, R = 2 * P + 2, WW = 32 + 2 * P;
+  DwBnSum bs;
+  if (bsp) bs = *bsp; else { bs.sums = nullptr; bs.save = nullptr; bs.C = bs.coff = 0; bs.add[0] = bs.add[1] = nullptr; }
+  const int cg = (x->C + 31) / 32;
+  const int sh = (x->H + ps - 1) / ps, sw = (x->W + ps - 1) / ps;     // largest parity sub-lattice
+  const int nstrips = (sw + 31) / 32;
+  const size_t lds = (size_t)(2 * R * WW * 8 + 2 * 9 * 8 + 16 + (BNS ? R * 32 * 8 : 0)) * 16;
+  static LhnKernelCfg cfg;
+  int per_cu = 1;
+  (void)lhn_kernel_cfg(cfg, &k_dw3_bwd_rows<DIL, BNS>, lds, 8, &per_cu);
+  // row chunks: about one item per resident workgroup, at least 8 rows each (the 2*P halo rows are loaded once per item)
+  const int base = x->N * ps * ps * nstrips * cg;
+  int nch = (lhn_num_cus() * per_cu + base - 1) / base;
+  nch = std::max(1, std::min(nch, (sh + 7) / 8));
+  const int CH = (sh + nch - 1) / nch;
+  nch = (sh + CH - 1) / CH;
+  const int ntile = base * nch;
+  const int grid = dw3_grid(ntile, cg, per_cu);       // one round of resident workgroups
+  hipLaunchKernelGGL((k_dw3_bwd_rows<DIL, BNS>), dim3(grid), dim3(256), lds, s, *x, w, *y, *gy, dx, dx_acc, dw, nstrips, nch, CH, cg,
+                     nrep, rep_stride, ps, bs);
+}
+// LHN_DW_BWD_V1=1 (read once): the 3x3 backward runs the 8 x 16 tile kernel k_dwk_bwd_lds instead of k_dw3_bwd_rows
+static bool lhn_dw_bwd_v1() {
+  static int v = -1;
+  if (v < 0) {
+    const char* e = getenv("LHN_DW_BWD_V1");
+    v = (e && e[0] == '1') ? 1 : 0;
+  }
+  return v == 1;
 }
 
 
@@ -1805,13 +2046,21 @@ int lhn_dwk_bwd_lds(const lhn_view* x, const float* w, const lhn_view* y, const 
                     float* dw, int k, int dil, int nrep, int64_t rep_stride, hipStream_t s, const DwBnSum* bs) {
   if (bs && bs->sums) {        // fused BatchNorm-backward sums of the producer: the 3x3 / dilation 1 instance only
     if (!(k == 3 && dil == 1 && dx && !dx_acc)) return 0;
-    launch_dwk_bwd<3, 1, true>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs);
+    if (lhn_dw_bwd_v1()) launch_dwk_bwd<3, 1, true>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs);
+    else launch_dw3_bwd_rows<1, true>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs);
     return 1;
   }
-  if (k == 3 && dil == 1) launch_dwk_bwd<3, 1>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs);
-  else if (k == 3 && dil == 2 && x->W >= 16) launch_dwk_bwd<3, 1>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 2, bs);
-  else if (k == 3 && dil == 2) launch_dwk_bwd<3, 2>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs);
-  else if (k == 7 && dil == 1) launch_dwk_bwd<7, 1>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs);
+  const bool v1 = lhn_dw_bwd_v1();
+  if (k == 3 && dil == 1) {
+    if (v1) launch_dwk_bwd<3, 1>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs);
+    else launch_dw3_bwd_rows<1>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs);
+  } else if (k == 3 && dil == 2 && x->W >= 16) {       // parity sub-lattices
+    if (v1) launch_dwk_bwd<3, 1>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 2, bs);
+    else launch_dw3_bwd_rows<1>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 2, bs);
+  } else if (k == 3 && dil == 2) {
+    if (v1) launch_dwk_bwd<3, 2>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs);
+    else launch_dw3_bwd_rows<2>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs);
+  } else if (k == 7 && dil == 1) launch_dwk_bwd<7, 1>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs);     // K = 7: tile kernel
   else return 0;
   return 1;
 }
