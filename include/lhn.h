@@ -232,6 +232,15 @@ int lhn_conv_dw_fwd2(const lhn_view* x, const float* w, const lhn_view* y, doubl
 /* ... and sum_out (or NULL): the summed input is also written there, see lhn_pw_opts.sum_out. */
 int lhn_conv_dw_fwd3(const lhn_view* x, const float* w, const lhn_view* y, double* stats, int k, int stride, int pad, int dil,
                      const lhn_bnfin* fin, const lhn_view* extra, const float* coef2, const lhn_view* sum_out, void* stream);
+/* Inference only: RepBasicUnit's right branch, RepConv 1x1 then RepConv depthwise 3x3 (litehourglass.py:52-78 over
+ * repblocks.py:8-44), in one launch -- the tensor between the two convolutions never reaches memory.  Per image:
+ *   t     = lrelu_slope1(scale1 * (w1 . value(x)) + shift1)      t_table = [3][Cm] scale | shift | slope (NULL = identity)
+ *   y_raw = depthwise 3x3 of t, stride 1, dilation 1, t padded with ZEROS (not with lrelu(shift1))
+ * y_raw is stored raw into channels [y.coff, y.coff + Cm) of y; its own bias / BatchNorm / activation stay pending in y's
+ * table exactly as lhn_conv_dw_fwd leaves them.  No statistics, no atomics: repeated calls give identical bits.
+ * Built for Cin == Cm == 64 (any N, H, W); any other channel count returns the invalid-argument status and writes nothing. */
+int lhn_conv_pw_dw3_fwd(const lhn_view* x, const float* w1 /*[Cm,Cin]*/, const float* t_table /*[3][Cm] or NULL*/,
+                        const float* w2 /*[Cm,1,3,3]*/, const lhn_view* y, void* stream);
 int lhn_conv_stem_fwd(const float* img /*[N,3,Hi,Wi]*/, const float* w /*[Cout,3,k,k]*/, const lhn_view* y,
                       double* stats, int Hi, int Wi, int k, int stride, int pad, const lhn_bnfin* fin, void* stream);
 /* wt_scratch: optional 9*Cout*Cin floats of caller-owned scratch; the call re-lays the OIHW weights tap-major into it

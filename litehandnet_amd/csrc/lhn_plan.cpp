@@ -23,6 +23,7 @@ static lhn_bnsum mkbns(void* ws, int64_t sums_off, int64_t save_off, int C, int 
 enum {
   OP_STEM = 1, OP_PW = 2, OP_DW = 3, OP_KXK = 4, OP_FINALIZE = 5, OP_EW = 6, OP_MAXPOOL = 7, OP_AVGPOOL = 8,
   OP_CA_MLP = 9, OP_TABLE_FILL = 10, OP_MEMSET = 11, OP_ATT_MLP = 12, OP_SE_MLP = 13, OP_SHUFFLE = 14,
+  OP_PWDW = 15,
   OP_STEM_BWD = 101, OP_PW_BWD = 102, OP_DW_BWD = 103, OP_KXK_BWD = 104, OP_BN_BWD = 105, OP_EW_BWD = 106,
   OP_MAXPOOL_BWD = 107, OP_AVGPOOL_BWD = 108, OP_GATE_REDUCE = 109, OP_CA_MLP_BWD = 110, OP_ATT_MLP_BWD = 111, OP_SE_MLP_BWD = 112,
   OP_SHUFFLE_BWD = 113,
@@ -322,6 +323,18 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
                               (bn && fz) ? &fin : nullptr,
                               o.ws[3] >= 0 ? reinterpret_cast<float*>(at(ws, o.ws[3])) : nullptr, stream);
         if (!rc && bn && h1 && !skip_tables && !deferred && !fz) rc = sep_finalize(fin, reinterpret_cast<const double*>(at(ws, o.ws[0])), training, stream);
+        break;
+      }
+      case OP_PWDW: {  // in: x, the intermediate buffer (only its table exists); p: w1, w2.  Inference plans only.
+        if (training) {
+          lhn_set_error("lhn_plan_run: a fused 1x1 -> depthwise launch has no batch statistics (inference plans only)");
+          rc = 1;
+          break;
+        }
+        lhn_view x = mkview(P, ws, o.in_buf[0], o.in_coff[0], o.in_C[0]);
+        lhn_view y = mkview(P, ws, o.out_buf, o.out_coff, o.out_C);
+        rc = lhn_conv_pw_dw3_fwd(&x, prm<const float>(params, o.p[0]), reinterpret_cast<const float*>(at(ws, P->bufs[o.in_buf[1]].table_off)),
+                                 prm<const float>(params, o.p[1]), &y, stream);
         break;
       }
       case OP_FINALIZE: {

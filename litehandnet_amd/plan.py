@@ -25,6 +25,7 @@ from ._lib import Buf, Op
 
 # op kinds (must match csrc/lhn_plan.cpp)
 STEM, PW, DW, KXK, FINALIZE, EW, MAXPOOL, AVGPOOL, CA_MLP, TABLE_FILL, MEMSET, ATT_MLP, SE_MLP, SHUFFLE = range(1, 15)
+PWDW = 15              # inference plans only: 1x1 -> depthwise 3x3 in one launch (lhn_conv_pw_dw3_fwd), see PlanBuilder.fuse_pw_dw
 STEM_BWD, PW_BWD, DW_BWD, KXK_BWD, BN_BWD, EW_BWD, MAXPOOL_BWD, AVGPOOL_BWD, GATE_REDUCE, CA_MLP_BWD, ATT_MLP_BWD, SE_MLP_BWD, SHUFFLE_BWD = range(101, 114)
 SLOPE_SILU = 2.0       # LHN_SLOPE_SILU in include/lhn.h: the combine applies SiLU instead of a leaky ReLU
 SLOPE_RELU_SIGMOID = 3.0   # LHN_SLOPE_RELU_SIGMOID: sigmoid(relu(v)) (lite_hrnet.py: nn.ReLU followed by nn.Sigmoid)
@@ -33,6 +34,32 @@ EW_MUL, EW_BILINEAR = 1, 2   # EwSrcs.mode bits: product of the sources / biline
 ALIGN = 256
 STAT_REPLICAS = 32     # LHN_STAT_REPLICAS in include/lhn.h
 TICKET_WORDS = 33      # arrival counters of a fused finalize (lhn_bnfin.counter: one top word + 32 group words)
+
+
+_INFER_FUSE = None     # set_infer_fuse(): in-process override of LHN_INFER_FUSE
+
+
+def set_infer_fuse(on):
+    """Switch the inference fusion pass (PlanBuilder.fuse_pw_dw) on or off for plans built from now on; None = follow the
+    environment again.  Engine.plan_for keys its cache on the switch, so the next forward builds the matching plan."""
+    global _INFER_FUSE
+    _INFER_FUSE = None if on is None else bool(on)
+
+
+def infer_fuse_enabled():
+    """LHN_INFER_FUSE=1 (default off): plans without a backward run RepBasicUnit's 1x1 -> depthwise 3x3 pairs as one launch."""
+    return _INFER_FUSE if _INFER_FUSE is not None else os.environ.get("LHN_INFER_FUSE", "0") == "1"
+
+
+def _refs_in(v):
+    """Every TRef inside a record value (views, concatenations, lists of views or of (view, coefficient) pairs)."""
+    if isinstance(v, TRef):
+        yield v
+    elif isinstance(v, TCat):
+        yield from v.parts
+    elif isinstance(v, (list, tuple)):
+        for u in v:
+            yield from _refs_in(u)
 
 
 def _al(n):
@@ -82,6 +109,7 @@ class _BufRec:
     coef: bool = False
     dpool: bool = False
     lazy: object = None      # the EW record of a sum that is taken ON LOAD by its consumers (never written in forward)
+    fused: bool = False      # the tensor between the two convolutions of a PWDW launch: a table, no data
     off: dict = field(default_factory=dict)
 
 
@@ -104,8 +132,12 @@ _IDENT = _IdentConv()
 
 
 class PlanBuilder:
-    def __init__(self, N, state_index, image_hw=None, with_backward=True, p_drop=0.0):
+    def __init__(self, N, state_index, image_hw=None, with_backward=True, p_drop=0.0, infer_fuse=None):
         self.N = N
+        # inference fusion (fuse_pw_dw): None = the process-wide switch.  The fused launch has no batch statistics, so the
+        # caller passes False for a plan that will run train-mode BatchNorm under no_grad (Engine.plan_for).
+        self.infer_fuse = infer_fuse_enabled() if infer_fuse is None else bool(infer_fuse)
+        self.n_fused = 0
         self.state_index = state_index      # id(tensor) -> index in the params array
         self.bufs = []
         self.recs = []                      # forward records (python dicts)
@@ -489,6 +521,9 @@ class PlanBuilder:
                 b.off["dpool"] = base
                 base += _al(N * 25 * b.C * 4)      # LHN_DPOOL_SLOTS: 5 x 5 bin-overlap segments
         for b in self.bufs:
+            if b.fused:                                   # lives in LDS only
+                b.off["data"] = -1
+                continue
             b.off["data"] = base
             if b.lazy is None or self.with_backward:      # a lazy sum is only ever written by the backward pass
                 base += _al(N * b.H * b.W * b.C * 4)
@@ -574,7 +609,89 @@ class PlanBuilder:
             self._needs_zero_grad.add(t.buf)
             written.setdefault(t.buf, []).append((t.coff, hi))
 
+    # Channel counts lhn_conv_pw_dw3_fwd is built for (csrc/k_conv_pwdw.hip: pw_dw3_supported); any map size.
+    FUSE_PW_DW_CHANNELS = (64,)
+
+    def _fusable_pw_dw(self, r, uses):
+        """The depthwise record that can share a launch with the 1x1 record r, or None.  The pair: a stride-1 1x1 of one plain
+        source into a whole, ungated buffer whose ONLY reader is a 3x3 depthwise convolution (stride 1, dilation 1, padding 1,
+        one source) over all of it, with channel counts the entry point accepts."""
+        if r["op"] != PW or r["stride"] != 1 or r["nchw"] or r["wrc"] != (0, 0) or r["bn_repeat"] != 1 or self._xs(r)[1] != 1:
+            return None
+        x, t = r["x"], r["out"]
+        tb = self.bufs[t.buf]
+        if x.buf < 0 or x.C not in self.FUSE_PW_DW_CHANNELS or t.C != x.C or t.coff != 0 or tb.C != t.C or tb.gate or tb.lazy is not None:
+            return None
+        if any(v is not None and v.buf == t.buf for v in (self.in_ref, self.out_ref)):
+            return None
+        if r["bn"] is not None and getattr(r["conv"], "bias", None) is not None:
+            return None
+        q = None
+        for u, key in uses.get(t.buf, ()):
+            if u is r and key == "out":
+                continue
+            if u["op"] == TABLE_FILL and key == "out":       # deployed form: the 1x1's pending activation
+                continue
+            if u["op"] == DW and key == "x" and q is None:
+                q = u
+                continue
+            return None
+        if q is None or (q["k"], q["stride"], q["pad"], q["dil"]) != (3, 1, 1, 1) or q["conv"].weight is None or \
+                q.get("bn_repeat", 1) != 1 or self._xs(q)[1] != 1:
+            return None
+        qx, y = q["x"], q["out"]
+        if (qx.coff, qx.C) != (0, t.C) or y.C != t.C or y.buf == t.buf:
+            return None
+        if q["bn"] is not None and getattr(q["conv"], "bias", None) is not None:
+            return None
+        if y.buf == x.buf and x.coff < y.coff + y.C and y.coff < x.coff + x.C:
+            return None
+        return q
+
+    def fuse_pw_dw(self):
+        """Inference plans with the switch on (infer_fuse): RepBasicUnit's right branch, RepConv 1x1 then RepConv depthwise 3x3
+        (litehourglass.py:52-78), becomes ONE launch.  Without train-mode BatchNorm the transform between the two convolutions
+        is known before the launch: it is written into the intermediate buffer's table by what fills it in the unfused plan
+        (eval: FINALIZE from the running statistics; deployed: TABLE_FILL with the 1x1's bias, which the unfused 1x1 adds while
+        storing), the fused kernel reads it as t_table, and the intermediate buffer gets no data.  Both table launches sit
+        under LHN_RUN_TABLES_CURRENT like every other.  Plans with a backward are never rewritten."""
+        if self.with_backward or not self.infer_fuse:
+            return 0
+        uses = {}
+        for r in self.recs:
+            for key, v in r.items():
+                for t in _refs_in(v):
+                    uses.setdefault(t.buf, []).append((r, key))
+        pairs = {}
+        for r in self.recs:
+            q = self._fusable_pw_dw(r, uses)
+            if q is not None:
+                pairs[id(q)] = r
+        drop = {id(r) for r in pairs.values()}
+        drop |= {id(u) for r in pairs.values() for u, key in uses[r["out"].buf] if u["op"] == TABLE_FILL and key == "out"}
+        recs = []
+        for q in self.recs:
+            if id(q) in drop:
+                continue
+            r = pairs.get(id(q))
+            if r is None:
+                recs.append(q)
+                continue
+            t = r["out"]
+            if r["bn"] is not None:
+                recs.append(dict(op=FINALIZE, out=t, bn=r["bn"], slope=r["slope"]))
+            elif r["conv"].bias is not None or r["slope"] != 1.0:
+                recs.append(dict(op=TABLE_FILL, out=t, bias=r["conv"].bias, slope=r["slope"]))
+            recs.append(dict(op=PWDW, x=r["x"], mid=t, out=q["out"], conv=r["conv"], conv2=q["conv"]))
+            if q["bn"] is not None:
+                recs.append(dict(op=FINALIZE, out=q["out"], bn=q["bn"], slope=q["slope"]))
+            self.bufs[t.buf].fused = True
+        self.recs = recs
+        self.n_fused += len(pairs)
+        return len(pairs)
+
     def finalize(self):
+        self.fuse_pw_dw()
         self._layout()
         N = self.N
         fwd, bwd = [], []
@@ -639,6 +756,13 @@ class PlanBuilder:
                 else:
                     fwd.append(mk(KXK, ins=(x,), out=out, p=(pw, cb) + pbn, ws=(tuple(wsl) + (-1, -1, -1))[:3] + (self._abs(r["wt"]),),
                                   i=(r["stride"],), f=fl))
+            elif k == PWDW:
+                fwd.append(mk(PWDW, ins=(r["x"], r["mid"]), out=r["out"], p=(self._p(r["conv"].weight), self._p(r["conv2"].weight))))
+            elif k == FINALIZE:      # eval-mode table of a convolution that runs inside a PWDW launch (no statistics to fold)
+                bn = r["bn"]
+                fwd.append(mk(FINALIZE, out=r["out"], p=(self._p(bn.weight), self._p(bn.bias), self._p(bn.running_mean),
+                                                         self._p(bn.running_var), self._p(bn.num_batches_tracked)),
+                              f=(bn.eps, bn.momentum, r["slope"])))
             elif k == EW:
                 if r.get("lazy") or r.get("fwd_fused"):
                     continue
