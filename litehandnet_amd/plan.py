@@ -36,6 +36,26 @@ STAT_REPLICAS = 32     # LHN_STAT_REPLICAS in include/lhn.h
 TICKET_WORDS = 33      # arrival counters of a fused finalize (lhn_bnfin.counter: one top word + 32 group words)
 
 
+# Plan switches: every one is on by default and NAME=0 in the environment turns it off.  They are read at every plan build (the
+# first two while the modules emit their records, the rest in finalize()), not once per process like the library's own.
+PLAN_SWITCHES = {
+    "LHN_COPY_POOL": "a gated RepBasicUnit's pass-through copy rides in the attention's pooling launch",
+    "LHN_GATE_BN_SUMS": "BatchNorm-backward sums of gated buffers come from the attention's backward",
+    "LHN_SUM_OUT": "the readers of a lazy residual sum also write it (no re-materialising combine in the backward)",
+    "LHN_GRAD_ADDENDS": "depthwise backward kernels add the gradient of a residual sum while storing dx",
+    "LHN_FUSE_BN_SUMS": "a producer's BatchNorm-backward sums ride in its only reader, a 3x3 depthwise backward",
+    "LHN_READER_BN_SUMS": "... or in all of its readers' backward kernels (combines, pools, the fused 1x1 backward)",
+    "LHN_POOL_GRAD_ADDS": "the max-pool backward also stores the gradients of the average pool and sum that read the same view",
+    "LHN_EW_BWD_MULTI": "same-resolution sources of a combine get their gradients in one launch",
+}
+
+
+def _switch(name):
+    """State of a plan switch, read from the environment now."""
+    assert name in PLAN_SWITCHES, name
+    return os.environ.get(name, "1") != "0"
+
+
 _INFER_FUSE = None     # set_infer_fuse(): in-process override of LHN_INFER_FUSE
 
 
@@ -60,6 +80,14 @@ def _refs_in(v):
     elif isinstance(v, (list, tuple)):
         for u in v:
             yield from _refs_in(u)
+
+
+def _reads(rec):
+    """The views a record's launch reads as data (an attention record reads and gates its own buffer: not listed)."""
+    k = rec["op"]
+    if k in (STEM, PW, DW, KXK, MAXPOOL, AVGPOOL):
+        return [rec["x"]]
+    return rec["srcs"] if k == EW else [rec["a"], rec["b"]] if k == SHUFFLE else []
 
 
 def _al(n):
@@ -131,7 +159,28 @@ class _IdentConv:
 _IDENT = _IdentConv()
 
 
+@dataclass
+class _BwdFusions:
+    """What the backward analyses of PlanBuilder._lower_backward decided, in the order they ran (each saw the ones above it),
+    and below them the two trackers the emitters fill while they walk the records in reverse."""
+    uses: dict                  # buffer -> records that read it (_reader_map)
+    aliased: set                # buffers whose gradient buffer is their only reader's (_alias_gradients)
+    pending_add: dict           # buffer -> [(id(sum record), the sum's output buffer, channel shift)] (_grad_addends)
+    bns: dict                   # (id(reader record), buf, coff, C) -> ((sums, save) offsets, (producer's C, channel offset)) (_reader_bn_sums)
+    fused_mp: dict = field(default_factory=dict)       # id(max-pool record) -> ((sum record, source index) | None, average-pool record | None)
+    skip_ew_src: set = field(default_factory=set)      # (id(sum record), source index) handled by a max-pool backward
+    skip_ap: set = field(default_factory=set)          # id(average-pool record) handled by a max-pool backward (_pool_grad_fusion)
+    written: dict = field(default_factory=dict)        # buffer -> channel ranges of its gradient written so far (_grad_mode)
+    materialised: set = field(default_factory=set)     # lazy sums the backward list has re-materialised so far
+
+    def bns_of(self, q, t):
+        """(ws pair, (C, coff)) of the BatchNorm sums reader record q adds for its input view t, or ((-1, -1), (0, 0))."""
+        return self.bns.get((id(q), t.buf, t.coff, t.C), ((-1, -1), (0, 0)))
+
+
 class PlanBuilder:
+    _no_grad_buf = -1   # the image never needs a gradient
+
     def __init__(self, N, state_index, image_hw=None, with_backward=True, p_drop=0.0, infer_fuse=None):
         self.N = N
         # inference fusion (fuse_pw_dw): None = the process-wide switch.  The fused launch has no batch statistics, so the
@@ -218,6 +267,20 @@ class PlanBuilder:
     def _p(self, t):
         return -1 if t is None else self.state_index[id(t)]
 
+    def _p_bn(self, bn):
+        """The five parameter slots of a BatchNorm."""
+        return tuple(self._p(t) for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked))
+
+    def _bn_ws(self, rec, C, out):
+        """Statistics work areas of a convolution + BatchNorm record over C channels (bump-allocated: the order is part of the layout)."""
+        rec["stats"] = self._ws("zf", STAT_REPLICAS * 2 * C * 8)
+        rec["cnt"] = self._ws("zf", 4 * TICKET_WORDS)
+        rec["save"] = self._ws("misc", 2 * C * 4)
+        if self.with_backward:
+            rec["sums"] = self._ws("zb", STAT_REPLICAS * 2 * C * 8)
+            rec["bcnt"] = self._ws("zb", 4 * TICKET_WORDS)
+            self.bufs[out.buf].coef = True
+
     # ------------------------------------------------------------------ forward emitters
     def conv(self, x, conv, bn=None, slope=1.0, out=None, nchw_out=False, stack=None, bn_repeat=1):
         """conv (+ train/eval BatchNorm + leaky slope as a pending transform).  Returns the output view.
@@ -271,14 +334,7 @@ class PlanBuilder:
         if kind == KXK:
             rec["wt"] = self._ws("misc", 9 * cout * cin_g * 4)      # tap-major weight scratch (lhn_conv_kxk_*: wt_scratch)
         if bn is not None:
-            sc = max(cout, cpad)        # statistics are laid out for the (padded) output view
-            rec["stats"] = self._ws("zf", STAT_REPLICAS * 2 * sc * 8)
-            rec["cnt"] = self._ws("zf", 4 * TICKET_WORDS)
-            rec["save"] = self._ws("misc", 2 * sc * 4)
-            if self.with_backward:
-                rec["sums"] = self._ws("zb", STAT_REPLICAS * 2 * sc * 8)
-                rec["bcnt"] = self._ws("zb", 4 * TICKET_WORDS)
-                self.bufs[out.buf].coef = True
+            self._bn_ws(rec, max(cout, cpad), out)        # statistics are laid out for the (padded) output view
         self.recs.append(rec)
         if bn is None and not nchw_out:
             # BN-free conv (deployed RepConv/RepBlock, repblocks.py:41-43,118-119): bias and activation stay pending
@@ -297,13 +353,7 @@ class PlanBuilder:
         x = self.real(self.single(x))
         out = self.new(x.H, x.W, x.C)
         rec = dict(op=DW, x=x, out=out, conv=_IDENT, bn=bn, slope=float(slope), k=1, stride=1, pad=0, dil=1, nchw=False)
-        rec["stats"] = self._ws("zf", STAT_REPLICAS * 2 * x.C * 8)
-        rec["cnt"] = self._ws("zf", 4 * TICKET_WORDS)
-        rec["save"] = self._ws("misc", 2 * x.C * 4)
-        if self.with_backward:
-            rec["sums"] = self._ws("zb", STAT_REPLICAS * 2 * x.C * 8)
-            rec["bcnt"] = self._ws("zb", 4 * TICKET_WORDS)
-            self.bufs[out.buf].coef = True
+        self._bn_ws(rec, x.C, out)
         self.recs.append(rec)
         return out
 
@@ -429,7 +479,7 @@ class PlanBuilder:
                   q.get("coefs") is None and not isinstance(q["out"], TCat) and q["out"].buf == y.buf]
         writers = [q for q in self.recs if q["op"] in (STEM, PW, DW, KXK, MAXPOOL, AVGPOOL, SHUFFLE) and
                    q.get("out") is not None and not isinstance(q["out"], TCat) and q["out"].buf == y.buf]
-        if os.environ.get("LHN_COPY_POOL", "1") != "0" and len(copies) == 1 and not hasattr(ca, "rbr_reparam"):
+        if _switch("LHN_COPY_POOL") and len(copies) == 1 and not hasattr(ca, "rbr_reparam"):
             q = copies[0]
             src = q["srcs"][0] if len(q["srcs"]) == 1 else None
             if src is not None and not isinstance(src, TCat) and src.buf >= 0 and src.buf != y.buf and q["slope"] == 1.0 and \
@@ -446,7 +496,7 @@ class PlanBuilder:
             # over the feature map and its gradient disappear.  LHN_GATE_BN_SUMS=0: separate passes.
             prods = [q for q in self.recs if q["op"] in (STEM, PW, DW, KXK) and q["bn"] is not None and
                      not isinstance(q["out"], TCat) and q["out"].buf == y.buf]
-            if os.environ.get("LHN_GATE_BN_SUMS", "1") != "0" and 1 <= len(prods) <= 2 and not hasattr(ca, "rbr_reparam") and \
+            if _switch("LHN_GATE_BN_SUMS") and 1 <= len(prods) <= 2 and not hasattr(ca, "rbr_reparam") and \
                     all(not q.get("wrc", (0, 0))[0] and q.get("bn_repeat", 1) == 1 for q in prods):
                 rec["bnslices"] = prods
                 rec["pstat"] = self._ws("misc", self.N * 9 * 2 * Cc * 4)
@@ -549,14 +599,9 @@ class PlanBuilder:
             o.out_buf, o.out_coff, o.out_C = out.buf, out.coff, out.C
         else:
             o.out_buf = -1
-        for k in range(12):
-            o.p[k] = p[k] if k < len(p) else -1
-        for k in range(12):
-            o.ws[k] = ws[k] if k < len(ws) else -1
-        for k in range(8):
-            o.i[k] = i[k] if k < len(i) else 0
-        for k in range(8):
-            o.f[k] = f[k] if k < len(f) else 0.0
+        for slot, vals, fill in ((o.p, p, -1), (o.ws, ws, -1), (o.i, i, 0), (o.f, f, 0.0)):
+            for k in range(len(slot)):
+                slot[k] = vals[k] if k < len(vals) else fill
         return o
 
     def _xs(self, r):
@@ -690,538 +735,582 @@ class PlanBuilder:
         self.n_fused += len(pairs)
         return len(pairs)
 
+    # ------------------------------------------------------------------ finalize: the passes in the order they run
     def finalize(self):
+        """Lower the records to what lhn_plan_create takes: (Buf array, forward Op array, backward Op array or None, n_fwd, n_bwd)."""
         self.fuse_pw_dw()
         self._layout()
-        N = self.N
-        fwd, bwd = [], []
-        mk = self._mk
-        # ---------------- forward
-        if self.ar["zf"].size:
-            fwd.append(mk(MEMSET, ws=(self.arena_base["zf"], self.ar["zf"].size)))
-        # Plans with a backward: a convolution that sums a lazy residual on load also WRITES the sum (lhn_pw_opts.sum_out) when
-        # the readers' channel slices cover the buffer -- the weight gradients of the backward then find it in memory and the
-        # re-materialising combine (which re-reads every operand) is not needed.  LHN_SUM_OUT=0: re-materialise.
+        self._plan_sum_out()
+        fwd = self._lower_forward()
+        bwd = self._lower_backward() if self.with_backward else []
+        self.sync_points = self._sync_points(fwd, bwd)
+        return self._c_arrays(fwd, bwd)
+
+    def _plan_sum_out(self):
+        """Plans with a backward: a convolution that sums a lazy residual on load also WRITES the sum (lhn_pw_opts.sum_out) when
+        the readers' channel slices cover the buffer -- the weight gradients of the backward then find it in memory and the
+        re-materialising combine (which re-reads every operand) is not needed.  LHN_SUM_OUT=0: re-materialise."""
         self.sum_out = {}               # id(conv record) -> (byte offset of the sum's buffer, pixel stride * 65536 + channel)
         self._sum_written = set()       # lazy buffers complete after the forward
-        if self.with_backward and os.environ.get("LHN_SUM_OUT", "1") != "0":
-            cover = {}
-            for r in self.recs:
-                if r["op"] not in (PW, DW) or isinstance(r["x"], TCat):
-                    continue
-                x = r["x"]
-                if self._xs(r)[1] < 2 or (r["op"] == PW and (x.C > 128 or r["out"].C > 128)):
-                    continue
-                spans = cover.setdefault(x.buf, [])
-                if any(a < x.coff + x.C and x.coff < b for a, b, _ in spans):
-                    continue
-                spans.append((x.coff, x.coff + x.C, r))
-            for b, spans in cover.items():
-                spans.sort(key=lambda t: t[0])
-                C = self.bufs[b].C
-                if spans[0][0] != 0 or spans[-1][1] != C or any(p[1] != q[0] for p, q in zip(spans, spans[1:])):
-                    continue
-                self._sum_written.add(b)
-                for lo, hi, r in spans:
-                    self.sum_out[id(r)] = (self.bufs[b].off["data"], C * 65536 + lo)
+        if not (self.with_backward and _switch("LHN_SUM_OUT")):
+            return
+        cover = {}
         for r in self.recs:
-            k = r["op"]
-            if k in (STEM, PW, DW, KXK):
-                conv, bn, x, out = r["conv"], r["bn"], r["x"], r["out"]
-                stats = self._abs(r.get("stats"))
-                so = self.sum_out.get(id(r), (-1, -1))
-                pw = self._p(conv.weight)
-                # a trailing BatchNorm rides on the conv op: the last workgroup of the conv finalizes the table
-                if bn is not None:
-                    pbn = (self._p(bn.weight), self._p(bn.bias), self._p(bn.running_mean), self._p(bn.running_var),
-                           self._p(bn.num_batches_tracked))
-                    wsl = (stats, self._abs(r["save"]), self._abs(r["cnt"]))
-                    fl = (bn.eps, bn.momentum, r["slope"], float(r.get("bn_repeat", 1)))
-                else:
-                    pbn, wsl, fl = (-1, -1, -1, -1, -1), (stats,), ()
-                cb = self._p(getattr(conv, "bias", None)) if bn is not None else -1   # biased conv + BN: bias goes to the finalize
-                if k == STEM:
-                    fwd.append(mk(STEM, out=out, p=(pw, cb) + pbn, ws=wsl, i=(r["k"], r["stride"], r["pad"], x.H, x.W), f=fl))
-                elif k == PW:
-                    o = TRef(-1, 0, out.C, out.H, out.W) if r["nchw"] else out
-                    xv, nx, cf = self._xs(r)
-                    fwd.append(mk(PW, ins=xv, out=o, p=(pw, self._p(conv.bias)) + pbn, ws=(tuple(wsl) + (-1,) * 4)[:4] + so,
-                                  i=(r["stride"], 1 if r["nchw"] else 0, r["wrc"][0], r["wrc"][1], r["stack"][0], r["stack"][1], nx),
-                                  f=(tuple(fl) + (0.0,) * 4)[:4] + tuple(cf)))
-                elif k == DW:
-                    xv, nx, cf = self._xs(r)
-                    fwd.append(mk(DW, ins=xv, out=out, p=(pw, cb) + pbn, ws=(tuple(wsl) + (-1,) * 4)[:4] + so,
-                                  i=(r["k"], r["stride"], r["pad"], r["dil"], 0, 0, nx),
-                                  f=(tuple(fl) + (0.0,) * 4)[:4] + tuple(cf)))
-                else:
-                    fwd.append(mk(KXK, ins=(x,), out=out, p=(pw, cb) + pbn, ws=(tuple(wsl) + (-1, -1, -1))[:3] + (self._abs(r["wt"]),),
-                                  i=(r["stride"],), f=fl))
-            elif k == PWDW:
-                fwd.append(mk(PWDW, ins=(r["x"], r["mid"]), out=r["out"], p=(self._p(r["conv"].weight), self._p(r["conv2"].weight))))
-            elif k == FINALIZE:      # eval-mode table of a convolution that runs inside a PWDW launch (no statistics to fold)
-                bn = r["bn"]
-                fwd.append(mk(FINALIZE, out=r["out"], p=(self._p(bn.weight), self._p(bn.bias), self._p(bn.running_mean),
-                                                         self._p(bn.running_var), self._p(bn.num_batches_tracked)),
-                              f=(bn.eps, bn.momentum, r["slope"])))
-            elif k == EW:
-                if r.get("lazy") or r.get("fwd_fused"):
-                    continue
-                if "flat" in r:
-                    # a lazy sum that had to be materialised after all (a reader that cannot add on load): launched on the
-                    # flattened operand list -- an operand that is itself a lazy sum has never been written
-                    fl = r["flat"]
-                    fwd.append(mk(EW, ins=[t for t, _ in fl], out=r["out"], i=(len(fl), 1), f=(r["slope"], 0.0, 0.0, 0.0) + tuple(c for _, c in fl)))
-                elif r.get("mode") or r.get("coefs") is not None:
-                    cf = r["coefs"] or [1.0] * len(r["srcs"])
-                    fwd.append(mk(EW, ins=r["srcs"], out=r["out"], i=(len(r["srcs"]), 1, r.get("mode", 0)),
-                                  f=(r["slope"], 0.0, 0.0, 0.0) + tuple(cf)))
-                else:
-                    fwd.append(mk(EW, ins=r["srcs"], out=r["out"], i=(len(r["srcs"]),), f=(r["slope"],)))
-            elif k == SHUFFLE:
-                fwd.append(mk(SHUFFLE, ins=(r["a"], r["b"]), out=r["out"]))
-            elif k == MAXPOOL:
-                fwd.append(mk(MAXPOOL, ins=(r["x"],), out=r["out"]))
-            elif k == AVGPOOL:
-                ob = self.bufs[r["out"].buf]
-                fwd.append(mk(AVGPOOL, ins=(r["x"],), ws=(ob.off["data"],), i=(r["OH"], r["OW"], 0, ob.C, r["out"].coff)))
-            elif k == TABLE_FILL:
-                fwd.append(mk(TABLE_FILL, out=r["out"], p=(self._p(r["bias"]),), i=(1,), f=(1.0, 0.0, r["slope"])))
-            elif k == CA_MLP and hasattr(r["ca"], "rbr_reparam"):
-                y, ca = r["y"], r["ca"]
-                if self.with_backward:
-                    raise _lib.LhnError("deployed ChannelAttension is inference-only")
-                fwd.append(mk(AVGPOOL, ins=(y,), ws=(self._abs(r["pooled"]),), i=(3, 3, 1)))
-                fwd.append(mk(CA_MLP, out=y,
-                              p=(self._p(ca.rbr_reparam.weight), -1, self._p(ca.rbr_reparam.bias), -1, -1, -1,
-                                 self._p(ca.conv1x1[1].weight), self._p(ca.conv1x1[1].bias),
-                                 self._p(ca.conv1x1[3].weight), self._p(ca.conv1x1[3].bias)),
-                              ws=(self._abs(r["pooled"]), self._abs(r["save"]), self._abs(r["mask"])),
-                              f=(1e-5, 0.1)))
-            elif k == SE_MLP:
-                y, dn, up = r["y"], r["down"], r["up"]
-                fwd.append(mk(AVGPOOL, ins=(y,), ws=(self._abs(r["pooled"]),), i=(1, 1, 1)))
-                fwd.append(mk(SE_MLP, out=y, p=(self._p(dn.weight), self._p(dn.bias), self._p(up.weight), self._p(up.bias)),
-                              ws=(self._abs(r["pooled"]), self._abs(r["save"])), i=(r["J"], r["mode"])))
-            elif k == ATT_MLP:
-                y, att = r["y"], r["att"]
-                bn, dw, lin = att[1], att[3], att[6]
-                fwd.append(mk(AVGPOOL, ins=(y,), ws=(self._abs(r["pooled"]),), i=(3, 3, 1)))
-                fwd.append(mk(ATT_MLP, out=y,
-                              p=(self._p(bn.weight), self._p(bn.bias), self._p(bn.running_mean), self._p(bn.running_var),
-                                 self._p(bn.num_batches_tracked), self._p(dw.weight), self._p(dw.bias),
-                                 self._p(lin.weight), self._p(lin.bias)),
-                              ws=(self._abs(r["pooled"]), self._abs(r["save"]), self._abs(r["mask"]), self._abs(r["gsum"])),
-                              f=(bn.eps, bn.momentum)))
-            elif k == CA_MLP:
-                y, ca = r["y"], r["ca"]
-                sl = r.get("bnslices")
-                pins = (y, r["copy"]["srcs"][0]) if r.get("copy") else (y,)       # second input: pass-through half copied by this launch
-                if sl:      # pooling pass that also leaves M0, M1 per (n, bin, c) for the backward (lhn_avgpool_fwd4)
-                    fwd.append(mk(AVGPOOL, ins=pins, ws=(self._abs(r["pooled"]), self._abs(r["pstat"])) + tuple(self._abs(q["save"]) for q in sl),
-                                  i=(3, 3, 1, 0, 0) + tuple((q["out"].coff << 16) | q["out"].C for q in sl)))
-                else:
-                    fwd.append(mk(AVGPOOL, ins=pins, ws=(self._abs(r["pooled"]),), i=(3, 3, 1)))
-                bn = ca.conv3x3.bn
-                fwd.append(mk(CA_MLP, out=y,
-                              p=(self._p(ca.conv3x3.conv.weight), self._p(bn.weight), self._p(bn.bias),
-                                 self._p(bn.running_mean), self._p(bn.running_var), self._p(bn.num_batches_tracked),
-                                 self._p(ca.conv1x1[1].weight), self._p(ca.conv1x1[1].bias),
-                                 self._p(ca.conv1x1[3].weight), self._p(ca.conv1x1[3].bias)),
-                              ws=(self._abs(r["pooled"]), self._abs(r["save"]), self._abs(r["mask"]), self._abs(r["gsum"])),
-                              f=(bn.eps, bn.momentum)))
-            else:
-                raise AssertionError(k)
-        # (round 2's deferred finalize -- the first reader of a convolution folding the replicated statistics in its prologue --
-        # was measured slower than the separate ~5 us launch and is gone: DESIGN.md section 5.2; the kernels' lhn_pend inputs stay
-        # empty)
-        # ---------------- backward
-        if self.with_backward:
-            written = {}
-            self._needs_zero_grad = set()
-            body = []
-            # Gradient aliasing: a source of a plain (slope 1, same-size, whole-buffer) combine whose ONLY reader is
-            # that combine receives exactly d(out) -- its gradient buffer becomes an alias of the output's and the
-            # copy launch disappears (MSRB: the gated branch buffer of every residual add).
-            uses = {}
-            for r in self.recs:
-                for t in ([r["x"]] if r["op"] in (PW, DW, KXK, MAXPOOL, AVGPOOL) else r["srcs"] if r["op"] == EW else
-                          [r["a"], r["b"]] if r["op"] == SHUFFLE else []):
+            if r["op"] not in (PW, DW) or isinstance(r["x"], TCat):
+                continue
+            x = r["x"]
+            if self._xs(r)[1] < 2 or (r["op"] == PW and (x.C > 128 or r["out"].C > 128)):
+                continue
+            spans = cover.setdefault(x.buf, [])
+            if any(a < x.coff + x.C and x.coff < b for a, b, _ in spans):
+                continue
+            spans.append((x.coff, x.coff + x.C, r))
+        for b, spans in cover.items():
+            spans.sort(key=lambda t: t[0])
+            C = self.bufs[b].C
+            if spans[0][0] != 0 or spans[-1][1] != C or any(p[1] != q[0] for p, q in zip(spans, spans[1:])):
+                continue
+            self._sum_written.add(b)
+            for lo, hi, r in spans:
+                self.sum_out[id(r)] = (self.bufs[b].off["data"], C * 65536 + lo)
+
+    # ------------------------------------------------------------------ forward lowering: one emitter per record family -> [Op]
+    def _lower_forward(self):
+        emit = {STEM: self._fwd_conv, PW: self._fwd_conv, DW: self._fwd_conv, KXK: self._fwd_conv, PWDW: self._fwd_pwdw,
+                FINALIZE: self._fwd_table, TABLE_FILL: self._fwd_table, EW: self._fwd_ew, SHUFFLE: self._fwd_pool,
+                MAXPOOL: self._fwd_pool, AVGPOOL: self._fwd_pool, CA_MLP: self._fwd_ca, SE_MLP: self._fwd_se, ATT_MLP: self._fwd_att}
+        fwd = [self._mk(MEMSET, ws=(self.arena_base["zf"], self.ar["zf"].size))] if self.ar["zf"].size else []
+        for r in self.recs:
+            fwd += emit[r["op"]](r)
+        return fwd
+
+    def _fwd_conv(self, r):
+        mk = self._mk
+        k, conv, bn, x, out = r["op"], r["conv"], r["bn"], r["x"], r["out"]
+        stats = self._abs(r.get("stats"))
+        so = self.sum_out.get(id(r), (-1, -1))
+        pw = self._p(conv.weight)
+        # a trailing BatchNorm rides on the conv op: the last workgroup of the conv finalizes the table
+        if bn is not None:
+            pbn = self._p_bn(bn)
+            wsl = (stats, self._abs(r["save"]), self._abs(r["cnt"]))
+            fl = (bn.eps, bn.momentum, r["slope"], float(r.get("bn_repeat", 1)))
+        else:
+            pbn, wsl, fl = (-1, -1, -1, -1, -1), (stats,), ()
+        cb = self._p(getattr(conv, "bias", None)) if bn is not None else -1   # biased conv + BN: bias goes to the finalize
+        if k == STEM:
+            return [mk(STEM, out=out, p=(pw, cb) + pbn, ws=wsl, i=(r["k"], r["stride"], r["pad"], x.H, x.W), f=fl)]
+        if k == KXK:
+            return [mk(KXK, ins=(x,), out=out, p=(pw, cb) + pbn, ws=(tuple(wsl) + (-1, -1, -1))[:3] + (self._abs(r["wt"]),),
+                       i=(r["stride"],), f=fl)]
+        xv, nx, cf = self._xs(r)
+        ws, f = (tuple(wsl) + (-1,) * 4)[:4] + so, (tuple(fl) + (0.0,) * 4)[:4] + tuple(cf)
+        if k == PW:
+            o = TRef(-1, 0, out.C, out.H, out.W) if r["nchw"] else out
+            return [mk(PW, ins=xv, out=o, p=(pw, self._p(conv.bias)) + pbn, ws=ws, f=f,
+                       i=(r["stride"], 1 if r["nchw"] else 0, r["wrc"][0], r["wrc"][1], r["stack"][0], r["stack"][1], nx))]
+        return [mk(DW, ins=xv, out=out, p=(pw, cb) + pbn, ws=ws, i=(r["k"], r["stride"], r["pad"], r["dil"], 0, 0, nx), f=f)]
+
+    def _fwd_pwdw(self, r):
+        return [self._mk(PWDW, ins=(r["x"], r["mid"]), out=r["out"], p=(self._p(r["conv"].weight), self._p(r["conv2"].weight)))]
+
+    def _fwd_table(self, r):
+        """FINALIZE: eval-mode table of a convolution that runs inside a PWDW launch (no statistics to fold); TABLE_FILL: the
+        pending bias / activation of a BatchNorm-free convolution."""
+        if r["op"] == FINALIZE:
+            bn = r["bn"]
+            return [self._mk(FINALIZE, out=r["out"], p=self._p_bn(bn), f=(bn.eps, bn.momentum, r["slope"]))]
+        return [self._mk(TABLE_FILL, out=r["out"], p=(self._p(r["bias"]),), i=(1,), f=(1.0, 0.0, r["slope"]))]
+
+    def _fwd_ew(self, r):
+        mk = self._mk
+        if r.get("lazy") or r.get("fwd_fused"):
+            return []
+        if "flat" in r:
+            # a lazy sum that had to be materialised after all (a reader that cannot add on load): launched on the
+            # flattened operand list -- an operand that is itself a lazy sum has never been written
+            fl = r["flat"]
+            return [mk(EW, ins=[t for t, _ in fl], out=r["out"], i=(len(fl), 1), f=(r["slope"], 0.0, 0.0, 0.0) + tuple(c for _, c in fl))]
+        if r.get("mode") or r.get("coefs") is not None:
+            cf = r["coefs"] or [1.0] * len(r["srcs"])
+            return [mk(EW, ins=r["srcs"], out=r["out"], i=(len(r["srcs"]), 1, r.get("mode", 0)), f=(r["slope"], 0.0, 0.0, 0.0) + tuple(cf))]
+        return [mk(EW, ins=r["srcs"], out=r["out"], i=(len(r["srcs"]),), f=(r["slope"],))]
+
+    def _fwd_pool(self, r):
+        """Pools and the channel shuffle: data movement without parameters."""
+        if r["op"] == SHUFFLE:
+            return [self._mk(SHUFFLE, ins=(r["a"], r["b"]), out=r["out"])]
+        if r["op"] == MAXPOOL:
+            return [self._mk(MAXPOOL, ins=(r["x"],), out=r["out"])]
+        ob = self.bufs[r["out"].buf]
+        return [self._mk(AVGPOOL, ins=(r["x"],), ws=(ob.off["data"],), i=(r["OH"], r["OW"], 0, ob.C, r["out"].coff))]
+
+    def _fwd_ca(self, r):
+        mk = self._mk
+        y, ca = r["y"], r["ca"]
+        mlp = (self._p(ca.conv1x1[1].weight), self._p(ca.conv1x1[1].bias), self._p(ca.conv1x1[3].weight), self._p(ca.conv1x1[3].bias))
+        if hasattr(ca, "rbr_reparam"):
+            if self.with_backward:
+                raise _lib.LhnError("deployed ChannelAttension is inference-only")
+            return [mk(AVGPOOL, ins=(y,), ws=(self._abs(r["pooled"]),), i=(3, 3, 1)),
+                    mk(CA_MLP, out=y, p=(self._p(ca.rbr_reparam.weight), -1, self._p(ca.rbr_reparam.bias), -1, -1, -1) + mlp,
+                       ws=(self._abs(r["pooled"]), self._abs(r["save"]), self._abs(r["mask"])), f=(1e-5, 0.1))]
+        sl = r.get("bnslices")
+        pins = (y, r["copy"]["srcs"][0]) if r.get("copy") else (y,)       # second input: pass-through half copied by this launch
+        if sl:      # pooling pass that also leaves M0, M1 per (n, bin, c) for the backward (lhn_avgpool_fwd4)
+            pool = mk(AVGPOOL, ins=pins, ws=(self._abs(r["pooled"]), self._abs(r["pstat"])) + tuple(self._abs(q["save"]) for q in sl),
+                      i=(3, 3, 1, 0, 0) + tuple((q["out"].coff << 16) | q["out"].C for q in sl))
+        else:
+            pool = mk(AVGPOOL, ins=pins, ws=(self._abs(r["pooled"]),), i=(3, 3, 1))
+        bn = ca.conv3x3.bn
+        return [pool, mk(CA_MLP, out=y, p=(self._p(ca.conv3x3.conv.weight),) + self._p_bn(bn) + mlp,
+                         ws=(self._abs(r["pooled"]), self._abs(r["save"]), self._abs(r["mask"]), self._abs(r["gsum"])),
+                         f=(bn.eps, bn.momentum))]
+
+    def _fwd_se(self, r):
+        y, dn, up = r["y"], r["down"], r["up"]
+        return [self._mk(AVGPOOL, ins=(y,), ws=(self._abs(r["pooled"]),), i=(1, 1, 1)),
+                self._mk(SE_MLP, out=y, p=(self._p(dn.weight), self._p(dn.bias), self._p(up.weight), self._p(up.bias)),
+                         ws=(self._abs(r["pooled"]), self._abs(r["save"])), i=(r["J"], r["mode"]))]
+
+    def _fwd_att(self, r):
+        y, att = r["y"], r["att"]
+        bn, dw, lin = att[1], att[3], att[6]
+        return [self._mk(AVGPOOL, ins=(y,), ws=(self._abs(r["pooled"]),), i=(3, 3, 1)),
+                self._mk(ATT_MLP, out=y, p=self._p_bn(bn) + (self._p(dw.weight), self._p(dw.bias), self._p(lin.weight), self._p(lin.bias)),
+                         ws=(self._abs(r["pooled"]), self._abs(r["save"]), self._abs(r["mask"]), self._abs(r["gsum"])),
+                         f=(bn.eps, bn.momentum))]
+
+    # ------------------------------------------------------------------ backward lowering
+    def _lower_backward(self):
+        """The backward op list: the analyses (each one consults the results of those above it), then one emitter per record
+        family over the records in REVERSE order -- the emitters share the written-range tracker (_grad_mode / _covered), so
+        their order and the order of their tracker calls inside one record decide store against accumulate."""
+        self._needs_zero_grad = set()
+        self.grad_aliases = self.grad_addends = self.fused_bn_sums = self.reader_bn_sums = self.pool_grad_adds = self.ew_bwd_multi = 0
+        for r in self.recs:                     # (not sums_by_ca: the attention record set it while the modules emitted)
+            r.pop("sums_by_reader", None)
+            r.pop("sums_by_readers", None)
+        uses = self._reader_map()
+        aliased = self._alias_gradients(uses)
+        pending_add = self._grad_addends(uses, aliased)
+        fz = _BwdFusions(uses, aliased, pending_add, self._reader_bn_sums(uses, aliased, pending_add))
+        fz.fused_mp, fz.skip_ew_src, fz.skip_ap = self._pool_grad_fusion(pending_add, fz.bns_of)
+        emit = {STEM: self._bwd_conv, PW: self._bwd_conv, DW: self._bwd_conv, KXK: self._bwd_conv, EW: self._bwd_ew,
+                SHUFFLE: self._bwd_shuffle, MAXPOOL: self._bwd_maxpool, AVGPOOL: self._bwd_avgpool,
+                CA_MLP: self._bwd_ca, SE_MLP: self._bwd_se, ATT_MLP: self._bwd_att}
+        body = []
+        for r in reversed(self.recs):
+            if r["op"] in (STEM, PW, DW, KXK, EW, SHUFFLE, MAXPOOL, AVGPOOL) and not (r["op"] == PW and r.get("nchw")) and \
+                    not (self.out_ref is not None and not isinstance(r["out"], TCat) and r["out"].buf == self.out_ref.buf):
+                self._covered(fz.written, r["out"])      # (the block output's gradient is written by the engine, not by an op)
+            body += emit[r["op"]](r, fz)
+        bwd = [self._mk(MEMSET, ws=(self.arena_base["zb"], self.ar["zb"].size))] if self.ar["zb"].size else []
+        for b in sorted(self._needs_zero_grad):
+            rec = self.bufs[b]
+            bwd.append(self._mk(MEMSET, ws=(rec.off["grad"], self.N * rec.H * rec.W * rec.C * 4)))
+        self._force_accumulate(body)
+        return bwd + body
+
+    def _reader_map(self):
+        """buffer -> the records that read it, in record order (one entry per reading view)."""
+        uses = {}
+        for r in self.recs:
+            for t in _reads(r):
+                if t.buf >= 0:
                     uses.setdefault(t.buf, []).append(r)
-            aliased = set()
-            self._alias_of = {}
-            for r in reversed(self.recs):
-                if r["op"] != EW or r["slope"] != 1.0 or r.get("mode") or r.get("coefs") is not None:
+        return uses
+
+    def _alias_gradients(self, uses):
+        """Gradient aliasing: a source of a plain (slope 1, same-size, whole-buffer) combine whose ONLY reader is that combine
+        receives exactly d(out) -- its gradient buffer becomes an alias of the output's and the copy launch disappears (MSRB:
+        the gated branch buffer of every residual add).  Returns the aliased buffers; self._alias_of maps each to its combine's."""
+        aliased = set()
+        self._alias_of = {}
+        for r in reversed(self.recs):
+            if r["op"] != EW or r["slope"] != 1.0 or r.get("mode") or r.get("coefs") is not None:
+                continue
+            out = r["out"]
+            ob = self.bufs[out.buf]
+            if out.coff != 0 or out.C != ob.C or ob.gate or ob.dpool:
+                continue
+            for t in r["srcs"]:
+                if t.buf < 0 or t.buf == out.buf or t.buf in aliased or len(uses.get(t.buf, ())) != 1:
                     continue
-                out = r["out"]
-                ob = self.bufs[out.buf]
-                if out.coff != 0 or out.C != ob.C or ob.gate or ob.dpool:
+                tb = self.bufs[t.buf]
+                if (self.in_ref is not None and t.buf == self.in_ref.buf) or t.coff != 0 or t.C != tb.C:
                     continue
-                for t in r["srcs"]:
-                    if t.buf < 0 or t.buf == out.buf or t.buf in aliased or len(uses.get(t.buf, ())) != 1:
-                        continue
-                    tb = self.bufs[t.buf]
-                    if (self.in_ref is not None and t.buf == self.in_ref.buf) or t.coff != 0 or t.C != tb.C:
-                        continue
-                    if (t.H, t.W) != (out.H, out.W) or sum(1 for q in r["srcs"] if q.buf == t.buf) != 1:
-                        continue
-                    tb.off["grad"] = ob.off["grad"]
-                    aliased.add(t.buf)
-                    self._alias_of[t.buf] = out.buf
-            self.grad_aliases = len(aliased)
-            materialised = set()
-            # Gradient addends: a plain residual sum O = S + ... hands d(O) to every source.  When S's other readers are
-            # tiled depthwise convolutions whose input slices tile S exactly (MSRB: `out` feeds the two dilated 3x3 halves
-            # and the running sum, litehourglass.py:41-49), those convolutions' backward kernels add d(O) while storing
-            # their dx (include/lhn.h: lhn_conv_dw_bwd3) and the sum's copy / accumulate pass over S's gradient disappears.
-            pending_add, self.grad_addends = {}, 0
-            if os.environ.get("LHN_GRAD_ADDENDS", "1") != "0":
-                order = {id(q): j for j, q in enumerate(self.recs)}
+                if (t.H, t.W) != (out.H, out.W) or sum(1 for q in r["srcs"] if q.buf == t.buf) != 1:
+                    continue
+                tb.off["grad"] = ob.off["grad"]
+                aliased.add(t.buf)
+                self._alias_of[t.buf] = out.buf
+        self.grad_aliases = len(aliased)
+        return aliased
 
-                def plain_sum(q):
-                    return q["op"] == EW and q["slope"] == 1.0 and not q.get("mode") and q.get("coefs") is None and \
-                        not isinstance(q["out"], TCat)
+    def _grad_addends(self, uses, aliased):
+        """Gradient addends: a plain residual sum O = S + ... hands d(O) to every source.  When S's other readers are
+        tiled depthwise convolutions whose input slices tile S exactly (MSRB: `out` feeds the two dilated 3x3 halves
+        and the running sum, litehourglass.py:41-49), those convolutions' backward kernels add d(O) while storing
+        their dx (include/lhn.h: lhn_conv_dw_bwd3) and the sum's copy / accumulate pass over S's gradient disappears.
+        Returns S's buffer -> [(id(sum record), O's buffer, channel shift)]."""
+        pending_add = {}
+        if not _switch("LHN_GRAD_ADDENDS"):
+            return pending_add
+        order = {id(q): j for j, q in enumerate(self.recs)}
 
-                for sb, rd in uses.items():
-                    if sb < 0 or sb in aliased or sb == self._no_grad_buf:
-                        continue
-                    sums = [q for q in rd if plain_sum(q)]
-                    dws = [q for q in rd if not plain_sum(q)]
-                    if not sums or not dws or len(sums) > 2:
-                        continue
-                    if not all(q["op"] == DW and q["conv"].weight is not None and q["stride"] == 1 and q["k"] == 3 and
-                               q["pad"] == q["dil"] and q["x"].C % 32 == 0 and q["x"].W >= 8 and not isinstance(q["x"], TCat)
-                               for q in dws):
-                        continue
-                    if min(order[id(q)] for q in sums) < max(order[id(q)] for q in dws):
-                        continue
-                    spans = sorted((q["x"].coff, q["x"].coff + q["x"].C) for q in dws)
-                    lo, hi = spans[0][0], spans[-1][1]
-                    if any(a[1] != b[0] for a, b in zip(spans, spans[1:])):
-                        continue
-                    adds = []
-                    for q in sums:
-                        mine = [t for t in q["srcs"] if not isinstance(t, TCat) and t.buf == sb]
-                        o = q["out"]
-                        if len(mine) != 1 or (mine[0].coff, mine[0].C) != (lo, hi - lo) or (mine[0].H, mine[0].W) != (o.H, o.W) or \
-                                self.bufs[o.buf].C != self.bufs[sb].C:
-                            break
-                        adds.append((id(q), o.buf, o.coff - lo))
-                    else:
-                        pending_add[sb] = adds
-            fuse_sums = os.environ.get("LHN_FUSE_BN_SUMS", "1") != "0"
-            self.fused_bn_sums = 0
-            for r in self.recs:
-                r.pop("sums_by_reader", None)
-                r.pop("sums_by_readers", None)
-            # Reader-side BatchNorm sums, general form (include/lhn.h: lhn_bnsum): du is linear in dz and dz is the sum of what the
-            # readers' backward kernels hand back, so when EVERY reader of a convolution + BatchNorm output can add its part
-            # (elementwise combines, pools, the fused 1x1 backward) the producer's lhn_bn_bwd_reduce pass is not launched.
-            # bns[(id(reader record), buf, coff, C)] = (producer record, channel offset inside the producer's BatchNorm)
-            bns = {}
-            self.reader_bn_sums = 0
-            if os.environ.get("LHN_READER_BN_SUMS", "1") != "0":
-                for P in self.recs:
-                    if P["op"] not in (STEM, PW, DW, KXK) or P["bn"] is None or P.get("sums_by_ca") or isinstance(P["out"], TCat):
-                        continue
-                    o = P["out"]
-                    if o.buf < 0 or P.get("wrc", (0, 0))[0] or P.get("bn_repeat", 1) != 1 or o.buf in aliased:
-                        continue
-                    ob = self.bufs[o.buf]
-                    if ob.gate or ob.dpool or ob.lazy is not None or (self.out_ref is not None and o.buf == self.out_ref.buf):
-                        continue
-                    lo, hi = o.coff, o.coff + o.C
-                    mine, ok = [], True
-                    for q in uses.get(o.buf, ()):
-                        views = [q["x"]] if q["op"] in (PW, DW, KXK, MAXPOOL, AVGPOOL) else q["srcs"] if q["op"] == EW else [q["a"], q["b"]]
-                        for t in views:
-                            if t.buf != o.buf or t.coff + t.C <= lo or hi <= t.coff:
-                                continue
-                            if not (lo <= t.coff and t.coff + t.C <= hi):
-                                ok = False
-                            elif q["op"] == EW:
-                                ok = ok and not q.get("lazy") and "flat" not in q and not q.get("mode") and q.get("coefs") is None and \
-                                    q["slope"] not in (SLOPE_SILU, SLOPE_RELU_SIGMOID) and not isinstance(q["out"], TCat) and \
-                                    not any(a[0] == id(q) for a in pending_add.get(t.buf, ())) and \
-                                    q["out"].H % t.H == 0 and q["out"].W % t.W == 0
-                            elif q["op"] in (MAXPOOL, AVGPOOL):
-                                pass
-                            elif q["op"] == PW:
-                                # (the fused 1x1 backward kernel keeps the shapes whose TILES stay below 64 x 128: csrc/k_conv_pw.hip)
-                                ci_t = 32 if t.C <= 32 else 64 if t.C <= 64 else 128
-                                nto = (q["out"].C + 31) // 32
-                                nto = 4 if nto == 3 else nto
-                                ok = ok and q["stride"] == 1 and not q.get("nchw") and q.get("xs") is None and t.C <= 128 and \
-                                    q["out"].C <= 128 and ci_t * nto * 32 < 64 * 128 and not q["wrc"][1] and not q["wrc"][0] and \
-                                    (t.coff, t.C) == (q["x"].coff, q["x"].C)
-                            else:
-                                ok = False
-                            mine.append((q, t))
-                    if ok and mine:
-                        P["sums_by_readers"] = True
-                        self.reader_bn_sums += 1
-                        for q, t in mine:
-                            bns[(id(q), t.buf, t.coff, t.C)] = (P, t.coff - lo)
+        def plain_sum(q):
+            return q["op"] == EW and q["slope"] == 1.0 and not q.get("mode") and q.get("coefs") is None and \
+                not isinstance(q["out"], TCat)
 
-            def bns_of(q, t):
-                """(ws pair, (C, coff)) of the BatchNorm sums reader record q adds for its input view t, or ((-1, -1), (0, 0))."""
-                e = bns.get((id(q), t.buf, t.coff, t.C))
-                if e is None:
-                    return (-1, -1), (0, 0)
-                P, off = e
-                return (self._abs(P["sums"]), self._abs(P["save"])), (P["out"].C, off)
-            # ---- readers of one tensor whose gradients meet in ONE store (lhn_grad_adds): a 2x2 max-pool, an adaptive average pool
-            # and a plain same-resolution sum reading the same view (the skip tensor of an hourglass level, litehourglass.py:139-163)
-            # -- the max-pool's backward, which runs last, takes the other two gradients on the way (LHN_POOL_GRAD_ADDS=0: three
-            # read-modify-write passes over d(x) as before)
-            fused_mp, skip_ew_src, skip_ap = {}, set(), set()
-            if os.environ.get("LHN_POOL_GRAD_ADDS", "1") != "0":
-                order = {id(q): i for i, q in enumerate(self.recs)}
-                for mp in self.recs:
-                    if mp["op"] != MAXPOOL or isinstance(mp["x"], TCat) or mp["x"].H % 2 or mp["x"].W % 2 or mp["x"].buf == self._no_grad_buf:
-                        continue
-                    X = mp["x"]
+        for sb, rd in uses.items():
+            if sb in aliased or sb == self._no_grad_buf:
+                continue
+            sums = [q for q in rd if plain_sum(q)]
+            dws = [q for q in rd if not plain_sum(q)]
+            if not sums or not dws or len(sums) > 2:
+                continue
+            if not all(q["op"] == DW and q["conv"].weight is not None and q["stride"] == 1 and q["k"] == 3 and
+                       q["pad"] == q["dil"] and q["x"].C % 32 == 0 and q["x"].W >= 8 and not isinstance(q["x"], TCat)
+                       for q in dws):
+                continue
+            if min(order[id(q)] for q in sums) < max(order[id(q)] for q in dws):
+                continue
+            spans = sorted((q["x"].coff, q["x"].coff + q["x"].C) for q in dws)
+            lo, hi = spans[0][0], spans[-1][1]
+            if any(a[1] != b[0] for a, b in zip(spans, spans[1:])):
+                continue
+            adds = []
+            for q in sums:
+                mine = [t for t in q["srcs"] if not isinstance(t, TCat) and t.buf == sb]
+                o = q["out"]
+                if len(mine) != 1 or (mine[0].coff, mine[0].C) != (lo, hi - lo) or (mine[0].H, mine[0].W) != (o.H, o.W) or \
+                        self.bufs[o.buf].C != self.bufs[sb].C:
+                    break
+                adds.append((id(q), o.buf, o.coff - lo))
+            else:
+                pending_add[sb] = adds
+        return pending_add
 
-                    def same(t, X=X):
-                        return not isinstance(t, TCat) and t.buf == X.buf and t.coff == X.coff and t.C == X.C
-                    ap = next((q for q in self.recs if q["op"] == AVGPOOL and "OH" in q and same(q["x"]) and order[id(q)] > order[id(mp)]
-                               and id(q) not in skip_ap), None)
-                    ew = None
-                    for q in self.recs:
-                        if q["op"] != EW or q.get("lazy") or q.get("fwd_fused") or "flat" in q or q.get("mode") or q.get("coefs") is not None:
-                            continue
-                        if order[id(q)] < order[id(mp)] or float(q["slope"]) != 1.0 or isinstance(q["out"], TCat):
-                            continue
-                        ob = self.bufs[q["out"].buf]
-                        idx = [j for j, t in enumerate(q["srcs"]) if same(t)]
-                        if ob.gate or ob.dpool or len(idx) != 1 or (q["srcs"][idx[0]].H, q["srcs"][idx[0]].W) != (q["out"].H, q["out"].W):
-                            continue
-                        if (id(q), idx[0]) in skip_ew_src or any(a[0] == id(q) for a in pending_add.get(X.buf, ())):
-                            continue
-                        ew = (q, idx[0])
-                        break
-                    if ap is None and ew is None:
+    @staticmethod
+    def _can_add_bn_sums(q, t, pending_add):
+        """True when the backward kernel of reader record q can add its part of the BatchNorm-backward sums for its input view t."""
+        if q["op"] == EW:
+            return not q.get("lazy") and "flat" not in q and not q.get("mode") and q.get("coefs") is None and \
+                q["slope"] not in (SLOPE_SILU, SLOPE_RELU_SIGMOID) and not isinstance(q["out"], TCat) and \
+                not any(a[0] == id(q) for a in pending_add.get(t.buf, ())) and \
+                q["out"].H % t.H == 0 and q["out"].W % t.W == 0
+        if q["op"] == PW:
+            # (the fused 1x1 backward kernel keeps the shapes whose TILES stay below 64 x 128: csrc/k_conv_pw.hip)
+            ci_t = 32 if t.C <= 32 else 64 if t.C <= 64 else 128
+            nto = (q["out"].C + 31) // 32
+            nto = 4 if nto == 3 else nto
+            return q["stride"] == 1 and not q.get("nchw") and q.get("xs") is None and t.C <= 128 and \
+                q["out"].C <= 128 and ci_t * nto * 32 < 64 * 128 and not q["wrc"][1] and not q["wrc"][0] and \
+                (t.coff, t.C) == (q["x"].coff, q["x"].C)
+        return q["op"] in (MAXPOOL, AVGPOOL)
+
+    def _reader_bn_sums(self, uses, aliased, pending_add):
+        """Reader-side BatchNorm sums, general form (include/lhn.h: lhn_bnsum): du is linear in dz and dz is the sum of what the
+        readers' backward kernels hand back, so when EVERY reader of a convolution + BatchNorm output can add its part
+        (elementwise combines, pools, the fused 1x1 backward) the producer's lhn_bn_bwd_reduce pass is not launched: the
+        producer record gets sums_by_readers.  Returns (id(reader record), buf, coff, C) of every such reading view ->
+        ((sums, save) offsets of the producer, (the producer's C, the view's channel offset inside it))."""
+        bns = {}
+        if not _switch("LHN_READER_BN_SUMS"):
+            return bns
+        for P in self.recs:
+            if P["op"] not in (STEM, PW, DW, KXK) or P["bn"] is None or P.get("sums_by_ca") or isinstance(P["out"], TCat):
+                continue
+            o = P["out"]
+            if o.buf < 0 or P.get("wrc", (0, 0))[0] or P.get("bn_repeat", 1) != 1 or o.buf in aliased:
+                continue
+            ob = self.bufs[o.buf]
+            if ob.gate or ob.dpool or ob.lazy is not None or (self.out_ref is not None and o.buf == self.out_ref.buf):
+                continue
+            lo, hi = o.coff, o.coff + o.C
+            mine, ok = [], True
+            for q in uses.get(o.buf, ()):
+                for t in _reads(q):
+                    if t.buf != o.buf or t.coff + t.C <= lo or hi <= t.coff:
                         continue
-                    keys = [bns_of(mp, X)] + ([bns_of(ap, X)] if ap else []) + ([bns_of(ew[0], X)] if ew else [])
-                    if any(kk != keys[0] for kk in keys):      # the producer's BatchNorm sums: all of x's readers or none
-                        continue
-                    fused_mp[id(mp)] = (ew, ap)
-                    if ew:
-                        skip_ew_src.add((id(ew[0]), ew[1]))
-                    if ap:
-                        skip_ap.add(id(ap))
-            self.pool_grad_adds = len(fused_mp)
-            for r in reversed(self.recs):
-                k = r["op"]
-                if k in (STEM, PW, DW, KXK, EW, SHUFFLE, MAXPOOL, AVGPOOL) and not (k == PW and r.get("nchw")) and \
-                        not (self.out_ref is not None and not isinstance(r["out"], TCat) and r["out"].buf == self.out_ref.buf):
-                    self._covered(written, r["out"])      # (the block output's gradient is written by the engine, not by an op)
-                if k in (STEM, PW, DW, KXK):
-                    conv, bn, x, out = r["conv"], r["bn"], r["x"], r["out"]
-                    pw = self._p(conv.weight)
-                    use_coef = 1 if bn is not None else 0
-                    lz = self.bufs[x.buf].lazy if x.buf >= 0 else None
-                    if lz is not None and x.buf not in materialised and x.buf not in self._sum_written:
-                        # the weight gradient needs the summed input: written once per backward, whole buffer
-                        materialised.add(x.buf)
-                        fl = lz["flat"]
-                        body.append(mk(EW, ins=[t for t, _ in fl], out=lz["out"], i=(len(fl), 1),
-                                       f=(1.0, 0.0, 0.0, 0.0) + tuple(c for _, c in fl)))
-                    if bn is not None:
-                        body.append(mk(BN_BWD, out=out, p=(self._p(bn.weight), self._p(bn.weight), self._p(bn.bias)),
-                                       ws=(self._abs(r["sums"]), self._abs(r["save"]), self._abs(r["bcnt"])),
-                                       i=(r["wrc"][0] if k == PW else 0, 1 if (r.get("sums_by_reader") or r.get("sums_by_ca") or r.get("sums_by_readers")) else 0)))
-                    if k == STEM:
-                        body.append(mk(STEM_BWD, out=out, p=(pw, pw), i=(r["k"], r["stride"], r["pad"], x.H, x.W, use_coef)))
-                        continue
-                    need_dx = x.buf != self._no_grad_buf
-                    mode = self._grad_mode(written, x) if need_dx else 0
-                    if k == PW:
-                        if r["stride"] != 1 and mode == 1:   # strided dgrad touches a subset of pixels
-                            self._needs_zero_grad.add(x.buf)
-                            mode = 2
-                        o = TRef(-1, 0, out.C, out.H, out.W) if r["nchw"] else out
-                        # a bias in front of a train-mode BatchNorm has an identically zero gradient
-                        bw, bc = bns_of(r, x) if need_dx else ((-1, -1), (0, 0))
-                        body.append(mk(PW_BWD, ins=(x,), out=o, p=(pw, pw, self._p(conv.bias) if bn is None else -1), ws=bw,
-                                       i=(r["stride"], 1 if r["nchw"] else 0, mode, r["wrc"][0], r["wrc"][1], use_coef,
-                                          r["stack"][0], r["stack"][1]), f=(0.0,) * 6 + (float(bc[0]), float(bc[1]))))
-                    elif k == DW:
-                        # the producer's BatchNorm-backward sums ride in this kernel when it is the only reader of x
-                        # (RepBasicUnit 1x1 -> 3x3 depthwise; include/lhn.h: lhn_conv_dw_bwd2)
-                        prod, xb = None, self.bufs[x.buf]
-                        if (fuse_sums and mode == 1 and r["k"] == 3 and r["stride"] == 1 and r["pad"] == 1 and r["dil"] == 1 and
-                                x.C % 32 == 0 and x.W >= 8 and not xb.gate and not xb.dpool and xb.lazy is None and
-                                conv.weight is not None and len(uses.get(x.buf, ())) == 1 and x.buf not in aliased):
-                            for q in self.recs:
-                                if q["op"] in (STEM, PW, DW, KXK) and q["bn"] is not None and q["out"].buf == x.buf and \
-                                        (q["out"].coff, q["out"].C) == (x.coff, x.C) and not q.get("wrc", (0, 0))[0] and q.get("bn_repeat", 1) == 1:
-                                    prod = q
-                        adds = pending_add.get(x.buf)
-                        if adds and need_dx:
-                            self.grad_addends += 1
-                            offs = [self.bufs[ob].off["grad"] + 4 * sh for _, ob, sh in adds]
-                            body.append(mk(DW_BWD, ins=(x,), out=out, p=(pw, pw), ws=(-1, -1, offs[0], offs[1] if len(offs) > 1 else -1),
-                                           i=(r["k"], r["stride"], r["pad"], r["dil"], mode, use_coef)))
-                        elif prod is not None:
-                            prod["sums_by_reader"] = True
-                            self.fused_bn_sums += 1
-                            body.append(mk(DW_BWD, ins=(x,), out=out, p=(pw, pw), ws=(-1, -1, -1, -1, self._abs(prod["sums"]), self._abs(prod["save"])),
-                                           i=(r["k"], r["stride"], r["pad"], r["dil"], mode, use_coef, x.C, 0)))
-                        else:
-                            body.append(mk(DW_BWD, ins=(x,), out=out, p=(pw, pw),
-                                           i=(r["k"], r["stride"], r["pad"], r["dil"], mode, use_coef)))
-                    else:
-                        body.append(mk(KXK_BWD, ins=(x,), out=out, p=(pw, pw), ws=(-1, -1, -1, self._abs(r["wt"])),
-                                       i=(r["stride"], 0, mode, 0, 0, use_coef)))
-                elif k == EW and (r.get("mode") or r.get("coefs") is not None):
-                    md, srcs = r.get("mode", 0), r["srcs"]
-                    if r.get("coefs") is not None and any(c != 1.0 for c in r["coefs"]):
-                        raise _lib.LhnError("a combine with coefficients is forward-only")
-                    for j, s in enumerate(srcs):
-                        if s.buf == self._no_grad_buf:
-                            continue
-                        gm = self._grad_mode(written, s)
-                        acc = 1 if gm == 2 else 0
-                        if md & EW_MUL:
-                            body.append(mk(EW_BWD, ins=(s, srcs[1 - j]), out=r["out"], i=(acc, 1), f=(r["slope"],)))
-                        elif (md & EW_BILINEAR) and (s.H, s.W) != (r["out"].H, r["out"].W):
-                            body.append(mk(EW_BWD, ins=(s,), out=r["out"], i=(acc, 2), f=(r["slope"],)))
-                        else:
-                            body.append(mk(EW_BWD, ins=(s,), out=r["out"], i=(acc,), f=(r["slope"],)))
-                elif k == EW:
-                    todo = []
-                    for j, s in enumerate(r["srcs"]):
-                        if s.buf == self._no_grad_buf or (s.buf in aliased and self.bufs[s.buf].off["grad"] == self.bufs[r["out"].buf].off["grad"]):
-                            continue
-                        if (id(r), j) in skip_ew_src:
-                            continue                # d(out) joins s's gradient inside the max-pool backward that reads s (fused_mp)
-                        if any(a[0] == id(r) for a in pending_add.get(s.buf, ())):
-                            continue                # d(out) joins s's gradient inside the depthwise backward kernels that read s
-                        mode = self._grad_mode(written, s)
-                        bw, bc = bns_of(r, s)
-                        todo.append((s, 1 if mode == 2 else 0, bw, bc))
-                    # sources of the destination's own resolution (residual sums) share ONE pass over d(out) / out (lhn_ew_bwd_multi)
-                    o_ = r["out"]
-                    same = [t for t in todo if not isinstance(t[0], TCat) and (t[0].H, t[0].W, t[0].C) == (o_.H, o_.W, o_.C)]
-                    if os.environ.get("LHN_EW_BWD_MULTI", "1") == "0" or len(same) < 2 or r["slope"] in (SLOPE_SILU, SLOPE_RELU_SIGMOID):
-                        same = []
-                    groups, rest_same = [], list(same)
-                    while len(rest_same) >= 2:
-                        take = 3 if len(rest_same) != 4 else 2
-                        groups.append(rest_same[:take])
-                        rest_same = rest_same[take:]
-                    grouped = {id(t[0]) for g in groups for t in g}
-                    for g in groups:
-                        ws_, iv, fv = [], [g[0][1], 3, g[1][1], g[2][1] if len(g) > 2 else 0], [r["slope"], 0.0, 0.0, 0.0, 0.0, 0.0]
-                        cc = []
-                        for q in range(3):
-                            if q < len(g):
-                                ws_ += list(g[q][2])
-                                cc.append(g[q][3])
-                            else:
-                                ws_ += [-1, -1]
-                                cc.append((0, 0))
-                        iv += [cc[0][0], cc[0][1], cc[1][0], cc[1][1]]
-                        fv[4], fv[5] = float(cc[2][0]), float(cc[2][1])
-                        body.append(mk(EW_BWD, ins=tuple(t[0] for t in g), out=o_, ws=tuple(ws_), i=tuple(iv), f=tuple(fv)))
-                        self.ew_bwd_multi = getattr(self, "ew_bwd_multi", 0) + 1
-                    for s, acc, bw, bc in todo:
-                        if id(s) in grouped:
-                            continue
-                        body.append(mk(EW_BWD, ins=(s,), out=o_, ws=bw, i=(acc, 0, 0, 0, bc[0], bc[1]), f=(r["slope"],)))
-                elif k == SHUFFLE:
-                    ma = 0 if r["a"].buf == self._no_grad_buf else self._grad_mode(written, r["a"])
-                    mb = 0 if r["b"].buf == self._no_grad_buf else self._grad_mode(written, r["b"])
-                    body.append(mk(SHUFFLE_BWD, ins=(r["a"], r["b"]), out=r["out"], i=(ma, mb)))
-                elif k == MAXPOOL:
-                    mode = self._grad_mode(written, r["x"])
-                    bw, bc = bns_of(r, r["x"])
-                    ew, ap = fused_mp.get(id(r), (None, None))
-                    sw, si, pw_, pi = -1, (0, 0), -1, (0, 0, 0)
-                    if ew is not None:
-                        eo = ew[0]["out"]
-                        sw, si = self.bufs[eo.buf].off["grad"], (self.bufs[eo.buf].C, eo.coff)
-                    if ap is not None:
-                        ob = self.bufs[ap["out"].buf]
-                        pw_, pi = ob.off["grad"], (ob.C, ap["out"].coff, (ap["OH"] << 16) | ap["OW"])
-                    body.append(mk(MAXPOOL_BWD, ins=(r["x"],), out=r["out"], ws=bw + (sw, pw_),
-                                   i=(1 if mode == 2 else 0, si[0], si[1], pi[0], bc[0], bc[1], pi[1], pi[2])))
-                elif k == AVGPOOL:
-                    if id(r) in skip_ap:
-                        continue                    # its gradient joins d(x) inside the max-pool backward (fused_mp)
-                    mode = self._grad_mode(written, r["x"])
-                    ob = self.bufs[r["out"].buf]
-                    bw, bc = bns_of(r, r["x"])
-                    body.append(mk(AVGPOOL_BWD, ins=(r["x"],), ws=(ob.off["grad"],) + bw,
-                                   i=(r["OH"], r["OW"], 1 if mode == 2 else 0, ob.C, r["out"].coff, bc[0], bc[1])))
-                elif k == SE_MLP:
-                    y, dn, up = r["y"], r["down"], r["up"]
-                    body.append(mk(GATE_REDUCE, out=y, ws=(-1, -1, -1, self._abs(r["dgate"]))))
-                    body.append(mk(SE_MLP_BWD, out=y,
-                                   p=(self._p(dn.weight), self._p(up.weight), self._p(dn.weight),
-                                      self._p(dn.bias), self._p(up.weight), self._p(up.bias)),
-                                   ws=(self._abs(r["pooled"]), self._abs(r["save"]), -1, self._abs(r["dgate"])), i=(r["J"], r["mode"])))
-                elif k == ATT_MLP:
-                    y, att = r["y"], r["att"]
-                    bn, dw, lin = att[1], att[3], att[6]
-                    body.append(mk(GATE_REDUCE, out=y, ws=(-1, -1, -1, self._abs(r["dgate"]))))
-                    body.append(mk(ATT_MLP_BWD, out=y,
-                                   p=(self._p(bn.weight), self._p(bn.bias), self._p(dw.weight), self._p(lin.weight),
-                                      self._p(bn.weight), self._p(bn.bias), self._p(dw.weight), self._p(dw.bias),
-                                      self._p(lin.weight), self._p(lin.bias)),
-                                   ws=(self._abs(r["pooled"]), self._abs(r["save"]), self._abs(r["mask"]),
-                                       self._abs(r["dgate"]), self._abs(r["gsum_b"]))))
-                elif k == CA_MLP:
-                    y, ca = r["y"], r["ca"]
-                    bn = ca.conv3x3.bn
-                    sl = r.get("bnslices") or []
-                    pk = tuple((q["out"].coff << 16) | q["out"].C for q in sl)
-                    sv = (tuple(self._abs(q["save"]) for q in sl) + (-1, -1))[:2]
-                    sm = (tuple(self._abs(q["sums"]) for q in sl) + (-1, -1))[:2]
-                    body.append(mk(GATE_REDUCE, out=y, ws=(-1, -1, -1, self._abs(r["dgate"]), 1 if sl else -1) + sv, i=pk))
-                    body.append(mk(CA_MLP_BWD, out=y,
-                                   p=(self._p(ca.conv3x3.conv.weight), self._p(bn.weight), self._p(ca.conv1x1[1].weight),
-                                      self._p(ca.conv1x1[3].weight),
-                                      self._p(ca.conv3x3.conv.weight), self._p(bn.weight), self._p(bn.bias),
-                                      self._p(ca.conv1x1[1].weight), self._p(ca.conv1x1[1].bias),
-                                      self._p(ca.conv1x1[3].weight), self._p(ca.conv1x1[3].bias)),
-                                   ws=(self._abs(r["pooled"]), self._abs(r["save"]), self._abs(r["mask"]),
-                                       self._abs(r["dgate"]), self._abs(r["gsum_b"]), self._abs(r.get("pstat"))) + sv + sm, i=pk))
-            if self.ar["zb"].size:
-                bwd.append(mk(MEMSET, ws=(self.arena_base["zb"], self.ar["zb"].size)))
-            for b in sorted(self._needs_zero_grad):
-                rec = self.bufs[b]
-                bwd.append(mk(MEMSET, ws=(rec.off["grad"], N * rec.H * rec.W * rec.C * 4)))
-            if self._needs_zero_grad:
-                # every write into a zero-initialised gradient buffer must accumulate
-                for o in body:
-                    if o.kind in (PW_BWD, KXK_BWD) and o.in_buf[0] in self._needs_zero_grad and o.i[2]:
-                        o.i[2] = 2
-                    elif o.kind == DW_BWD and o.in_buf[0] in self._needs_zero_grad and o.i[4]:
-                        o.i[4] = 2
-                    elif o.kind in (EW_BWD, MAXPOOL_BWD) and o.in_buf[0] in self._needs_zero_grad:
-                        o.i[0] = 1
-                    elif o.kind == SHUFFLE_BWD:
-                        for q in range(2):
-                            if o.in_buf[q] in self._needs_zero_grad and o.i[q]:
-                                o.i[q] = 2
-                    elif o.kind == AVGPOOL_BWD and o.in_buf[0] in self._needs_zero_grad:
-                        o.i[2] = 1
-            bwd += body
-        # ---------------- SyncBatchNorm: (op index, byte offset, number of doubles, replicated layout?) of every statistics buffer that has
-        # to be all-reduced between half-step 2*i and 2*i+1 of lhn_plan_run_range
-        self.sync_points = {0: [], 1: []}
-        for phase, lst in ((0, fwd), (1, bwd)):
+                    ok = ok and lo <= t.coff and t.coff + t.C <= hi and self._can_add_bn_sums(q, t, pending_add)
+                    mine.append((q, t))
+            if ok and mine:
+                P["sums_by_readers"] = True
+                self.reader_bn_sums += 1
+                for q, t in mine:
+                    bns[(id(q), t.buf, t.coff, t.C)] = ((self._abs(P["sums"]), self._abs(P["save"])), (o.C, t.coff - lo))
+        return bns
+
+    def _pool_grad_fusion(self, pending_add, bns_of):
+        """Readers of one tensor whose gradients meet in ONE store (lhn_grad_adds): a 2x2 max-pool, an adaptive average pool
+        and a plain same-resolution sum reading the same view (the skip tensor of an hourglass level, litehourglass.py:139-163)
+        -- the max-pool's backward, which runs last, takes the other two gradients on the way (LHN_POOL_GRAD_ADDS=0: three
+        read-modify-write passes over d(x) as before).  Returns (id(max-pool record) -> ((sum record, source index) | None,
+        average-pool record | None), the (id(sum record), source index) pairs and the id(average-pool record)s taken over)."""
+        fused_mp, skip_ew_src, skip_ap = {}, set(), set()
+        if not _switch("LHN_POOL_GRAD_ADDS"):
+            return fused_mp, skip_ew_src, skip_ap
+        order = {id(q): i for i, q in enumerate(self.recs)}
+        for mp in self.recs:
+            if mp["op"] != MAXPOOL or isinstance(mp["x"], TCat) or mp["x"].H % 2 or mp["x"].W % 2 or mp["x"].buf == self._no_grad_buf:
+                continue
+            X = mp["x"]
+
+            def same(t, X=X):
+                return not isinstance(t, TCat) and t.buf == X.buf and t.coff == X.coff and t.C == X.C
+            ap = next((q for q in self.recs if q["op"] == AVGPOOL and "OH" in q and same(q["x"]) and order[id(q)] > order[id(mp)]
+                       and id(q) not in skip_ap), None)
+            ew = None
+            for q in self.recs:
+                if q["op"] != EW or q.get("lazy") or q.get("fwd_fused") or "flat" in q or q.get("mode") or q.get("coefs") is not None:
+                    continue
+                if order[id(q)] < order[id(mp)] or float(q["slope"]) != 1.0 or isinstance(q["out"], TCat):
+                    continue
+                ob = self.bufs[q["out"].buf]
+                idx = [j for j, t in enumerate(q["srcs"]) if same(t)]
+                if ob.gate or ob.dpool or len(idx) != 1 or (q["srcs"][idx[0]].H, q["srcs"][idx[0]].W) != (q["out"].H, q["out"].W):
+                    continue
+                if (id(q), idx[0]) in skip_ew_src or any(a[0] == id(q) for a in pending_add.get(X.buf, ())):
+                    continue
+                ew = (q, idx[0])
+                break
+            if ap is None and ew is None:
+                continue
+            keys = [bns_of(mp, X)] + ([bns_of(ap, X)] if ap else []) + ([bns_of(ew[0], X)] if ew else [])
+            if any(kk != keys[0] for kk in keys):      # the producer's BatchNorm sums: all of x's readers or none
+                continue
+            fused_mp[id(mp)] = (ew, ap)
+            if ew:
+                skip_ew_src.add((id(ew[0]), ew[1]))
+            if ap:
+                skip_ap.add(id(ap))
+        self.pool_grad_adds = len(fused_mp)
+        return fused_mp, skip_ew_src, skip_ap
+
+    # ---- backward emitters: (record, _BwdFusions) -> [Op]
+    def _bwd_conv(self, r, fz):
+        mk = self._mk
+        k, conv, bn, x, out = r["op"], r["conv"], r["bn"], r["x"], r["out"]
+        pw = self._p(conv.weight)
+        use_coef = 1 if bn is not None else 0
+        ops = []
+        lz = self.bufs[x.buf].lazy if x.buf >= 0 else None
+        if lz is not None and x.buf not in fz.materialised and x.buf not in self._sum_written:
+            # the weight gradient needs the summed input: written once per backward, whole buffer
+            fz.materialised.add(x.buf)
+            fl = lz["flat"]
+            ops.append(mk(EW, ins=[t for t, _ in fl], out=lz["out"], i=(len(fl), 1), f=(1.0, 0.0, 0.0, 0.0) + tuple(c for _, c in fl)))
+        if bn is not None:      # (sums_by_reader: set by the depthwise reader's emitter, which ran before this one -- see _bwd_dw)
+            by_others = r.get("sums_by_reader") or r.get("sums_by_ca") or r.get("sums_by_readers")
+            ops.append(mk(BN_BWD, out=out, p=(self._p(bn.weight), self._p(bn.weight), self._p(bn.bias)),
+                          ws=(self._abs(r["sums"]), self._abs(r["save"]), self._abs(r["bcnt"])),
+                          i=(r["wrc"][0] if k == PW else 0, 1 if by_others else 0)))
+        if k == STEM:
+            return ops + [mk(STEM_BWD, out=out, p=(pw, pw), i=(r["k"], r["stride"], r["pad"], x.H, x.W, use_coef))]
+        need_dx = x.buf != self._no_grad_buf
+        mode = self._grad_mode(fz.written, x) if need_dx else 0
+        if k == PW:
+            if r["stride"] != 1 and mode == 1:   # strided dgrad touches a subset of pixels
+                self._needs_zero_grad.add(x.buf)
+                mode = 2
+            o = TRef(-1, 0, out.C, out.H, out.W) if r["nchw"] else out
+            # a bias in front of a train-mode BatchNorm has an identically zero gradient
+            bw, bc = fz.bns_of(r, x) if need_dx else ((-1, -1), (0, 0))
+            ops.append(mk(PW_BWD, ins=(x,), out=o, p=(pw, pw, self._p(conv.bias) if bn is None else -1), ws=bw,
+                          i=(r["stride"], 1 if r["nchw"] else 0, mode, r["wrc"][0], r["wrc"][1], use_coef,
+                             r["stack"][0], r["stack"][1]), f=(0.0,) * 6 + (float(bc[0]), float(bc[1]))))
+        elif k == DW:
+            ops.append(self._bwd_dw(r, mode, need_dx, fz))
+        else:
+            ops.append(mk(KXK_BWD, ins=(x,), out=out, p=(pw, pw), ws=(-1, -1, -1, self._abs(r["wt"])),
+                          i=(r["stride"], 0, mode, 0, 0, use_coef)))
+        return ops
+
+    def _sole_reader_producer(self, r, mode, fz):
+        """The convolution + BatchNorm record whose output is exactly the input view of depthwise record r, when r is that
+        buffer's only reader and stores its dx (mode 1) with the 3x3 stride-1 kernel -- or None."""
+        x, xb = r["x"], self.bufs[r["x"].buf]
+        if not (_switch("LHN_FUSE_BN_SUMS") and mode == 1 and r["k"] == 3 and r["stride"] == 1 and r["pad"] == 1 and r["dil"] == 1 and
+                x.C % 32 == 0 and x.W >= 8 and not xb.gate and not xb.dpool and xb.lazy is None and
+                r["conv"].weight is not None and len(fz.uses.get(x.buf, ())) == 1 and x.buf not in fz.aliased):
+            return None
+        prod = None
+        for q in self.recs:
+            if q["op"] in (STEM, PW, DW, KXK) and q["bn"] is not None and q["out"].buf == x.buf and \
+                    (q["out"].coff, q["out"].C) == (x.coff, x.C) and not q.get("wrc", (0, 0))[0] and q.get("bn_repeat", 1) == 1:
+                prod = q
+        return prod
+
+    def _bwd_dw(self, r, mode, need_dx, fz):
+        """The DW_BWD op of depthwise record r.  It carries the gradient addends of its input buffer (fz.pending_add), or else
+        the BatchNorm-backward sums of its input's producer when it is the only reader of x (RepBasicUnit 1x1 -> 3x3 depthwise;
+        include/lhn.h: lhn_conv_dw_bwd2).  The second is decided HERE, not in an analysis, because it depends on the store mode
+        the tracker just returned: the producer gets sums_by_reader, which its own BN_BWD op -- emitted later, the records
+        being walked in reverse -- reads in _bwd_conv."""
+        x, pw = r["x"], self._p(r["conv"].weight)
+        geo = (r["k"], r["stride"], r["pad"], r["dil"], mode, 1 if r["bn"] is not None else 0)
+        adds = fz.pending_add.get(x.buf)
+        if adds and need_dx:
+            self.grad_addends += 1
+            offs = [self.bufs[ob].off["grad"] + 4 * sh for _, ob, sh in adds]
+            return self._mk(DW_BWD, ins=(x,), out=r["out"], p=(pw, pw), ws=(-1, -1, offs[0], offs[1] if len(offs) > 1 else -1), i=geo)
+        prod = self._sole_reader_producer(r, mode, fz)
+        if prod is None:
+            return self._mk(DW_BWD, ins=(x,), out=r["out"], p=(pw, pw), i=geo)
+        prod["sums_by_reader"] = True
+        self.fused_bn_sums += 1
+        return self._mk(DW_BWD, ins=(x,), out=r["out"], p=(pw, pw), ws=(-1, -1, -1, -1, self._abs(prod["sums"]), self._abs(prod["save"])),
+                        i=geo + (x.C, 0))
+
+    def _bwd_ew_mode(self, r, fz):
+        """Products, bilinear resampling and combines with coefficients: one op per source."""
+        md, srcs, ops = r.get("mode", 0), r["srcs"], []
+        if r.get("coefs") is not None and any(c != 1.0 for c in r["coefs"]):
+            raise _lib.LhnError("a combine with coefficients is forward-only")
+        for j, s in enumerate(srcs):
+            if s.buf == self._no_grad_buf:
+                continue
+            acc = 1 if self._grad_mode(fz.written, s) == 2 else 0
+            if md & EW_MUL:
+                ops.append(self._mk(EW_BWD, ins=(s, srcs[1 - j]), out=r["out"], i=(acc, 1), f=(r["slope"],)))
+            elif (md & EW_BILINEAR) and (s.H, s.W) != (r["out"].H, r["out"].W):
+                ops.append(self._mk(EW_BWD, ins=(s,), out=r["out"], i=(acc, 2), f=(r["slope"],)))
+            else:
+                ops.append(self._mk(EW_BWD, ins=(s,), out=r["out"], i=(acc,), f=(r["slope"],)))
+        return ops
+
+    @staticmethod
+    def _multi_groups(r, todo):
+        """Sources of the destination's own resolution (residual sums) share ONE pass over d(out) / out (lhn_ew_bwd_multi): the
+        (source, accumulate, sums ws, sums (C, coff)) entries of `todo` in groups of 2 or 3, or [] (LHN_EW_BWD_MULTI=0)."""
+        o = r["out"]
+        same = [t for t in todo if not isinstance(t[0], TCat) and (t[0].H, t[0].W, t[0].C) == (o.H, o.W, o.C)]
+        if not _switch("LHN_EW_BWD_MULTI") or len(same) < 2 or r["slope"] in (SLOPE_SILU, SLOPE_RELU_SIGMOID):
+            return []
+        groups = []
+        while len(same) >= 2:
+            take = 3 if len(same) != 4 else 2
+            groups.append(same[:take])
+            same = same[take:]
+        return groups
+
+    def _bwd_ew(self, r, fz):
+        if r.get("mode") or r.get("coefs") is not None:
+            return self._bwd_ew_mode(r, fz)
+        todo = []
+        for j, s in enumerate(r["srcs"]):
+            if s.buf == self._no_grad_buf or (s.buf in fz.aliased and self.bufs[s.buf].off["grad"] == self.bufs[r["out"].buf].off["grad"]):
+                continue
+            if (id(r), j) in fz.skip_ew_src:
+                continue                # d(out) joins s's gradient inside the max-pool backward that reads s (fused_mp)
+            if any(a[0] == id(r) for a in fz.pending_add.get(s.buf, ())):
+                continue                # d(out) joins s's gradient inside the depthwise backward kernels that read s
+            mode = self._grad_mode(fz.written, s)
+            todo.append((s, 1 if mode == 2 else 0) + fz.bns_of(r, s))
+        groups = self._multi_groups(r, todo)        # (after every tracker call of this record)
+        self.ew_bwd_multi += len(groups)
+        ops = []
+        for g in groups:
+            g3 = g + [(None, 0, (-1, -1), (0, 0))] * (3 - len(g))
+            ops.append(self._mk(EW_BWD, ins=tuple(t[0] for t in g), out=r["out"], ws=g3[0][2] + g3[1][2] + g3[2][2],
+                                i=(g3[0][1], 3, g3[1][1], g3[2][1]) + g3[0][3] + g3[1][3],
+                                f=(r["slope"], 0.0, 0.0, 0.0, float(g3[2][3][0]), float(g3[2][3][1]))))
+        grouped = {id(t[0]) for g in groups for t in g}
+        ops += [self._mk(EW_BWD, ins=(s,), out=r["out"], ws=bw, i=(acc, 0, 0, 0, bc[0], bc[1]), f=(r["slope"],))
+                for s, acc, bw, bc in todo if id(s) not in grouped]
+        return ops
+
+    def _bwd_shuffle(self, r, fz):
+        ma = 0 if r["a"].buf == self._no_grad_buf else self._grad_mode(fz.written, r["a"])
+        mb = 0 if r["b"].buf == self._no_grad_buf else self._grad_mode(fz.written, r["b"])
+        return [self._mk(SHUFFLE_BWD, ins=(r["a"], r["b"]), out=r["out"], i=(ma, mb))]
+
+    def _bwd_maxpool(self, r, fz):
+        mode = self._grad_mode(fz.written, r["x"])
+        bw, bc = fz.bns_of(r, r["x"])
+        ew, ap = fz.fused_mp.get(id(r), (None, None))
+        sw, si, pw_, pi = -1, (0, 0), -1, (0, 0, 0)
+        if ew is not None:
+            eo = ew[0]["out"]
+            sw, si = self.bufs[eo.buf].off["grad"], (self.bufs[eo.buf].C, eo.coff)
+        if ap is not None:
+            ob = self.bufs[ap["out"].buf]
+            pw_, pi = ob.off["grad"], (ob.C, ap["out"].coff, (ap["OH"] << 16) | ap["OW"])
+        return [self._mk(MAXPOOL_BWD, ins=(r["x"],), out=r["out"], ws=bw + (sw, pw_),
+                         i=(1 if mode == 2 else 0, si[0], si[1], pi[0], bc[0], bc[1], pi[1], pi[2]))]
+
+    def _bwd_avgpool(self, r, fz):
+        if id(r) in fz.skip_ap:
+            return []                   # its gradient joins d(x) inside the max-pool backward (fused_mp)
+        mode = self._grad_mode(fz.written, r["x"])
+        ob = self.bufs[r["out"].buf]
+        bw, bc = fz.bns_of(r, r["x"])
+        return [self._mk(AVGPOOL_BWD, ins=(r["x"],), ws=(ob.off["grad"],) + bw,
+                         i=(r["OH"], r["OW"], 1 if mode == 2 else 0, ob.C, r["out"].coff, bc[0], bc[1]))]
+
+    def _bwd_se(self, r, fz):
+        y, dn, up, P = r["y"], r["down"], r["up"], self._p
+        return [self._mk(GATE_REDUCE, out=y, ws=(-1, -1, -1, self._abs(r["dgate"]))),
+                self._mk(SE_MLP_BWD, out=y, p=(P(dn.weight), P(up.weight), P(dn.weight), P(dn.bias), P(up.weight), P(up.bias)),
+                         ws=(self._abs(r["pooled"]), self._abs(r["save"]), -1, self._abs(r["dgate"])), i=(r["J"], r["mode"]))]
+
+    def _bwd_att(self, r, fz):
+        y, att, P = r["y"], r["att"], self._p
+        bn, dw, lin = att[1], att[3], att[6]
+        return [self._mk(GATE_REDUCE, out=y, ws=(-1, -1, -1, self._abs(r["dgate"]))),
+                self._mk(ATT_MLP_BWD, out=y, p=(P(bn.weight), P(bn.bias), P(dw.weight), P(lin.weight),
+                                                P(bn.weight), P(bn.bias), P(dw.weight), P(dw.bias), P(lin.weight), P(lin.bias)),
+                         ws=tuple(self._abs(r[key]) for key in ("pooled", "save", "mask", "dgate", "gsum_b")))]
+
+    def _bwd_ca(self, r, fz):
+        y, ca, P = r["y"], r["ca"], self._p
+        c3, bn, l1, l2 = ca.conv3x3.conv, ca.conv3x3.bn, ca.conv1x1[1], ca.conv1x1[3]
+        sl = r.get("bnslices") or []
+        pk = tuple((q["out"].coff << 16) | q["out"].C for q in sl)
+        sv = (tuple(self._abs(q["save"]) for q in sl) + (-1, -1))[:2]
+        sm = (tuple(self._abs(q["sums"]) for q in sl) + (-1, -1))[:2]
+        return [self._mk(GATE_REDUCE, out=y, ws=(-1, -1, -1, self._abs(r["dgate"]), 1 if sl else -1) + sv, i=pk),
+                self._mk(CA_MLP_BWD, out=y, p=(P(c3.weight), P(bn.weight), P(l1.weight), P(l2.weight), P(c3.weight), P(bn.weight), P(bn.bias),
+                                               P(l1.weight), P(l1.bias), P(l2.weight), P(l2.bias)),
+                         ws=tuple(self._abs(r.get(key)) for key in ("pooled", "save", "mask", "dgate", "gsum_b", "pstat")) + sv + sm, i=pk)]
+
+    # gradient-write slot of a backward op and the value that means "accumulate": mode slots (0 none, 1 store, 2 accumulate)
+    # are only raised when set, flag slots are set
+    _ACCUMULATE = {PW_BWD: (2, 2), KXK_BWD: (2, 2), DW_BWD: (4, 2), EW_BWD: (0, 1), MAXPOOL_BWD: (0, 1), AVGPOOL_BWD: (2, 1)}
+
+    def _force_accumulate(self, body):
+        """Every write into a zero-initialised gradient buffer (_needs_zero_grad, complete only after the emitters ran) must accumulate."""
+        zg = self._needs_zero_grad
+        for o in (body if zg else ()):
+            if o.kind == SHUFFLE_BWD:
+                for q in range(2):
+                    if o.in_buf[q] in zg and o.i[q]:
+                        o.i[q] = 2
+            elif o.kind in self._ACCUMULATE and o.in_buf[0] in zg:
+                slot, acc = self._ACCUMULATE[o.kind]
+                if acc == 1 or o.i[slot]:
+                    o.i[slot] = acc
+
+    @staticmethod
+    def _sync_points(fwd, bwd):
+        """SyncBatchNorm: (op index, byte offset, number of doubles, replicated layout?) of every statistics buffer that has to be
+        all-reduced between half-step 2*i and 2*i+1 of lhn_plan_run_range, per phase."""
+        pts = {0: [], 1: []}
+        for lst in (fwd, bwd):
             for i, o in enumerate(lst):
                 if o.kind in (STEM, PW, DW, KXK) and o.p[2] >= 0 and o.ws[0] >= 0:
-                    self.sync_points[0].append((i, o.ws[0], STAT_REPLICAS * 2 * o.out_C, True))
+                    pts[0].append((i, o.ws[0], STAT_REPLICAS * 2 * o.out_C, True))
                 elif o.kind in (CA_MLP, ATT_MLP) and o.ws[3] >= 0:
-                    self.sync_points[0].append((i, o.ws[3], 2 * o.out_C, False))
+                    pts[0].append((i, o.ws[3], 2 * o.out_C, False))
                 elif o.kind == BN_BWD:
-                    self.sync_points[1].append((i, o.ws[0], STAT_REPLICAS * 2 * o.out_C, True))
+                    pts[1].append((i, o.ws[0], STAT_REPLICAS * 2 * o.out_C, True))
                 elif o.kind in (CA_MLP_BWD, ATT_MLP_BWD) and o.ws[4] >= 0:
-                    self.sync_points[1].append((i, o.ws[4], 2 * o.out_C, False))
-        # ---------------- C arrays
+                    pts[1].append((i, o.ws[4], 2 * o.out_C, False))
+        return pts
+
+    def _c_arrays(self, fwd, bwd):
         cb = (Buf * len(self.bufs))()
         for j, b in enumerate(self.bufs):
             cb[j].data_off = b.off["data"]
@@ -1230,12 +1319,10 @@ class PlanBuilder:
             cb[j].grad_off = b.off.get("grad", -1)
             cb[j].dpool_off = b.off.get("dpool", -1)
             cb[j].coef_off = b.off.get("coef", -1)
-            cb[j].N, cb[j].H, cb[j].W, cb[j].C = N, b.H, b.W, b.C
+            cb[j].N, cb[j].H, cb[j].W, cb[j].C = self.N, b.H, b.W, b.C
         cf = (Op * len(fwd))(*fwd)
         cbw = (Op * max(1, len(bwd)))(*bwd) if bwd else None
         return cb, cf, cbw, len(fwd), len(bwd)
-
-    _no_grad_buf = -1   # the image never needs a gradient
 
 
 _SIDE_STREAMS = {}

@@ -8,7 +8,7 @@ import pytest
 
 from litehandnet_amd import get_model
 from litehandnet_amd.config import litehandnet_cfg
-from litehandnet_amd.plan import AVGPOOL, DW, EW, KXK, MAXPOOL, PW, STEM, PlanBuilder
+from litehandnet_amd.plan import AVGPOOL, DW, EW, KXK, PW, STEM, PlanBuilder, _reads
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -37,8 +37,7 @@ def test_plan_structure(variant):
     # every launch reads buffers that an earlier launch (or the image) wrote
     written = {-1}
     for r in pb.recs:
-        ins = [r["x"]] if r["op"] in (STEM, PW, DW, KXK, MAXPOOL, AVGPOOL) else (r["srcs"] if r["op"] == EW else [])
-        for t in ins:
+        for t in _reads(r):
             assert t.buf in written, (r["op"], t.buf)
         if "out" in r and r["out"] is not None:
             written.add(r["out"].buf)
