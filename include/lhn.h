@@ -111,6 +111,7 @@ int         lhn_device_ok(void);              /* 0 if a gfx950 device is usable 
  * lhn_heatmap_decode    .../top_down_eval.py:375-463 (keypoints_from_heatmaps, 'default'), fused
  * lhn_heatmap_nms       utils/HeatmapParser.py:41-50 (k x k max-pool peak keep)
  * lhn_pck_accuracy      .../top_down_eval.py:12-62,129-165
+ * lhn_eval_*            datasets/datasets/base_dataset.py:193-261 (_report_metric: PCK, AUC, EPE over the whole test set)
  * lhn_loss_balanced_mse loss/loss.py:93-114 + loss/heatmapLoss.py:242-265
  */
 int lhn_heatmap_encode(const float* joints /*[N,K,3]*/, const float* visible /*[N,K,3]*/,
@@ -180,6 +181,32 @@ int lhn_heatmap_topk(const float* centre_maps, const float* size_maps, float* ca
 int lhn_pck_accuracy(const float* pred, const float* gt, const uint8_t* mask /*[N,K]*/,
                      const float* normalize /*[N,2]*/, float thr, float* acc /*[K]*/,
                      float* avg_cnt /*[2]: avg, cnt*/, int N, int K, void* stream);
+/* Streaming dataset-level evaluation: base_dataset.py:193-261 (_report_metric) = keypoint_pck_accuracy (top_down_eval.py:129-165),
+ * keypoint_auc (:168-196) and keypoint_epe (:104-126) over the concatenated predictions of a test set, all three on
+ * _calc_distances / _distance_acc (:12-62).  Every figure but EPE's numerator is a ratio of per-joint integer counts, so
+ * the state is added to batch by batch (any split, any order, any number of devices) and divided once.
+ * state: ONE device allocation of lhn_eval_state_bytes(K, num_step) bytes, zeroed by the caller before the first batch,
+ * int64 words throughout (so states of several processes are merged by adding them word by word):
+ *   [0,  K)              valid_pck[k]     samples of joint k with mask != 0 and no zero in their PCK normaliser
+ *   [K,  2K)             hit_pck[k]       ... of those with distance < pck_thr
+ *   [2K, 3K)             valid_auc[k]     samples of joint k with mask != 0 (and auc_normalize != 0)
+ *   [3K, 3K+num_step*K)  hit_auc[i][k]    ... of those with distance < float32(i / num_step)
+ *   then 4 words         epe_cnt          masked-in keypoints
+ *                        epe_hi, epe_lo   sum of their float32 distances in exact fixed point: whole pixels, and the
+ *                                         fractions in units of 2^-32 px (each rounded to that unit: <= 2^-33 px off)
+ *                        epe_bad          distances that are inf, NaN or >= 2^62 px (EPE then reads NaN)
+ * Integer atomics only: the state after a batch does not depend on workgroup order, with or without LHN_DETERMINISTIC.
+ * Arithmetic follows the reference's three routes: PCK float32 / float32 normaliser, EPE float32 / ones, AUC float32
+ * difference / integer normaliser = float64 up to the root, rounded to float32 once.
+ * lhn_eval_state_bytes is host-only (no device needed); 0 = unsupported (K, num_step): (3 + num_step) * K <= 8192.
+ * pck_normalize [N,2] may be NULL: the PCK counts are then left alone (keypoint_auc / keypoint_epe on their own).
+ * lhn_eval_finalize: out = double[K + 4] = acc[K] (-1 for a joint without a valid sample) | pck (mean of acc >= 0) |
+ * cnt (joints in that mean) | auc | epe, computed on the device. */
+int64_t lhn_eval_state_bytes(int K, int num_step);
+int lhn_eval_accumulate(const float* pred /*[N,K,2]*/, const float* gt /*[N,K,2]*/, const uint8_t* mask /*[N,K]*/,
+                        const float* pck_normalize /*[N,2] or NULL*/, float pck_thr, double auc_normalize, int num_step,
+                        void* state, int N, int K, void* stream);
+int lhn_eval_finalize(const void* state, int K, int num_step, double* out /*[K+4]*/, void* stream);
 /* acc: double[68]: [0..3] = {S_pos, S_neg, n_pos (exact integer < 2^53), unused} after the call,
  * [4..67] = 16 replicated partial-sum slots (spread the atomics); zeroed by the call */
 int lhn_loss_balanced_mse_fwd(const float* out, const float* target, const float* weight /*[N,K]*/,

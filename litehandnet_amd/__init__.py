@@ -19,3 +19,11 @@ def invalidate_tables():
     """See litehandnet_amd.plan.invalidate_tables: call after writing parameters / running statistics through `.data`."""
     from .plan import invalidate_tables as _i
     _i()
+
+
+def __getattr__(name):
+    # evaluation entry points (heatmap.py), imported on first use like get_model / get_loss
+    if name in ("TopDownEvaluator", "TopDownDecoder", "keypoint_pck_accuracy", "keypoint_auc", "keypoint_epe"):
+        from . import heatmap
+        return getattr(heatmap, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

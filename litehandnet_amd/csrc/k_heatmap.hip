@@ -1023,3 +1023,151 @@ extern "C" int lhn_heatmap_decode_dark_udp(const float* hm, const float* center,
   LHN_CHECK_LAUNCH("lhn_heatmap_decode_dark_udp");
   return 0;
 }
+
+// ------------------------------------------------------------------ streaming dataset-level PCK / AUC / EPE
+// base_dataset.py:193-261 (_report_metric) over top_down_eval.py:12-62 (_calc_distances, _distance_acc), :104-126
+// (keypoint_epe), :129-165 (keypoint_pck_accuracy), :168-196 (keypoint_auc).  Every figure but EPE's numerator is a ratio of
+// per-joint integer counts, so counts added batch by batch give the concatenate-then-divide result in any split and order.
+// State (int64 words, layout in include/lhn.h): valid_pck[K] | hit_pck[K] | valid_auc[K] | hit_auc[num_step][K] |
+// epe_cnt | epe_hi | epe_lo | epe_bad.  EPE's numerator is exact fixed point (whole pixels in epe_hi, the fraction in units
+// of 2^-32 px in epe_lo), so it is as order-independent as the counts.
+// The three metrics keep the reference's three dtype routes: PCK float32 / float32 box (as k_pck), EPE float32 / ones,
+// AUC float32 difference / INTEGER normaliser = float64 division, squares, sum and root, rounded to float32 once.
+#define LHN_EVAL_MAX_WORDS 8192      // (3 + num_step) * K workgroup counters in LDS
+__global__ void __launch_bounds__(256) k_eval_accumulate(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                         const uint8_t* __restrict__ mask, const float* __restrict__ pck_norm,
+                                                         float pck_thr, double auc_norm, int num_step,
+                                                         unsigned long long* __restrict__ state, int64_t NK, int K) {
+  extern __shared__ unsigned s_cnt[];        // valid_pck[K] | hit_pck[K] | valid_auc[K] | first-hit histogram [num_step][K]
+  __shared__ unsigned long long s_epe[4];    // cnt, hi, lo, bad
+  const int words = (3 + num_step) * K;
+  for (int i = threadIdx.x; i < words; i += blockDim.x) s_cnt[i] = 0u;
+  if (threadIdx.x < 4) s_epe[threadIdx.x] = 0ull;
+  __syncthreads();
+  const bool auc_on = auc_norm != 0.0;                       // _calc_distances: a zero in the normaliser drops the sample
+  const double an = auc_norm <= 0.0 ? 1e6 : auc_norm;
+  unsigned long long e_cnt = 0, e_hi = 0, e_lo = 0, e_bad = 0;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < NK; e += (int64_t)gridDim.x * blockDim.x) {
+    if (mask[e] == 0) continue;
+    const int64_t n = e / K;
+    const int k = (int)(e - n * K);
+    const float dx = sub_rn(pred[e * 2], gt[e * 2]), dy = sub_rn(pred[e * 2 + 1], gt[e * 2 + 1]);
+    if (pck_norm) {
+      float n0 = pck_norm[n * 2], n1 = pck_norm[n * 2 + 1];
+      if (n0 != 0.f && n1 != 0.f) {
+        if (n0 <= 0.f) n0 = 1e6f;
+        if (n1 <= 0.f) n1 = 1e6f;
+        const float qx = dx / n0, qy = dy / n1;
+        const float d = sqrtf(add_rn(mul_rn(qx, qx), mul_rn(qy, qy)));
+        atomicAdd(&s_cnt[k], 1u);
+        if (d < pck_thr) atomicAdd(&s_cnt[K + k], 1u);
+      }
+    }
+    if (auc_on) {
+      const double qx = (double)dx / an, qy = (double)dy / an;
+      const float d = (float)sqrt(qx * qx + qy * qy);
+      atomicAdd(&s_cnt[2 * K + k], 1u);
+      int first = 0;                                         // d < i/num_step is monotone in i: count the first hit only
+      while (first < num_step && !(d < (float)((double)first / (double)num_step))) ++first;
+      if (first < num_step) atomicAdd(&s_cnt[(3 + first) * K + k], 1u);
+    }
+    const float d = sqrtf(add_rn(mul_rn(dx, dx), mul_rn(dy, dy)));
+    ++e_cnt;
+    if (d < 4.6e18f) {
+      const unsigned long long w = (unsigned long long)d;
+      e_hi += w;
+      e_lo += (unsigned long long)llrint(((double)d - (double)w) * 4294967296.0);
+    } else {
+      ++e_bad;                                               // inf / NaN / beyond the fixed-point range: EPE reads NaN
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    e_cnt += __shfl_xor(e_cnt, o, 64);
+    e_hi += __shfl_xor(e_hi, o, 64);
+    e_lo += __shfl_xor(e_lo, o, 64);
+    e_bad += __shfl_xor(e_bad, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0 && e_cnt) {
+    atomicAdd(&s_epe[0], e_cnt);
+    atomicAdd(&s_epe[1], e_hi);
+    atomicAdd(&s_epe[2], e_lo);
+    atomicAdd(&s_epe[3], e_bad);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 3 * K; i += blockDim.x)
+    if (s_cnt[i]) atomicAdd(state + i, (unsigned long long)s_cnt[i]);
+  for (int k = threadIdx.x; k < K; k += blockDim.x) {
+    unsigned long long run = 0;
+    for (int i = 0; i < num_step; ++i) {
+      run += s_cnt[(3 + i) * K + k];
+      if (run) atomicAdd(state + (int64_t)(3 + i) * K + k, run);
+    }
+  }
+  if (threadIdx.x < 4 && s_epe[threadIdx.x]) atomicAdd(state + (int64_t)(3 + num_step) * K + threadIdx.x, s_epe[threadIdx.x]);
+}
+
+// out = acc[K] | pck | cnt | auc | epe, all double
+__global__ void __launch_bounds__(256) k_eval_finalize(const long long* __restrict__ st, int K, int num_step,
+                                                       double* __restrict__ out) {
+  extern __shared__ double s_avg[];          // [num_step] mean accuracy at threshold i / num_step
+  for (int k = threadIdx.x; k < K; k += blockDim.x)
+    out[k] = st[k] > 0 ? (double)st[K + k] / (double)st[k] : -1.0;
+  for (int i = threadIdx.x; i < num_step; i += blockDim.x) {
+    double s = 0;
+    int c = 0;
+    for (int k = 0; k < K; ++k)
+      if (st[2 * K + k] > 0) {
+        s += (double)st[(int64_t)(3 + i) * K + k] / (double)st[2 * K + k];
+        ++c;
+      }
+    s_avg[i] = c > 0 ? s / c : 0.0;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0;
+    int c = 0;
+    for (int k = 0; k < K; ++k)
+      if (st[k] > 0) {
+        s += (double)st[K + k] / (double)st[k];
+        ++c;
+      }
+    out[K] = c > 0 ? s / c : 0.0;
+    out[K + 1] = (double)c;
+    double a = 0;
+    for (int i = 0; i < num_step; ++i) a += s_avg[i];
+    out[K + 2] = a / num_step;
+    const long long* ep = st + (int64_t)(3 + num_step) * K;
+    const double sum = (double)ep[1] + (double)ep[2] * (1.0 / 4294967296.0);
+    out[K + 3] = ep[3] ? (double)NAN : sum / (double)(ep[0] > 1 ? ep[0] : 1);
+  }
+}
+
+extern "C" int64_t lhn_eval_state_bytes(int K, int num_step) {
+  if (K <= 0 || num_step <= 0 || (int64_t)(3 + num_step) * K > LHN_EVAL_MAX_WORDS) return 0;
+  return ((int64_t)(3 + num_step) * K + 4) * 8;
+}
+
+extern "C" int lhn_eval_accumulate(const float* pred, const float* gt, const uint8_t* mask, const float* pck_normalize,
+                                   float pck_thr, double auc_normalize, int num_step, void* state, int N, int K, void* stream) {
+  LHN_CHECK_ARG(pred && gt && mask && state, "lhn_eval_accumulate: null pointer");
+  LHN_CHECK_ARG(N > 0 && K > 0, "lhn_eval_accumulate: bad shape N=%d K=%d", N, K);
+  LHN_CHECK_ARG(lhn_eval_state_bytes(K, num_step) > 0, "lhn_eval_accumulate: (3 + num_step) * K must be in 1..%d (K=%d num_step=%d)",
+                LHN_EVAL_MAX_WORDS, K, num_step);
+  const int64_t NK = (int64_t)N * K, want = (NK + 1023) / 1024, cap = (int64_t)lhn_num_cus() * 4;
+  const int grid = (int)(want < cap ? want : cap);
+  hipLaunchKernelGGL(k_eval_accumulate, dim3(grid), dim3(256), (size_t)(3 + num_step) * K * sizeof(unsigned), (hipStream_t)stream,
+                     pred, gt, mask, pck_normalize, pck_thr, auc_normalize, num_step, (unsigned long long*)state, NK, K);
+  LHN_CHECK_LAUNCH("lhn_eval_accumulate");
+  return 0;
+}
+
+extern "C" int lhn_eval_finalize(const void* state, int K, int num_step, double* out, void* stream) {
+  LHN_CHECK_ARG(state && out, "lhn_eval_finalize: null pointer");
+  LHN_CHECK_ARG(lhn_eval_state_bytes(K, num_step) > 0, "lhn_eval_finalize: (3 + num_step) * K must be in 1..%d (K=%d num_step=%d)",
+                LHN_EVAL_MAX_WORDS, K, num_step);
+  hipLaunchKernelGGL(k_eval_finalize, dim3(1), dim3(256), (size_t)num_step * sizeof(double), (hipStream_t)stream,
+                     (const long long*)state, K, num_step, out);
+  LHN_CHECK_LAUNCH("lhn_eval_finalize");
+  return 0;
+}

@@ -2,7 +2,8 @@
 datasets/data_pipeline/generateTarget.py (TopDownGenerateTarget, MSRA branches),
 utils/post_processing/evaluation/top_down_eval.py (_get_max_preds, keypoints_from_heatmaps 'default',
 keypoint_pck_accuracy), datasets/data_pipeline/post_transforms.py (transform_preds),
-utils/post_processing/decoder.py (TopDownDecoder) and utils/HeatmapParser.py:41-50 (nms)."""
+utils/post_processing/decoder.py (TopDownDecoder), utils/HeatmapParser.py:41-50 (nms) and
+datasets/datasets/base_dataset.py:193-261 (_report_metric: dataset-level PCK / AUC / EPE, TopDownEvaluator)."""
 import ctypes as C
 
 import numpy as np
@@ -275,12 +276,17 @@ class TopDownDecoder:
         res["output_heatmap"] = out.detach().cpu().numpy()
         return res
 
-    def decode(self, meta, model_output, post_process=None):
+    def _keypoints(self, meta, model_output, post_process=None):
+        """The device half of decode(), shared with TopDownEvaluator.update: nothing here waits for the GPU."""
         pp = post_process or self.post_process
         out = model_output[:, :self.num_joints]
         center, scale = _dev(meta["center"], out.device).float(), _dev(meta["scale"], out.device).float()
         hm_preds, preds, maxvals = keypoints_from_heatmaps(out, center, scale, post_process=pp, kernel=self.kernel,
                                                            use_udp=self.use_udp)
+        return out, center, scale, hm_preds, preds, maxvals
+
+    def decode(self, meta, model_output, post_process=None):
+        out, center, scale, hm_preds, preds, maxvals = self._keypoints(meta, model_output, post_process)
         res = dict(image_paths=meta.get("image_file"), bbox_ids=self._ids(meta))
         small = [("preds", torch.cat([preds, maxvals], dim=2)), ("hm_preds", torch.cat([hm_preds * 4, maxvals], dim=2)),
                  ("boxes", self._boxes(meta, center, scale, out.device))]
@@ -295,3 +301,138 @@ class TopDownDecoder:
         res = dict(image_paths=meta.get("image_file"), bbox_ids=self._ids(meta))
         res = self._finish(res, [("preds", preds), ("boxes", self._boxes(meta, center, scale, out.device))], out)
         return {k: res[k] for k in ("preds", "boxes", "image_paths", "bbox_ids", "output_heatmap")}
+
+
+# ------------------------------------------------------------------ dataset-level metrics (PCK / AUC / EPE)
+def _eval_state(K, num_step, device):
+    nbytes = int(_lib.lib().lhn_eval_state_bytes(int(K), int(num_step)))
+    if nbytes <= 0:
+        raise _lib.LhnError(f"evaluation state: unsupported K={K}, num_step={num_step} ((3 + num_step) * K <= 8192)")
+    return torch.zeros(nbytes // 8, dtype=torch.int64, device=device)
+
+
+def _eval_accumulate(state, pred, gt, mask, pck_normalize, pck_thr, auc_normalize, num_step):
+    """One lhn_eval_accumulate launch on the current stream; nothing is read back."""
+    p = _lib.f32c(_dev(pred))
+    g = _lib.f32c(_dev(gt, p.device))
+    m = _dev(mask, p.device).to(torch.uint8).contiguous()
+    nz = None if pck_normalize is None else _lib.f32c(_dev(pck_normalize, p.device))
+    N, K, _ = p.shape
+    assert tuple(g.shape) == (N, K, 2) and tuple(m.shape) == (N, K) and p.shape[2] == 2
+    assert nz is None or tuple(nz.shape) == (N, 2)
+    if N == 0:
+        return
+    _lib.check(_lib.lib().lhn_eval_accumulate(_lib.ptr(p), _lib.ptr(g), _lib.ptr(m), _lib.ptr(nz), C.c_float(pck_thr),
+                                              C.c_double(auc_normalize), int(num_step), _lib.ptr(state), N, K,
+                                              _lib.stream()), "lhn_eval_accumulate")
+
+
+def _eval_finalize(state, K, num_step):
+    """-> host float64 [K + 4] = acc[K] | pck | cnt | auc | epe: the ONE read-back of an evaluation."""
+    out = torch.empty(K + 4, dtype=torch.float64, device=state.device)
+    _lib.check(_lib.lib().lhn_eval_finalize(_lib.ptr(state), int(K), int(num_step), _lib.ptr(out), _lib.stream()),
+               "lhn_eval_finalize")
+    return out.cpu().numpy()
+
+
+def keypoint_auc(pred, gt, mask, normalize, num_step=20):
+    """top_down_eval.py:168-196 -> float."""
+    p = _lib.f32c(_dev(pred))
+    K = p.shape[1]
+    st = _eval_state(K, num_step, p.device)
+    _eval_accumulate(st, p, gt, mask, None, 0.0, float(normalize), num_step)
+    return float(_eval_finalize(st, K, num_step)[K + 2])
+
+
+def keypoint_epe(pred, gt, mask):
+    """top_down_eval.py:104-126 -> float."""
+    p = _lib.f32c(_dev(pred))
+    K = p.shape[1]
+    st = _eval_state(K, 1, p.device)
+    _eval_accumulate(st, p, gt, mask, None, 0.0, 1.0, 1)
+    return float(_eval_finalize(st, K, 1)[K + 3])
+
+
+class TopDownEvaluator:
+    """Streaming replacement of `test_set.evaluate(results, ..., ['PCK', 'AUC', 'EPE'])` (test.py:114-128 ->
+    base_dataset.py:193-261 _report_metric): per-joint integer counts and an exact fixed-point EPE sum live in one int64
+    device tensor (layout: include/lhn.h), `update` adds a batch with one launch and reads nothing back, `compute` divides
+    once.  Any batch split, batch order or sharding over processes (`reduce_`) gives the same state.  Left to the caller:
+    feeding each sample once (no `bbox_id` de-duplication), the JSON result file, PCKh and NME."""
+
+    METRICS = ("PCK", "AUC", "EPE")
+
+    def __init__(self, cfg, metrics=("PCK", "AUC", "EPE"), pck_thr=0.2, auc_nor=30, num_step=20):
+        metrics = [metrics] if isinstance(metrics, str) else list(metrics)
+        for m in metrics:
+            if m not in self.METRICS:
+                raise _lib.LhnError(f"TopDownEvaluator: metric {m} is not built (PCK, AUC, EPE are)")
+        self.metrics, self.pck_thr, self.auc_nor, self.num_step = metrics, float(pck_thr), float(auc_nor), int(num_step)
+        self.decoder = TopDownDecoder(cfg, as_numpy=False)
+        self.num_joints = int(cfg.DATASET.num_joints)
+        self._state = None
+
+    def _st(self, device=None):
+        if self._state is None:
+            _lib.require_device()
+            self._state = _eval_state(self.num_joints, self.num_step, device or torch.device("cuda", torch.cuda.current_device()))
+        return self._state
+
+    def reset(self):
+        if self._state is not None:
+            self._state.zero_()
+
+    def update_preds(self, preds, gt, mask, bbox_thr):
+        """preds [N,K,2|3], gt [N,K,2|3] image pixels, mask [N,K], bbox_thr [N] | [N,1] | [N,2] (the PCK normaliser)."""
+        p = _dev(preds if torch.is_tensor(preds) else np.asarray(preds))[..., :2]
+        g = _dev(gt if torch.is_tensor(gt) else np.asarray(gt), p.device)[..., :2]
+        t = _dev(bbox_thr if torch.is_tensor(bbox_thr) else np.asarray(bbox_thr), p.device).float().reshape(p.shape[0], -1)
+        if t.shape[1] == 1:
+            t = t.expand(-1, 2)
+        _eval_accumulate(self._st(p.device), p, g, mask if torch.is_tensor(mask) else np.asarray(mask), t, self.pck_thr,
+                         self.auc_nor, self.num_step)
+
+    def update(self, meta, model_output, post_process=None):
+        """Decode as TopDownDecoder.decode does and add the batch (base_dataset.py:217-232: ground truth joints_3d[:, :2],
+        mask joints_3d_visible[:, 0] > 0, PCK normaliser max(bbox w, h))."""
+        preds = self.decoder._keypoints(meta, model_output, post_process)[4]
+        vis = torch.as_tensor(meta["joints_3d_visible"])[..., 0] > 0
+        thr = torch.as_tensor(meta["bbox"])[:, 2:4].max(dim=1).values
+        self.update_preds(preds, torch.as_tensor(meta["joints_3d"])[..., :2].contiguous(), vis.contiguous(), thr)
+
+    def reduce_(self, group=None):
+        """Sum the state over a torch.distributed process group (one all-reduce); a no-op without an initialised group."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            return self
+        st = self._st()
+        if "nccl" in str(dist.get_backend(group)):
+            dist.all_reduce(st, group=group)
+        else:                                   # host backends (gloo): the state is a few KB
+            h = st.cpu()
+            dist.all_reduce(h, group=group)
+            st.copy_(h)
+        return self
+
+    def state(self):
+        """The raw counts as host numpy int64 (one read-back): valid_pck / hit_pck / valid_auc [K], hit_auc [num_step, K],
+        epe_cnt, epe_hi (whole pixels), epe_lo (2^-32 px), epe_bad."""
+        K, S = self.num_joints, self.num_step
+        h = self._st().cpu().numpy()
+        e = h[(3 + S) * K:]
+        return dict(valid_pck=h[:K].copy(), hit_pck=h[K:2 * K].copy(), valid_auc=h[2 * K:3 * K].copy(),
+                    hit_auc=h[3 * K:(3 + S) * K].reshape(S, K).copy(), epe_cnt=int(e[0]), epe_hi=int(e[1]), epe_lo=int(e[2]),
+                    epe_bad=int(e[3]))
+
+    def _final(self):
+        return _eval_finalize(self._st(), self.num_joints, self.num_step)
+
+    def per_joint_pck(self):
+        """acc [K] float64, -1 for a joint without a valid sample."""
+        return self._final()[:self.num_joints].copy()
+
+    def compute(self):
+        """[("PCK", ...), ("AUC", ...), ("EPE", ...)]: names and order of _report_metric, the chosen metrics only."""
+        o, K = self._final(), self.num_joints
+        val = dict(PCK=float(o[K]), AUC=float(o[K + 2]), EPE=float(o[K + 3]))
+        return [(m, val[m]) for m in self.METRICS if m in self.metrics]
