@@ -74,6 +74,7 @@ __global__ void __launch_bounds__(256, NS > 1 ? 1 : ((CIN == 64 && NT == 2) || (
   const int c4 = tid % C4, row0 = tid / C4;
   const bool kok = 4 * c4 < x.C;                     // channel groups beyond the view are zero columns of the tile
   const int cabs = x.coff + (kok ? 4 * c4 : 0);
+  const int kleft = geo.kvalid - 4 * c4;             // real input channels from this thread's group on (>= 4: all four)
   const Xf4 xf = lhn_load_xf(x, cabs);
   const int HoWo = y.H * y.W;
   // extra sources (NS > 1): own buffer, table, gate, channel offset
@@ -128,8 +129,14 @@ __global__ void __launch_bounds__(256, NS > 1 ? 1 : ((CIN == 64 && NT == 2) || (
               if (ex.v[e].gate) u *= *reinterpret_cast<const f4*>(ex.v[e].gate + (int64_t)(m / HoWo) * ex.v[e].cstride + ecabs[e]);
               v += u * ex.coef[e + 1];
             }
-          if (ex.sum_out) *reinterpret_cast<f4*>(ex.sum_out + (int64_t)m * ex.so_cstride + ex.so_coff + 4 * c4) = v;
         }
+        if (kleft < 4) {      // pad channels of a view wider than the weight (w_cols): zero weights do not cancel a NaN / inf
+          if (kleft < 1) v.x = 0.f;
+          if (kleft < 2) v.y = 0.f;
+          if (kleft < 3) v.z = 0.f;
+          v.w = 0.f;
+        }
+        if (NS > 1 && ex.sum_out) *reinterpret_cast<f4*>(ex.sum_out + (int64_t)m * ex.so_cstride + ex.so_coff + 4 * c4) = v;
       }
       *reinterpret_cast<f4*>(As + row * LDA + 4 * c4) = v;
     }
@@ -479,15 +486,20 @@ static int launch_pw_fwd_wr(const lhn_view* x, const float* w, const float* bias
   return 0;
 }
 
+// LHN_PW_LDSW=1: always take the LDS-resident-W kernel (A/B comparisons)
+static bool pw_wr_off() {
+  static int off = -1;
+  if (off < 0) {
+    const char* e = getenv("LHN_PW_LDSW");
+    off = (e && e[0] == '1') ? 1 : 0;
+  }
+  return off == 1;
+}
+
 // returns -1 when the register-resident-weights kernel has no instance for the shape
 static int pw_fwd_wr(const lhn_view* x, const float* w, const float* bias, const lhn_view* y, double* stats, int cout, hipStream_t s,
                      const PwExtra* ex, const PwGeom& geo, int wt = 0, const lhn_bnfin* fin = nullptr) {
-  static int off = -1;
-  if (off < 0) {
-    const char* e = getenv("LHN_PW_LDSW");      // 1 = always take the LDS-resident-W kernel (A/B comparisons)
-    off = (e && e[0] == '1') ? 1 : 0;
-  }
-  if (off) return -1;
+  if (pw_wr_off()) return -1;
   const int ci = x->C, ncot = cout <= 32 ? 1 : cout <= 64 ? 2 : 4;
   const bool ms = ex && ex->n > 0;
   // K = 256 (hourglassnet.py: every 1x1 of the C = 256 residuals) in ONE pass: 128 VGPRs of W per lane, no second K slice that
@@ -511,12 +523,7 @@ static int pw_fwd_wr(const lhn_view* x, const float* w, const float* bias, const
 // (k_dy_inplace ran) as a view of C = 32/64/128 output features, dxv: <= 128 input channels of the gradient buffer,
 // w = &W[co0][ci0], wstride = Cin of the whole weight.  Returns -1 when there is no instance for the shape.
 int lhn_pw_dgrad_wr(const lhn_view* dyv, const float* w, const lhn_view* dxv, int wstride, int accumulate, hipStream_t s) {
-  static int off = -1;
-  if (off < 0) {
-    const char* e = getenv("LHN_PW_LDSW");
-    off = (e && e[0] == '1') ? 1 : 0;
-  }
-  if (off) return -1;
+  if (pw_wr_off()) return -1;
   PwGeom g;
   g.wstride = wstride;
   g.kvalid = dyv->C;
@@ -605,14 +612,14 @@ extern "C" int lhn_conv_pw_fwd2(const lhn_view* x, const float* w, const float* 
   } else {
     LHN_CHECK_ARG(!(opts && opts->sum_out), "lhn_conv_pw_fwd: sum_out without extra sources");
   }
-  // Cin = 256 with full-width rows: the register-W kernel takes the whole K at once (LHN_PW_K256=0: two K slices, the second
-  // one accumulating into y)
+  // Cin = 256 with full-width rows: the register-W kernel takes the whole K at once (LHN_PW_K256=0, or LHN_PW_LDSW=1 which has
+  // no register-W kernel to take it: two K slices, the second one accumulating into y)
   static int k256 = -1;
   if (k256 < 0) {
     const char* e = getenv("LHN_PW_K256");
     k256 = (e && e[0] == '0') ? 0 : 1;
   }
-  const int kstep = (k256 && Cin == 256 && wcols == 256 && stride == 1 && !y_nchw && ex.n == 0 && Cout % 128 == 0 && wrows == Cout &&
+  const int kstep = (k256 && !pw_wr_off() && Cin == 256 && wcols == 256 && stride == 1 && !y_nchw && ex.n == 0 && Cout % 128 == 0 && wrows == Cout &&
                      (reinterpret_cast<uintptr_t>(w) & 15) == 0 && !(fin && stats && single)) ? 256 : 128;
   for (int co0 = 0; co0 < Cout; co0 += 128) {
     const int cc = Cout - co0 < 128 ? Cout - co0 : 128;
