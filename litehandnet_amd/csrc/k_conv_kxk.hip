@@ -161,6 +161,12 @@ __global__ void __launch_bounds__(256) k_kxk(lhn_view x, const float* __restrict
       // tap-major copy of the weights (k_w_tapmajor): row = output feature of this GEMM, KD contiguous floats per row ->
       // 16-byte loads/stores instead of 4-byte gathers with a 36-byte stride (which cost more than the MFMAs of a phase)
       constexpr int NWV = 32 * NT * KD / 4 / 256, K4 = KD / 4;
+      // NWV < 4 (32 * NT * KD < 4096): the fixed group of four below runs past the W image, and vector j >= NWV of thread tid
+      // lands in As at exactly the slot that commit() writes for p = j - NWV of the SAME thread (both map the linear index
+      // tid + 256 * j to (row, k4) the same way, and 32 * NT * K4 == 256 * NWV).  commit() always follows stage_w() before the
+      // barrier, so the stray value is overwritten in program order by its own thread: in bounds (j - NWV < PF), no effect.
+      // That holds only while the two mappings stay equal -- change either and this becomes an LDS write-write race
+      // between waves; bound the loop by NWV then.
 #pragma unroll
       for (int j0 = 0; j0 < NWV; j0 += 4) {
         f4 t[4];
@@ -564,11 +570,16 @@ static int kxk_nt_block(int M, int nt) {
   return nt / splits;
 }
 
+// The instantiated (K, tiles-per-block) pairs of k_kxk / k_kxk_wgrad: K = 32, 64 or 128 channels exactly, 1, 2 or 4 tiles of 32.
+static bool kxk_instance_ok(int k, int nt) { return (k == 32 || k == 64 || k == 128) && (nt == 1 || nt == 2 || nt == 4); }
+
 extern "C" int lhn_conv_kxk_fwd(const lhn_view* x, const float* w, const lhn_view* y, double* stats, int stride,
                                 const lhn_bnfin* fin, float* wt_scratch, void* stream) {
   LHN_CHECK_ARG(lhn_view_ok(x) && lhn_view_ok(y) && w && lhn_no_pend(x), "lhn_conv_kxk_fwd: bad view / null pointer (no pending BatchNorm here)");
   LHN_CHECK_ARG((stride == 1 || stride == 2) && kxk_geometry_ok(x, y, stride), "lhn_conv_kxk_fwd: geometry / stride %d", stride);
   const int ntot = (y->C + 31) / 32, nt = (ntot == 1 || ntot == 2 || ntot == 4) ? kxk_nt_block(y->N * y->H * y->W, ntot) : ntot;
+  // decided BEFORE the first launch: a refused call writes nothing (not even the weight scratch)
+  LHN_CHECK_ARG(kxk_instance_ok(x->C, nt), "lhn_conv_kxk_fwd: unsupported channels Cin=%d Cout=%d", x->C, y->C);
   hipStream_t s = (hipStream_t)stream;
   int rc = -1;
   if (wt_scratch) launch_w_tapmajor(w, wt_scratch, y->C, x->C, 0, s);
@@ -589,26 +600,32 @@ extern "C" int lhn_conv_kxk_bwd(const lhn_view* x, const float* w, const lhn_vie
   if (nrep < 1) nrep = 1;
   hipStream_t s = (hipStream_t)stream;
   int rc = -1;
-  // large channel counts (or a channel-attention pooled gradient): turn dz into dy in place, then stream it plain
+  // Every instance is decided BEFORE the first launch: k_dy_inplace consumes dz and the dgrad writes dx, so a call refused
+  // after them would leave both changed.
+  const int wtot = (y->C + 31) / 32, wtiles = (y->N * y->H * y->W + 63) / 64;
+  // Cout >= 64: one 32-channel group per block (gridDim.z), pixel chunks = gradient replicas -> atomic-free flush
+  // (only while a pixel chunk stays short: <= 16 tiles of 64 pixels per block; big maps amortise the atomic flush)
+  const int cosplit = (wtot == 2 || wtot == 4) && x->C >= 64 && nrep > 1 && wtiles <= 16 * nrep ? wtot : 1, nto = wtot / cosplit;
+  const int dtot = (x->C + 31) / 32, dnt = (dtot == 1 || dtot == 2 || dtot == 4) ? kxk_nt_block(x->N * x->H * x->W, dtot) : dtot;
+  LHN_CHECK_ARG((!dx || kxk_instance_ok(y->C, dnt)) && kxk_instance_ok(x->C, nto), "lhn_conv_kxk_bwd: unsupported channels Cin=%d Cout=%d",
+                x->C, y->C);
+  // large channel counts: turn dz into dy in place, then stream it plain (LHN_PLAIN=0/1 overrides the size rule).  A
+  // channel-attention pooled gradient always takes this path: lhn_dy_fast has no pooled term.
   const char* pe = getenv("LHN_PLAIN");
-  const bool plain = pe ? (pe[0] == '1') : ((x->C * y->C >= 64 * 64) || gy->dpool);
+  const bool plain = gy->dpool || (pe ? (pe[0] == '1') : (x->C * y->C >= 64 * 64));
   if (plain) launch_dy_inplace(y, gy, s);
   if (dx) {
     // GEMM N = Cin, K = Cout
     const int par = stride == 2 ? 1 : 0;     // stride 2: four parity classes of input pixels (gridDim.z)
     if (wt_scratch) launch_w_tapmajor(w, wt_scratch, y->C, x->C, 1, s);
-    const int ntot = (x->C + 31) / 32, nt = (ntot == 1 || ntot == 2 || ntot == 4) ? kxk_nt_block(x->N * x->H * x->W, ntot) : ntot;
+    const int ntot = dtot, nt = dnt;
 #define KB(CO, NTV) if (y->C == CO && nt == NTV) rc = plain ? launch_kxk<CO, NTV, 1, 9, true>(x, w, y, gy, nullptr, dx, dx_accumulate, stride, x->C, s, nullptr, ntot / nt, par, wt_scratch) : launch_kxk<CO, NTV, 1, 9, false>(x, w, y, gy, nullptr, dx, dx_accumulate, stride, x->C, s, nullptr, ntot / nt, par, wt_scratch);
     KB(32, 1) KB(64, 2) KB(128, 4) KB(32, 2) KB(64, 1) KB(64, 4) KB(128, 2) KB(128, 1) KB(32, 4)
 #undef KB
-    LHN_CHECK_ARG(rc != -1, "lhn_conv_kxk_bwd: unsupported channels Cin=%d Cout=%d", x->C, y->C);
+    LHN_CHECK_ARG(rc != -1, "lhn_conv_kxk_bwd: unsupported channels Cin=%d Cout=%d", x->C, y->C);      // (kxk_instance_ok lists them all)
     if (rc) return rc;
   }
   rc = -1;
-  // Cout >= 64: one 32-channel group per block (gridDim.z), pixel chunks = gradient replicas -> atomic-free flush
-  // (only while a pixel chunk stays short: <= 16 tiles of 64 pixels per block; big maps amortise the atomic flush)
-  const int ntot = (y->C + 31) / 32, wtiles = (y->N * y->H * y->W + 63) / 64;
-  const int cosplit = (ntot == 2 || ntot == 4) && x->C >= 64 && nrep > 1 && wtiles <= 16 * nrep ? ntot : 1, nto = ntot / cosplit;
 #define KW(CI, NTV) if (x->C == CI && nto == NTV) rc = plain ? launch_kxk_wgrad<CI, NTV, 9, true>(x, y, gy, dw, stride, nrep, rep_stride, s, cosplit) : launch_kxk_wgrad<CI, NTV, 9, false>(x, y, gy, dw, stride, nrep, rep_stride, s, cosplit);
   KW(32, 1) KW(64, 2) KW(128, 4) KW(32, 2) KW(64, 1) KW(64, 4) KW(128, 2) KW(128, 1) KW(32, 4)
 #undef KW
