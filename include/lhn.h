@@ -268,6 +268,18 @@ int lhn_conv_dw_fwd3(const lhn_view* x, const float* w, const lhn_view* y, doubl
  * Built for Cin == Cm == 64 (any N, H, W); any other channel count returns the invalid-argument status and writes nothing. */
 int lhn_conv_pw_dw3_fwd(const lhn_view* x, const float* w1 /*[Cm,Cin]*/, const float* t_table /*[3][Cm] or NULL*/,
                         const float* w2 /*[Cm,1,3,3]*/, const lhn_view* y, void* stream);
+/* Inference only: DWConv (liteHandNet.py:8-21 over repblocks.py:8-44), RepConv depthwise 3x3 then RepConv 1x1, in one launch --
+ * the tensor between the two convolutions never reaches memory.  Per image:
+ *   u     = depthwise 3x3 of value(x), stride 1, dilation dil (1 or 2), padding dil; value(x) padded with ZEROS
+ *   t     = lrelu_slope(scale * u + shift)            t_table = [3][Cin] scale | shift | slope (NULL = identity)
+ *   y_raw = w_pw . t (+ bias)                          stored raw into channels [y.coff, y.coff + Cout) of y
+ * value(x) is the view's own table and gate applied on load, exactly as lhn_conv_dw_fwd3 does; a pixel outside the map is 0, not
+ * lrelu(shift_x).  y keeps its own pending BatchNorm / activation in its table as lhn_conv_pw_fwd leaves them.  No statistics, no
+ * atomics: repeated calls give identical bits.  Built for Cin, Cout in {32, 64} (any N, H, W); any other channel count, a dilation
+ * outside {1, 2} or a y view that overlaps x's channels in the same buffer returns the invalid-argument status ("unsupported
+ * shape") and writes nothing. */
+int lhn_conv_dw3_pw_fwd(const lhn_view* x, const float* w_dw /*[Cin,1,3,3]*/, int dil, const float* t_table /*[3][Cin] or NULL*/,
+                        const float* w_pw /*[Cout,Cin]*/, const float* bias /*[Cout] or NULL*/, const lhn_view* y, void* stream);
 int lhn_conv_stem_fwd(const float* img /*[N,3,Hi,Wi]*/, const float* w /*[Cout,3,k,k]*/, const lhn_view* y,
                       double* stats, int Hi, int Wi, int k, int stride, int pad, const lhn_bnfin* fin, void* stream);
 /* wt_scratch: optional 9*Cout*Cin floats of caller-owned scratch; the call re-lays the OIHW weights tap-major into it

@@ -23,7 +23,7 @@ static lhn_bnsum mkbns(void* ws, int64_t sums_off, int64_t save_off, int C, int 
 enum {
   OP_STEM = 1, OP_PW = 2, OP_DW = 3, OP_KXK = 4, OP_FINALIZE = 5, OP_EW = 6, OP_MAXPOOL = 7, OP_AVGPOOL = 8,
   OP_CA_MLP = 9, OP_TABLE_FILL = 10, OP_MEMSET = 11, OP_ATT_MLP = 12, OP_SE_MLP = 13, OP_SHUFFLE = 14,
-  OP_PWDW = 15,
+  OP_PWDW = 15, OP_DWPW = 16,
   OP_STEM_BWD = 101, OP_PW_BWD = 102, OP_DW_BWD = 103, OP_KXK_BWD = 104, OP_BN_BWD = 105, OP_EW_BWD = 106,
   OP_MAXPOOL_BWD = 107, OP_AVGPOOL_BWD = 108, OP_GATE_REDUCE = 109, OP_CA_MLP_BWD = 110, OP_ATT_MLP_BWD = 111, OP_SE_MLP_BWD = 112,
   OP_SHUFFLE_BWD = 113,
@@ -335,6 +335,18 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
         lhn_view y = mkview(P, ws, o.out_buf, o.out_coff, o.out_C);
         rc = lhn_conv_pw_dw3_fwd(&x, prm<const float>(params, o.p[0]), reinterpret_cast<const float*>(at(ws, P->bufs[o.in_buf[1]].table_off)),
                                  prm<const float>(params, o.p[1]), &y, stream);
+        break;
+      }
+      case OP_DWPW: {  // in: x, the intermediate buffer (only its table exists); p: w_dw, w_pw, bias or -1; i[0] = dilation.  Inference plans only.
+        if (training) {
+          lhn_set_error("lhn_plan_run: a fused depthwise -> 1x1 launch has no batch statistics (inference plans only)");
+          rc = 1;
+          break;
+        }
+        lhn_view x = mkview(P, ws, o.in_buf[0], o.in_coff[0], o.in_C[0]);
+        lhn_view y = mkview(P, ws, o.out_buf, o.out_coff, o.out_C);
+        rc = lhn_conv_dw3_pw_fwd(&x, prm<const float>(params, o.p[0]), o.i[0], reinterpret_cast<const float*>(at(ws, P->bufs[o.in_buf[1]].table_off)),
+                                 prm<const float>(params, o.p[1]), prm<const float>(params, o.p[2]), &y, stream);
         break;
       }
       case OP_FINALIZE: {

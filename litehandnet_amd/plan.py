@@ -26,6 +26,7 @@ from ._lib import Buf, Op
 # op kinds (must match csrc/lhn_plan.cpp)
 STEM, PW, DW, KXK, FINALIZE, EW, MAXPOOL, AVGPOOL, CA_MLP, TABLE_FILL, MEMSET, ATT_MLP, SE_MLP, SHUFFLE = range(1, 15)
 PWDW = 15              # inference plans only: 1x1 -> depthwise 3x3 in one launch (lhn_conv_pw_dw3_fwd), see PlanBuilder.fuse_pw_dw
+DWPW = 16              # inference plans only: depthwise 3x3 -> 1x1 in one launch (lhn_conv_dw3_pw_fwd), see PlanBuilder.fuse_dw_pw
 STEM_BWD, PW_BWD, DW_BWD, KXK_BWD, BN_BWD, EW_BWD, MAXPOOL_BWD, AVGPOOL_BWD, GATE_REDUCE, CA_MLP_BWD, ATT_MLP_BWD, SE_MLP_BWD, SHUFFLE_BWD = range(101, 114)
 SLOPE_SILU = 2.0       # LHN_SLOPE_SILU in include/lhn.h: the combine applies SiLU instead of a leaky ReLU
 SLOPE_RELU_SIGMOID = 3.0   # LHN_SLOPE_RELU_SIGMOID: sigmoid(relu(v)) (lite_hrnet.py: nn.ReLU followed by nn.Sigmoid)
@@ -69,6 +70,21 @@ def set_infer_fuse(on):
 def infer_fuse_enabled():
     """LHN_INFER_FUSE=1 (default off): plans without a backward run RepBasicUnit's 1x1 -> depthwise 3x3 pairs as one launch."""
     return _INFER_FUSE if _INFER_FUSE is not None else os.environ.get("LHN_INFER_FUSE", "0") == "1"
+
+
+_INFER_FUSE_DWPW = None     # set_infer_fuse_dwpw(): in-process override of LHN_INFER_FUSE_DWPW
+
+
+def set_infer_fuse_dwpw(on):
+    """Switch the depthwise -> 1x1 inference fusion pass (PlanBuilder.fuse_dw_pw) on or off for plans built from now on; None =
+    follow the environment again.  Independent of set_infer_fuse; Engine.plan_for keys its cache on both."""
+    global _INFER_FUSE_DWPW
+    _INFER_FUSE_DWPW = None if on is None else bool(on)
+
+
+def infer_fuse_dwpw_enabled():
+    """LHN_INFER_FUSE_DWPW=1 (default off): plans without a backward run DWConv's depthwise 3x3 -> 1x1 pairs as one launch."""
+    return _INFER_FUSE_DWPW if _INFER_FUSE_DWPW is not None else os.environ.get("LHN_INFER_FUSE_DWPW", "0") == "1"
 
 
 def _refs_in(v):
@@ -137,7 +153,7 @@ class _BufRec:
     coef: bool = False
     dpool: bool = False
     lazy: object = None      # the EW record of a sum that is taken ON LOAD by its consumers (never written in forward)
-    fused: bool = False      # the tensor between the two convolutions of a PWDW launch: a table, no data
+    fused: bool = False      # the tensor between the two convolutions of a PWDW / DWPW launch: a table, no data
     off: dict = field(default_factory=dict)
 
 
@@ -181,12 +197,14 @@ class _BwdFusions:
 class PlanBuilder:
     _no_grad_buf = -1   # the image never needs a gradient
 
-    def __init__(self, N, state_index, image_hw=None, with_backward=True, p_drop=0.0, infer_fuse=None):
+    def __init__(self, N, state_index, image_hw=None, with_backward=True, p_drop=0.0, infer_fuse=None, infer_fuse_dwpw=None):
         self.N = N
         # inference fusion (fuse_pw_dw): None = the process-wide switch.  The fused launch has no batch statistics, so the
         # caller passes False for a plan that will run train-mode BatchNorm under no_grad (Engine.plan_for).
         self.infer_fuse = infer_fuse_enabled() if infer_fuse is None else bool(infer_fuse)
         self.n_fused = 0
+        self.infer_fuse_dwpw = infer_fuse_dwpw_enabled() if infer_fuse_dwpw is None else bool(infer_fuse_dwpw)   # fuse_dw_pw, likewise
+        self.n_fused_dwpw = 0
         self.state_index = state_index      # id(tensor) -> index in the params array
         self.bufs = []
         self.recs = []                      # forward records (python dicts)
@@ -735,9 +753,89 @@ class PlanBuilder:
         self.n_fused += len(pairs)
         return len(pairs)
 
+    # Channel counts and dilations lhn_conv_dw3_pw_fwd is built for (csrc/k_conv_dwpw.hip: dw3_pw_supported); any map size.
+    FUSE_DW_PW_CHANNELS = (32, 64)
+    FUSE_DW_PW_DILATIONS = (1, 2)
+
+    def _fusable_dw_pw(self, q, uses):
+        """The 1x1 record that can share a launch with the depthwise record q, or None.  The pair: a 3x3 depthwise convolution
+        (stride 1, padding == dilation, one plain source) into a whole, ungated buffer whose ONLY reader is a stride-1 1x1 of one
+        source over all of it, with channel counts the entry point accepts."""
+        if q["op"] != DW or (q["k"], q["stride"]) != (3, 1) or q["pad"] != q["dil"] or q["dil"] not in self.FUSE_DW_PW_DILATIONS or \
+                q["conv"].weight is None or q.get("bn_repeat", 1) != 1 or self._xs(q)[1] != 1:
+            return None
+        x, t = q["x"], q["out"]
+        tb = self.bufs[t.buf]
+        if x.buf < 0 or x.C not in self.FUSE_DW_PW_CHANNELS or t.C != x.C or t.coff != 0 or tb.C != t.C or tb.gate or tb.lazy is not None:
+            return None
+        if any(v is not None and v.buf == t.buf for v in (self.in_ref, self.out_ref)):
+            return None
+        if q["bn"] is not None and getattr(q["conv"], "bias", None) is not None:
+            return None
+        r = None
+        for u, key in uses.get(t.buf, ()):
+            if u is q and key == "out":
+                continue
+            if u["op"] == TABLE_FILL and key == "out":       # deployed form: the depthwise convolution's pending bias / activation
+                continue
+            if u["op"] == PW and key == "x" and r is None:
+                r = u
+                continue
+            return None
+        if r is None or r["stride"] != 1 or r["nchw"] or r["wrc"] != (0, 0) or r["bn_repeat"] != 1 or self._xs(r)[1] != 1:
+            return None
+        rx, y = r["x"], r["out"]
+        if (rx.coff, rx.C) != (0, t.C) or y.C not in self.FUSE_DW_PW_CHANNELS or y.buf == t.buf:
+            return None
+        if r["bn"] is not None and getattr(r["conv"], "bias", None) is not None:
+            return None
+        if y.buf == x.buf and x.coff < y.coff + y.C and y.coff < x.coff + x.C:
+            return None
+        return r
+
+    def fuse_dw_pw(self):
+        """Inference plans with the switch on (infer_fuse_dwpw): DWConv, RepConv depthwise 3x3 (dilation 1 or 2) then RepConv 1x1
+        (liteHandNet.py:8-21), becomes ONE launch.  As in fuse_pw_dw the transform between the two convolutions is written into the
+        intermediate buffer's table by what fills it in the unfused plan (eval: FINALIZE from the running statistics; deployed: the
+        TABLE_FILL with the depthwise convolution's bias, which stays where it is), the fused kernel reads it as t_table, and the
+        intermediate buffer gets no data.  The launch stands where the 1x1 stood.  Plans with a backward are never rewritten."""
+        if self.with_backward or not self.infer_fuse_dwpw:
+            return 0
+        uses = {}
+        for r in self.recs:
+            for key, v in r.items():
+                for t in _refs_in(v):
+                    uses.setdefault(t.buf, []).append((r, key))
+        pairs = {}
+        for q in self.recs:
+            r = self._fusable_dw_pw(q, uses)
+            if r is not None:
+                pairs[id(r)] = q
+        drop = {id(q) for q in pairs.values()}
+        recs = []
+        for r in self.recs:
+            if id(r) in drop:
+                continue
+            q = pairs.get(id(r))
+            if q is None:
+                recs.append(r)
+                continue
+            t = q["out"]
+            if q["bn"] is not None:
+                recs.append(dict(op=FINALIZE, out=t, bn=q["bn"], slope=q["slope"]))
+            recs.append(dict(op=DWPW, x=q["x"], mid=t, out=r["out"], conv=q["conv"], conv2=r["conv"], dil=q["dil"],
+                             bias=None if r["bn"] is not None else r["conv"].bias))
+            if r["bn"] is not None:
+                recs.append(dict(op=FINALIZE, out=r["out"], bn=r["bn"], slope=r["slope"]))
+            self.bufs[t.buf].fused = True
+        self.recs = recs
+        self.n_fused_dwpw += len(pairs)
+        return len(pairs)
+
     # ------------------------------------------------------------------ finalize: the passes in the order they run
     def finalize(self):
         """Lower the records to what lhn_plan_create takes: (Buf array, forward Op array, backward Op array or None, n_fwd, n_bwd)."""
+        self.fuse_dw_pw()
         self.fuse_pw_dw()
         self._layout()
         self._plan_sum_out()
@@ -776,7 +874,7 @@ class PlanBuilder:
 
     # ------------------------------------------------------------------ forward lowering: one emitter per record family -> [Op]
     def _lower_forward(self):
-        emit = {STEM: self._fwd_conv, PW: self._fwd_conv, DW: self._fwd_conv, KXK: self._fwd_conv, PWDW: self._fwd_pwdw,
+        emit = {STEM: self._fwd_conv, PW: self._fwd_conv, DW: self._fwd_conv, KXK: self._fwd_conv, PWDW: self._fwd_pwdw, DWPW: self._fwd_dwpw,
                 FINALIZE: self._fwd_table, TABLE_FILL: self._fwd_table, EW: self._fwd_ew, SHUFFLE: self._fwd_pool,
                 MAXPOOL: self._fwd_pool, AVGPOOL: self._fwd_pool, CA_MLP: self._fwd_ca, SE_MLP: self._fwd_se, ATT_MLP: self._fwd_att}
         fwd = [self._mk(MEMSET, ws=(self.arena_base["zf"], self.ar["zf"].size))] if self.ar["zf"].size else []
@@ -814,8 +912,12 @@ class PlanBuilder:
     def _fwd_pwdw(self, r):
         return [self._mk(PWDW, ins=(r["x"], r["mid"]), out=r["out"], p=(self._p(r["conv"].weight), self._p(r["conv2"].weight)))]
 
+    def _fwd_dwpw(self, r):
+        return [self._mk(DWPW, ins=(r["x"], r["mid"]), out=r["out"], i=(r["dil"],),
+                         p=(self._p(r["conv"].weight), self._p(r["conv2"].weight), self._p(r["bias"])))]
+
     def _fwd_table(self, r):
-        """FINALIZE: eval-mode table of a convolution that runs inside a PWDW launch (no statistics to fold); TABLE_FILL: the
+        """FINALIZE: eval-mode table of a convolution that runs inside a PWDW / DWPW launch (no statistics to fold); TABLE_FILL: the
         pending bias / activation of a BatchNorm-free convolution."""
         if r["op"] == FINALIZE:
             bn = r["bn"]
