@@ -280,6 +280,26 @@ int lhn_conv_pw_dw3_fwd(const lhn_view* x, const float* w1 /*[Cm,Cin]*/, const f
  * shape") and writes nothing. */
 int lhn_conv_dw3_pw_fwd(const lhn_view* x, const float* w_dw /*[Cin,1,3,3]*/, int dil, const float* t_table /*[3][Cin] or NULL*/,
                         const float* w_pw /*[Cout,Cin]*/, const float* bias /*[Cout] or NULL*/, const lhn_view* y, void* stream);
+/* Inference only: one round of an MSRB (litehourglass.py:13-50 over repblocks.py:8-44, common.py:23-66) as one pass over the
+ * feature map -- both dilated depthwise 3x3 branches in one launch and, with pooled != NULL, the adaptive-average-pool means the
+ * round's ChannelAttension (OH = OW = 3) or SEBlock (OH = OW = 1) reads.  Half k (k = 0: dilation 1, padding 1; k = 1: dilation 2,
+ * padding 2; stride 1) consumes  coef2[0] * value(x[k]) + coef2[1] * value(extra[k])  (extra == NULL: value(x[k]) alone), the
+ * form lhn_conv_dw_fwd2 accepts; x[0], x[1] (and extra[0], extra[1]) are separate views of C/2 channels each, with their own
+ * buffer, cstride, coff, table and gate.  value() is the view's table and gate applied on load as lhn_conv_dw_fwd3 does; a pixel
+ * outside the map is 0, not lrelu(shift).  The raw results go to channels [y.coff, y.coff + C/2) and [y.coff + C/2, y.coff + C)
+ * of y; the BatchNorm / bias of each branch stays pending in y's table as lhn_conv_dw_fwd leaves it.
+ *   pooled[n, oh, ow, c] = mean over rows [floor(oh*H/OH), ceil((oh+1)*H/OH)) and the columns likewise of y's CONSUMED value: y's
+ *   table (current before the call; y has no gate yet) applied to the raw result -- what lhn_avgpool_fwd(y, pooled, OH, OW) would
+ *   write after the two depthwise launches, up to fp32 summation order.
+ * No float atomics: the launch writes per-(tile, bin, channel) sums into `scratch` (lhn_msrb_round_scratch_bytes, caller-owned, no
+ * initialisation needed) and a small second kernel of the same call folds them in a fixed order; repeated calls give identical
+ * bits.  Built for C/2 in {32, 64, 128}, any N, H, W.  Any other channel count, OH != OW or OH outside {1, 3} with pooled, pooled
+ * without scratch, or a y view that overlaps x[k] / extra[k] in the same buffer returns the invalid-argument status ("unsupported
+ * shape") and writes nothing. */
+int64_t lhn_msrb_round_scratch_bytes(int N, int H, int W, int C);   /* host-only, like lhn_eval_state_bytes; 0 = unsupported */
+int lhn_msrb_round_fwd(const lhn_view x[2], const lhn_view* extra /*[2] or NULL*/, const float* coef2 /*host, 2 floats, or NULL*/,
+                       const float* w_d1 /*[C/2,1,3,3]*/, const float* w_d2 /*[C/2,1,3,3]*/, const lhn_view* y /*C channels*/,
+                       float* pooled /*[N,OH,OW,C] or NULL*/, int OH, int OW, void* scratch, void* stream);
 int lhn_conv_stem_fwd(const float* img /*[N,3,Hi,Wi]*/, const float* w /*[Cout,3,k,k]*/, const lhn_view* y,
                       double* stats, int Hi, int Wi, int k, int stride, int pad, const lhn_bnfin* fin, void* stream);
 /* wt_scratch: optional 9*Cout*Cin floats of caller-owned scratch; the call re-lays the OIHW weights tap-major into it

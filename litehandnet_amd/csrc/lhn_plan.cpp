@@ -23,7 +23,7 @@ static lhn_bnsum mkbns(void* ws, int64_t sums_off, int64_t save_off, int C, int 
 enum {
   OP_STEM = 1, OP_PW = 2, OP_DW = 3, OP_KXK = 4, OP_FINALIZE = 5, OP_EW = 6, OP_MAXPOOL = 7, OP_AVGPOOL = 8,
   OP_CA_MLP = 9, OP_TABLE_FILL = 10, OP_MEMSET = 11, OP_ATT_MLP = 12, OP_SE_MLP = 13, OP_SHUFFLE = 14,
-  OP_PWDW = 15, OP_DWPW = 16,
+  OP_PWDW = 15, OP_DWPW = 16, OP_MSRB = 17,
   OP_STEM_BWD = 101, OP_PW_BWD = 102, OP_DW_BWD = 103, OP_KXK_BWD = 104, OP_BN_BWD = 105, OP_EW_BWD = 106,
   OP_MAXPOOL_BWD = 107, OP_AVGPOOL_BWD = 108, OP_GATE_REDUCE = 109, OP_CA_MLP_BWD = 110, OP_ATT_MLP_BWD = 111, OP_SE_MLP_BWD = 112,
   OP_SHUFFLE_BWD = 113,
@@ -347,6 +347,32 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
         lhn_view y = mkview(P, ws, o.out_buf, o.out_coff, o.out_C);
         rc = lhn_conv_dw3_pw_fwd(&x, prm<const float>(params, o.p[0]), o.i[0], reinterpret_cast<const float*>(at(ws, P->bufs[o.in_buf[1]].table_off)),
                                  prm<const float>(params, o.p[1]), prm<const float>(params, o.p[2]), &y, stream);
+        break;
+      }
+      case OP_MSRB: {  // one MSRB round.  in[0], in[1]: the x views of the two halves; in[2] and i[1..3] (buffer, first channel, channels):
+        // their extra sources when i[6] > 1, coefficients f[4..5] as OP_DW; out: the whole y view; p: the two weights; ws[0], ws[1]:
+        // pooled / scratch or -1; i[0] = OH.  Inference plans only.
+        if (training) {
+          lhn_set_error("lhn_plan_run: a fused MSRB round has no batch statistics (inference plans only)");
+          rc = 1;
+          break;
+        }
+        const lhn_view x[2] = {mkview(P, ws, o.in_buf[0], o.in_coff[0], o.in_C[0]), mkview(P, ws, o.in_buf[1], o.in_coff[1], o.in_C[1])};
+        lhn_view extra[2];
+        const bool two = o.i[6] > 1;
+        if (two) {
+          if (o.in_buf[2] < 0 || o.i[1] < 0 || o.i[1] >= (int)P->bufs.size()) {
+            lhn_set_error("lhn_plan_run: fused MSRB round: extra source out of range");
+            rc = 1;
+            break;
+          }
+          extra[0] = mkview(P, ws, o.in_buf[2], o.in_coff[2], o.in_C[2]);
+          extra[1] = mkview(P, ws, o.i[1], o.i[2], o.i[3]);
+        }
+        const float coef2[2] = {o.f[4], o.f[5]};
+        lhn_view y = mkview(P, ws, o.out_buf, o.out_coff, o.out_C, false);      // (its gate is written by the attention MLP behind this launch)
+        rc = lhn_msrb_round_fwd(x, two ? extra : nullptr, two ? coef2 : nullptr, prm<const float>(params, o.p[0]), prm<const float>(params, o.p[1]),
+                                &y, reinterpret_cast<float*>(at(ws, o.ws[0])), o.i[0], o.i[0], at(ws, o.ws[1]), stream);
         break;
       }
       case OP_FINALIZE: {

@@ -27,6 +27,8 @@ from ._lib import Buf, Op
 STEM, PW, DW, KXK, FINALIZE, EW, MAXPOOL, AVGPOOL, CA_MLP, TABLE_FILL, MEMSET, ATT_MLP, SE_MLP, SHUFFLE = range(1, 15)
 PWDW = 15              # inference plans only: 1x1 -> depthwise 3x3 in one launch (lhn_conv_pw_dw3_fwd), see PlanBuilder.fuse_pw_dw
 DWPW = 16              # inference plans only: depthwise 3x3 -> 1x1 in one launch (lhn_conv_dw3_pw_fwd), see PlanBuilder.fuse_dw_pw
+MSRB = 17              # inference plans only: both depthwise branches of an MSRB round (+ its attention's pooling) in one pass
+                       # (lhn_msrb_round_fwd), see PlanBuilder.fuse_msrb_round
 STEM_BWD, PW_BWD, DW_BWD, KXK_BWD, BN_BWD, EW_BWD, MAXPOOL_BWD, AVGPOOL_BWD, GATE_REDUCE, CA_MLP_BWD, ATT_MLP_BWD, SE_MLP_BWD, SHUFFLE_BWD = range(101, 114)
 SLOPE_SILU = 2.0       # LHN_SLOPE_SILU in include/lhn.h: the combine applies SiLU instead of a leaky ReLU
 SLOPE_RELU_SIGMOID = 3.0   # LHN_SLOPE_RELU_SIGMOID: sigmoid(relu(v)) (lite_hrnet.py: nn.ReLU followed by nn.Sigmoid)
@@ -85,6 +87,22 @@ def set_infer_fuse_dwpw(on):
 def infer_fuse_dwpw_enabled():
     """LHN_INFER_FUSE_DWPW=1 (default off): plans without a backward run DWConv's depthwise 3x3 -> 1x1 pairs as one launch."""
     return _INFER_FUSE_DWPW if _INFER_FUSE_DWPW is not None else os.environ.get("LHN_INFER_FUSE_DWPW", "0") == "1"
+
+
+_INFER_FUSE_MSRB = None     # set_infer_fuse_msrb(): in-process override of LHN_INFER_FUSE_MSRB
+
+
+def set_infer_fuse_msrb(on):
+    """Switch the MSRB-round inference fusion pass (PlanBuilder.fuse_msrb_round) on or off for plans built from now on; None =
+    follow the environment again.  Independent of the other two switches; Engine.plan_for keys its cache on all three."""
+    global _INFER_FUSE_MSRB
+    _INFER_FUSE_MSRB = None if on is None else bool(on)
+
+
+def infer_fuse_msrb_enabled():
+    """LHN_INFER_FUSE_MSRB=1 (default off): plans without a backward run each MSRB round -- its two dilated depthwise 3x3
+    convolutions and the pooling of its attention -- as one pass over the feature map."""
+    return _INFER_FUSE_MSRB if _INFER_FUSE_MSRB is not None else os.environ.get("LHN_INFER_FUSE_MSRB", "0") == "1"
 
 
 def _refs_in(v):
@@ -197,7 +215,8 @@ class _BwdFusions:
 class PlanBuilder:
     _no_grad_buf = -1   # the image never needs a gradient
 
-    def __init__(self, N, state_index, image_hw=None, with_backward=True, p_drop=0.0, infer_fuse=None, infer_fuse_dwpw=None):
+    def __init__(self, N, state_index, image_hw=None, with_backward=True, p_drop=0.0, infer_fuse=None, infer_fuse_dwpw=None,
+                 infer_fuse_msrb=None):
         self.N = N
         # inference fusion (fuse_pw_dw): None = the process-wide switch.  The fused launch has no batch statistics, so the
         # caller passes False for a plan that will run train-mode BatchNorm under no_grad (Engine.plan_for).
@@ -205,6 +224,8 @@ class PlanBuilder:
         self.n_fused = 0
         self.infer_fuse_dwpw = infer_fuse_dwpw_enabled() if infer_fuse_dwpw is None else bool(infer_fuse_dwpw)   # fuse_dw_pw, likewise
         self.n_fused_dwpw = 0
+        self.infer_fuse_msrb = infer_fuse_msrb_enabled() if infer_fuse_msrb is None else bool(infer_fuse_msrb)   # fuse_msrb_round, likewise
+        self.n_fused_msrb = 0
         self.state_index = state_index      # id(tensor) -> index in the params array
         self.bufs = []
         self.recs = []                      # forward records (python dicts)
@@ -832,9 +853,89 @@ class PlanBuilder:
         self.n_fused_dwpw += len(pairs)
         return len(pairs)
 
+    # Channels per half lhn_msrb_round_fwd is built for (csrc/k_msrb.hip: msrb_half_ok); any map size.
+    FUSE_MSRB_HALF = (32, 64, 128)
+
+    def _msrb_branch(self, q, dil):
+        """True when the record q can be one branch of a fused MSRB round: a 3x3 depthwise convolution, stride 1, dilation ==
+        padding == dil, of at most two summed sources, over a channel count the entry point accepts."""
+        if q["op"] != DW or (q["k"], q["stride"], q["pad"], q["dil"]) != (3, 1, dil, dil) or q["conv"].weight is None or \
+                q.get("bn_repeat", 1) != 1 or self._xs(q)[1] > 2:
+            return False
+        x, y = q["x"], q["out"]
+        if x.buf < 0 or y.buf < 0 or x.C != y.C or y.C not in self.FUSE_MSRB_HALF:
+            return False
+        return not (q["bn"] is not None and getattr(q["conv"], "bias", None) is not None)
+
+    def fuse_msrb_round(self):
+        """Inference plans with the switch on (infer_fuse_msrb): one round of an MSRB (litehourglass.py:43-50) -- the depthwise 3x3
+        at dilation 1 into the lower half of a buffer, the one at dilation 2 into its upper half and, when a ChannelAttension /
+        SEBlock gates that buffer, the average pool its MLP reads -- becomes ONE record (lhn_msrb_round_fwd).  The pooling needs
+        the consumed value of what the launch has just computed, so the pending tables of both halves are emitted ahead of it by
+        what fills them in the unfused plan (eval: FINALIZE from the running statistics; deployed: TABLE_FILL with the bias), under
+        LHN_RUN_TABLES_CURRENT like every other table launch.  The launch stands where the second convolution stood.  Plans with a
+        backward are never rewritten."""
+        if self.with_backward or not self.infer_fuse_msrb:
+            return 0
+        uses = {}
+        for r in self.recs:
+            for key, v in r.items():
+                for t in _refs_in(v):
+                    uses.setdefault(t.buf, []).append((r, key))
+        order = {id(r): j for j, r in enumerate(self.recs)}
+        at, drop = {}, set()
+        for b, rec in enumerate(self.bufs):
+            if rec.lazy is not None or rec.fused or any(v is not None and v.buf == b for v in (self.in_ref, self.out_ref)):
+                continue
+            wr = [u for u, key in uses.get(b, ()) if key == "out"]
+            dws = [u for u in wr if u["op"] == DW]
+            fills = [u for u in wr if u["op"] == TABLE_FILL]
+            if len(dws) != 2 or len(dws) + len(fills) != len(wr):
+                continue
+            q1, q2 = dws if dws[0]["dil"] == 1 else dws[::-1]
+            h = q1["out"].C
+            if not (self._msrb_branch(q1, 1) and self._msrb_branch(q2, 2)) or q2["out"].C != h or rec.C != 2 * h or \
+                    (q1["out"].coff, q2["out"].coff) != (0, h):
+                continue
+            (v1, n1, c1), (v2, n2, c2) = self._xs(q1), self._xs(q2)
+            if n1 != n2 or c1 != c2 or any(v.buf == b or v.buf < 0 for v in v1 + v2):
+                continue
+            lo, hi = sorted((order[id(q1)], order[id(q2)]))
+            if any(not (u["op"] == TABLE_FILL and u["out"].buf == b) for u in self.recs[lo + 1:hi]):
+                continue
+            gates = [u for u, key in uses.get(b, ()) if key == "y" and u["op"] in (CA_MLP, SE_MLP, ATT_MLP)]
+            att = gates[0] if len(gates) == 1 and gates[0]["op"] in (CA_MLP, SE_MLP) and not gates[0].get("copy") and \
+                not gates[0].get("bnslices") and order[id(gates[0])] > hi else None
+            out = TRef(b, 0, 2 * h, rec.H, rec.W)
+            fused = dict(op=MSRB, x0=v1[0], x1=v2[0], e0=v1[1] if n1 > 1 else None, e1=v2[1] if n1 > 1 else None, coefs=(c1[0], c1[1]),
+                         out=out, conv=q1["conv"], conv2=q2["conv"], pooled=None, scratch=None, OH=0)
+            if att is not None:
+                nbytes = _lib.lib().lhn_msrb_round_scratch_bytes(self.N, rec.H, rec.W, 2 * h)
+                if nbytes <= 0:
+                    continue
+                att["pool_fused"] = True        # _fwd_ca / _fwd_se: no AVGPOOL launch, the fused record fills `pooled`
+                fused.update(pooled=att["pooled"], scratch=self._ws("misc", nbytes), OH=3 if att["op"] == CA_MLP else 1)
+            tables = []
+            for q in (q1, q2):
+                if q["bn"] is not None:
+                    tables.append(dict(op=FINALIZE, out=q["out"], bn=q["bn"], slope=q["slope"]))
+                elif q["conv"].bias is not None or q["slope"] != 1.0:
+                    tables.append(dict(op=TABLE_FILL, out=q["out"], bias=q["conv"].bias, slope=q["slope"]))
+            at[id(self.recs[hi])] = tables + [fused]
+            drop |= {id(q1), id(q2)} | {id(u) for u in fills}
+        if not at:
+            return 0
+        recs = []
+        for r in self.recs:
+            recs += at.get(id(r), [] if id(r) in drop else [r])
+        self.recs = recs
+        self.n_fused_msrb += len(at)
+        return len(at)
+
     # ------------------------------------------------------------------ finalize: the passes in the order they run
     def finalize(self):
         """Lower the records to what lhn_plan_create takes: (Buf array, forward Op array, backward Op array or None, n_fwd, n_bwd)."""
+        self.fuse_msrb_round()
         self.fuse_dw_pw()
         self.fuse_pw_dw()
         self._layout()
@@ -875,6 +976,7 @@ class PlanBuilder:
     # ------------------------------------------------------------------ forward lowering: one emitter per record family -> [Op]
     def _lower_forward(self):
         emit = {STEM: self._fwd_conv, PW: self._fwd_conv, DW: self._fwd_conv, KXK: self._fwd_conv, PWDW: self._fwd_pwdw, DWPW: self._fwd_dwpw,
+                MSRB: self._fwd_msrb,
                 FINALIZE: self._fwd_table, TABLE_FILL: self._fwd_table, EW: self._fwd_ew, SHUFFLE: self._fwd_pool,
                 MAXPOOL: self._fwd_pool, AVGPOOL: self._fwd_pool, CA_MLP: self._fwd_ca, SE_MLP: self._fwd_se, ATT_MLP: self._fwd_att}
         fwd = [self._mk(MEMSET, ws=(self.arena_base["zf"], self.ar["zf"].size))] if self.ar["zf"].size else []
@@ -916,8 +1018,17 @@ class PlanBuilder:
         return [self._mk(DWPW, ins=(r["x"], r["mid"]), out=r["out"], i=(r["dil"],),
                          p=(self._p(r["conv"].weight), self._p(r["conv2"].weight), self._p(r["bias"])))]
 
+    def _fwd_msrb(self, r):
+        """in: the x views of the two halves and the first half's extra source (the second's rides in i[1..3]: an op has three
+        input slots); i[0] = OH (0: no pooling), i[6] = sources per half, f[4..5] = their coefficients as on a DW op."""
+        two = r["e0"] is not None
+        e1 = (r["e1"].buf, r["e1"].coff, r["e1"].C) if two else (-1, 0, 0)
+        return [self._mk(MSRB, ins=(r["x0"], r["x1"]) + ((r["e0"],) if two else ()), out=r["out"],
+                         p=(self._p(r["conv"].weight), self._p(r["conv2"].weight)), ws=(self._abs(r["pooled"]), self._abs(r["scratch"])),
+                         i=(r["OH"],) + e1 + (0, 0, 2 if two else 1), f=(0.0, 0.0, 0.0, 0.0) + tuple(r["coefs"]))]
+
     def _fwd_table(self, r):
-        """FINALIZE: eval-mode table of a convolution that runs inside a PWDW / DWPW launch (no statistics to fold); TABLE_FILL: the
+        """FINALIZE: eval-mode table of a convolution that runs inside a PWDW / DWPW / MSRB launch (no statistics to fold); TABLE_FILL: the
         pending bias / activation of a BatchNorm-free convolution."""
         if r["op"] == FINALIZE:
             bn = r["bn"]
@@ -954,9 +1065,9 @@ class PlanBuilder:
         if hasattr(ca, "rbr_reparam"):
             if self.with_backward:
                 raise _lib.LhnError("deployed ChannelAttension is inference-only")
-            return [mk(AVGPOOL, ins=(y,), ws=(self._abs(r["pooled"]),), i=(3, 3, 1)),
-                    mk(CA_MLP, out=y, p=(self._p(ca.rbr_reparam.weight), -1, self._p(ca.rbr_reparam.bias), -1, -1, -1) + mlp,
-                       ws=(self._abs(r["pooled"]), self._abs(r["save"]), self._abs(r["mask"])), f=(1e-5, 0.1))]
+            pool = [] if r.get("pool_fused") else [mk(AVGPOOL, ins=(y,), ws=(self._abs(r["pooled"]),), i=(3, 3, 1))]
+            return pool + [mk(CA_MLP, out=y, p=(self._p(ca.rbr_reparam.weight), -1, self._p(ca.rbr_reparam.bias), -1, -1, -1) + mlp,
+                              ws=(self._abs(r["pooled"]), self._abs(r["save"]), self._abs(r["mask"])), f=(1e-5, 0.1))]
         sl = r.get("bnslices")
         pins = (y, r["copy"]["srcs"][0]) if r.get("copy") else (y,)       # second input: pass-through half copied by this launch
         if sl:      # pooling pass that also leaves M0, M1 per (n, bin, c) for the backward (lhn_avgpool_fwd4)
@@ -965,15 +1076,15 @@ class PlanBuilder:
         else:
             pool = mk(AVGPOOL, ins=pins, ws=(self._abs(r["pooled"]),), i=(3, 3, 1))
         bn = ca.conv3x3.bn
-        return [pool, mk(CA_MLP, out=y, p=(self._p(ca.conv3x3.conv.weight),) + self._p_bn(bn) + mlp,
+        return ([] if r.get("pool_fused") else [pool]) + [mk(CA_MLP, out=y, p=(self._p(ca.conv3x3.conv.weight),) + self._p_bn(bn) + mlp,
                          ws=(self._abs(r["pooled"]), self._abs(r["save"]), self._abs(r["mask"]), self._abs(r["gsum"])),
                          f=(bn.eps, bn.momentum))]
 
     def _fwd_se(self, r):
         y, dn, up = r["y"], r["down"], r["up"]
-        return [self._mk(AVGPOOL, ins=(y,), ws=(self._abs(r["pooled"]),), i=(1, 1, 1)),
-                self._mk(SE_MLP, out=y, p=(self._p(dn.weight), self._p(dn.bias), self._p(up.weight), self._p(up.bias)),
-                         ws=(self._abs(r["pooled"]), self._abs(r["save"])), i=(r["J"], r["mode"]))]
+        pool = [] if r.get("pool_fused") else [self._mk(AVGPOOL, ins=(y,), ws=(self._abs(r["pooled"]),), i=(1, 1, 1))]
+        return pool + [self._mk(SE_MLP, out=y, p=(self._p(dn.weight), self._p(dn.bias), self._p(up.weight), self._p(up.bias)),
+                                ws=(self._abs(r["pooled"]), self._abs(r["save"])), i=(r["J"], r["mode"]))]
 
     def _fwd_att(self, r):
         y, att = r["y"], r["att"]
