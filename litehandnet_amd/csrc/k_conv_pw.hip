@@ -1010,6 +1010,264 @@ static int launch_pw_bwd(const lhn_view* x, const float* w, const lhn_view* y, c
   return launch_pw_bwd_t<CIN, NTO, false>(x, w, y, gy, dx, dx_acc, dw, dbias, stride, dy_nchw, cout, nrep, rep_stride, geo, s, bs);
 }
 
+// =====================================================================================================
+// Backward of the WIDE 1x1 (Cin * Cout >= 64 * 128, both <= 128; stride 1, NHWC, full-width weight, no reader-side sums) with the
+// weights AND the weight gradient in registers: what k_pw_fwd_wr did for the forward.  k_pw_bwd<128,4> keeps W in LDS (135 KB with
+// the two pixel tiles: one workgroup per CU, its phases add up), which is why these shapes went to lhn_pw_bwd_split: three launches
+// and seven tensor passes (dz, y -> dy | dy -> dx | dy, x -> dW).  Here one launch reads dz, y, x and writes dx and dy:
+//   dX: a wave owns ONE 32-wide input-channel tile for the whole launch; its slice of W is the MFMA B operand (K = COUT: COUT / 2
+//       VGPRs per lane, loaded once from global memory).  CIN = 128: four tiles, a wave does every 32-pixel sub-tile of the tile;
+//       CIN = 64: two tiles, waves pair up over the halves as in k_pw_bwd.
+//   dW: the NTO * NTI 32x32 tiles are split four ways (tile row wave / NTI + (4 / NTI) t, column wave % NTI) and stay in accumulators
+//       for the whole launch; one atomic flush per workgroup into its gradient replica.  No per-tile predicate in the loop.
+//   LDS holds only the staged pixel tiles dYs / Xs and the per-channel tables (the pending transforms of x and y and the
+//       BatchNorm-backward coefficients: 36 registers per thread in k_pw_bwd, re-read here from LDS at each commit), 38..55 KB:
+//       two workgroups per CU (the register file decides, not LDS), so one's loads, commit and stores run under the other's MFMAs.
+// dy is ALSO stored over dz, as k_dy_inplace does on the split path: the callers of lhn_conv_pw_bwd3 see the same buffers whichever
+// path ran (tests/test_pw_gpu.py pins dz = dy for these shapes).  PX: pixels per tile (64, or 32 where 64 does not fit the registers).
+// PF: what rides in the register prefetch one tile ahead, 0 = x, 1 = x and y, 2 = x, y and dz; the rest is fetched inside commit()
+// four rows at a time, so that its registers are not live across the MFMA phase.
+template <int CIN, int COUT, int PX, int PF>
+__global__ void __launch_bounds__(256, 2) k_pw_bwd_wr(lhn_view x, const float* __restrict__ w, lhn_view y, lhn_gradview gy,
+                                                      float* __restrict__ dx, int dx_acc, float* __restrict__ dw, float* __restrict__ dbias,
+                                                      int M, int ntiles, int nrep, int64_t rep_stride) {
+  constexpr int NTI = CIN / 32, NTO = COUT / 32, LDY = COUT + 4, LDX = CIN + 4;
+  constexpr int NDW = NTO * NTI / 4;            // dW tiles per wave
+  constexpr int NDX = (NTI == 4 && PX == 64) ? 2 : 1;      // 32-pixel sub-tiles of dX per wave
+  static_assert((NTI == 2 || NTI == 4) && (NTO == 2 || NTO == 4) && NDW >= 2 && (PX == 64 || (PX == 32 && NTI == 4)), "wide instances only");
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* dYs = smem;                  // [PX][LDY]
+  float* Xs = dYs + PX * LDY;         // [PX][LDX]
+  float* xt = Xs + PX * LDX;          // [3][CIN]   scale | shift | slope of x
+  float* yt = xt + 3 * CIN;           // [3][COUT]  the same of y
+  float* cf = yt + 3 * COUT;          // [3][COUT]  A | B | C
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, lh = lane >> 5;
+  const int HoWo = y.H * y.W;
+  float* dzw = const_cast<float*>(gy.dz);
+
+  constexpr int XC4 = CIN / 4, XRP = 256 / XC4, XPF = PX / XRP;
+  constexpr int YC4 = COUT / 4, YRP = 256 / YC4, YPF = PX / YRP;
+  constexpr int ZCH = YPF < 4 ? YPF : 4;
+  const int xc4 = tid % XC4, xr0 = tid / XC4, xabs = x.coff + 4 * xc4;
+  const int yc4 = tid % YC4, yr0 = tid / YC4, yabs = y.coff + 4 * yc4;
+
+  f4 xraw[XPF], yraw[YPF], ydz[YPF];
+  auto issue = [&](int tile) __attribute__((always_inline)) {
+#pragma unroll
+    for (int p = 0; p < XPF; ++p) {
+      const int m = min(tile * PX + xr0 + p * XRP, M - 1);      // clamped (branch-free); commit() zeroes rows >= M
+      xraw[p] = *reinterpret_cast<const f4*>(x.data + (int64_t)m * x.cstride + xabs);
+    }
+#pragma unroll
+    for (int p = 0; p < YPF; ++p) {
+      const int m = min(tile * PX + yr0 + p * YRP, M - 1);
+      if (PF >= 1) yraw[p] = *reinterpret_cast<const f4*>(y.data + (int64_t)m * y.cstride + yabs);
+      if (PF >= 2) ydz[p] = *reinterpret_cast<const f4*>(gy.dz + (int64_t)m * y.cstride + yabs);
+    }
+  };
+  f4 bsum = (f4){0.f, 0.f, 0.f, 0.f};
+  auto commit = [&](int tile) __attribute__((always_inline)) {
+    Xf4 xxf;
+    xxf.sc = *reinterpret_cast<const f4*>(xt + 4 * xc4);
+    xxf.sh = *reinterpret_cast<const f4*>(xt + CIN + 4 * xc4);
+    xxf.sl = *reinterpret_cast<const f4*>(xt + 2 * CIN + 4 * xc4);
+#pragma unroll
+    for (int p = 0; p < XPF; ++p) {
+      const int row = xr0 + p * XRP, m = tile * PX + row;
+      f4 v = (f4){0.f, 0.f, 0.f, 0.f};
+      if (m < M) {
+        v = lhn_apply_xf(xraw[p], xxf);
+        if (x.gate) v *= *reinterpret_cast<const f4*>(x.gate + (int64_t)(m / HoWo) * x.cstride + xabs);
+      }
+      *reinterpret_cast<f4*>(Xs + row * LDX + 4 * xc4) = v;
+    }
+    Xf4 yxf;
+    Gr4 ygr;
+    yxf.sc = *reinterpret_cast<const f4*>(yt + 4 * yc4);
+    yxf.sh = *reinterpret_cast<const f4*>(yt + COUT + 4 * yc4);
+    yxf.sl = *reinterpret_cast<const f4*>(yt + 2 * COUT + 4 * yc4);
+    ygr.A = *reinterpret_cast<const f4*>(cf + 4 * yc4);
+    ygr.B = *reinterpret_cast<const f4*>(cf + COUT + 4 * yc4);
+    ygr.Cc = *reinterpret_cast<const f4*>(cf + 2 * COUT + 4 * yc4);
+#pragma unroll
+    for (int p = 0; p < YPF; ++p) {
+      if (PF < 2 && p % ZCH == 0) {      // what was not prefetched (its registers would be live across the MFMA phase): the next ZCH rows
+#pragma unroll
+        for (int q = p; q < p + ZCH; ++q) {
+          const int mq = min(tile * PX + yr0 + q * YRP, M - 1);
+          if (PF < 1) yraw[q] = *reinterpret_cast<const f4*>(y.data + (int64_t)mq * y.cstride + yabs);
+          ydz[q] = *reinterpret_cast<const f4*>(gy.dz + (int64_t)mq * y.cstride + yabs);
+        }
+      }
+      const int row = yr0 + p * YRP, m = tile * PX + row;
+      f4 v = (f4){0.f, 0.f, 0.f, 0.f};
+      if (m < M) {
+        int n = 0, h = 0, ww = 0;
+        if (y.gate || gy.dpool) {          // (pixel coordinates only where lhn_grad_du reads them)
+          n = m / HoWo;
+          const int r = m - n * HoWo;
+          h = r / y.W;
+          ww = r - h * y.W;
+        }
+        const f4 du = lhn_grad_du(y, gy, yxf, yraw[p], ydz[p], n, h, ww, yabs);
+        v = ygr.A * du + ygr.B * yraw[p] + ygr.Cc;
+        bsum += v;
+        *reinterpret_cast<f4*>(dzw + (int64_t)m * y.cstride + yabs) = v;
+      }
+      *reinterpret_cast<f4*>(dYs + row * LDY + 4 * yc4) = v;
+    }
+  };
+
+  int tile = blockIdx.x;
+  if (tile < ntiles) issue(tile);     // the first tile's loads are in flight while the tables and W are fetched
+  for (int i = tid; i < CIN; i += 256) {
+    xt[i] = x.table ? x.table[x.coff + i] : 1.f;
+    xt[CIN + i] = x.table ? x.table[x.cstride + x.coff + i] : 0.f;
+    xt[2 * CIN + i] = x.table ? x.table[2 * x.cstride + x.coff + i] : 1.f;
+  }
+  for (int i = tid; i < COUT; i += 256) {
+    yt[i] = y.table ? y.table[y.coff + i] : 1.f;
+    yt[COUT + i] = y.table ? y.table[y.cstride + y.coff + i] : 0.f;
+    yt[2 * COUT + i] = y.table ? y.table[2 * y.cstride + y.coff + i] : 1.f;
+    cf[i] = gy.coef ? gy.coef[y.coff + i] : 1.f;
+    cf[COUT + i] = gy.coef ? gy.coef[y.cstride + y.coff + i] : 0.f;
+    cf[2 * COUT + i] = gy.coef ? gy.coef[2 * y.cstride + y.coff + i] : 0.f;
+  }
+  // ---- B fragments of the data gradient: wreg[kc*4 + j] = W[8*kc + 4*lh + j][32*jt + l31]  (K permutation of the dYs reads below)
+  const int jt = NTI == 4 ? wave : wave >> 1;
+  float wreg[COUT / 2];
+#pragma unroll
+  for (int k = 0; k < COUT / 2; ++k) wreg[k] = dx ? w[(int64_t)((k >> 2) * 8 + 4 * lh + (k & 3)) * CIN + 32 * jt + l31] : 0.f;
+  f16v accw[NDW];
+#pragma unroll
+  for (int t = 0; t < NDW; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) accw[t][r] = 0.f;
+  __syncthreads();
+
+  for (; tile < ntiles; tile += gridDim.x) {
+    commit(tile);
+    __syncthreads();
+    if (tile + (int)gridDim.x < ntiles) issue(tile + gridDim.x);
+    // ---- dW += dY^T X   (K = PX pixels)
+    {
+      const float* ap = dYs + lh * LDY + l31 + 32 * (wave / NTI);
+      const float* bp = Xs + lh * LDX + l31 + 32 * (wave % NTI);
+#pragma unroll 4
+      for (int ks = 0; ks < PX / 2; ++ks) {
+        const float b = bp[(2 * ks) * LDX];
+        float a[NDW];
+#pragma unroll
+        for (int t = 0; t < NDW; ++t) a[t] = ap[(2 * ks) * LDY + 32 * (4 / NTI) * t];
+#pragma unroll
+        for (int t = 0; t < NDW; ++t) accw[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], b, accw[t], 0, 0, 0);
+      }
+    }
+    // ---- dX = dY W   (K = COUT)
+    if (dx) {
+      f16v accx[NDX];
+#pragma unroll
+      for (int hh = 0; hh < NDX; ++hh)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) accx[hh][r] = 0.f;
+      const int mt0 = NTI == 4 ? 0 : (wave & 1);      // (PX = 32: one sub-tile, every wave its own channel tile)
+      const float* arow = dYs + (mt0 * 32 + l31) * LDY + 4 * lh;
+#pragma unroll
+      for (int kc = 0; kc < COUT / 8; ++kc) {
+#pragma unroll
+        for (int hh = 0; hh < NDX; ++hh) {
+          const f4 a = *reinterpret_cast<const f4*>(arow + hh * 32 * LDY + kc * 8);
+          accx[hh] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, wreg[kc * 4 + 0], accx[hh], 0, 0, 0);
+          accx[hh] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, wreg[kc * 4 + 1], accx[hh], 0, 0, 0);
+          accx[hh] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, wreg[kc * 4 + 2], accx[hh], 0, 0, 0);
+          accx[hh] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, wreg[kc * 4 + 3], accx[hh], 0, 0, 0);
+        }
+      }
+      // C/D layout: col = lane&31 (input channel), row = (r&3) + 8*(r>>2) + 4*(lane>>5) (pixel)
+      const int cs = x.cstride;
+#pragma unroll
+      for (int hh = 0; hh < NDX; ++hh) {
+        const int mbase = tile * PX + (mt0 + hh) * 32 + 4 * lh;
+        float* o = dx + (int64_t)mbase * cs + x.coff + 32 * jt + l31;
+        if (tile * PX + PX <= M) {        // whole tile inside the tensor: stores off one base pointer, no row predicate
+          if (dx_acc) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[((r & 3) + 8 * (r >> 2)) * cs] += accx[hh][r];
+          } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[((r & 3) + 8 * (r >> 2)) * cs] = accx[hh][r];
+          }
+        } else {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int ro = (r & 3) + 8 * (r >> 2);
+            if (mbase + ro < M) o[ro * cs] = dx_acc ? o[ro * cs] + accx[hh][r] : accx[hh][r];
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+
+  // ---- flush dW (C/D layout: row = co within the tile, col = lane&31 = ci within the tile): one add per element and workgroup
+  dw += (size_t)(blockIdx.x % nrep) * rep_stride;
+#pragma unroll
+  for (int t = 0; t < NDW; ++t) {
+    const int it = wave / NTI + (4 / NTI) * t, jw = wave % NTI;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int co = 32 * it + (r & 3) + 8 * (r >> 2) + 4 * lh;
+      atomicAdd(dw + (int64_t)co * CIN + 32 * jw + l31, accw[t][r]);
+    }
+  }
+  if (dbias) {      // column sums of dy in a fixed order, one add per channel into the workgroup's replica (as k_pw_bwd; dYs is free)
+    f4* bred = reinterpret_cast<f4*>(dYs);            // [YRP][YC4] float4
+    bred[yr0 * YC4 + yc4] = bsum;
+    __syncthreads();
+    if (tid < YC4) {
+      f4 t = (f4){0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < YRP; ++j) t += bred[j * YC4 + tid];
+      float* db = dbias + (size_t)(blockIdx.x % nrep) * rep_stride + 4 * tid;
+      atomicAdd(db + 0, t.x);
+      atomicAdd(db + 1, t.y);
+      atomicAdd(db + 2, t.z);
+      atomicAdd(db + 3, t.w);
+    }
+  }
+}
+
+// Instances (compiler's resource report, two workgroups per CU = 256 registers per lane):
+//   128 -> 128: PX = 32, x and y prefetched.  With 64-pixel tiles the budget of 64 (W) + 64 (dW) + 32 (dX) + staging does not close:
+//               61..133 registers spill whichever tensors ride in the prefetch (the dX phase with two sub-tiles is the peak).
+//   64 -> 128:  PX = 64, x and y prefetched (dz too: 1 spill).      128 -> 64: PX = 64, x, y and dz prefetched.
+template <int CIN, int COUT, int PX, int PF>
+static int launch_pw_bwd_wr(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc, float* dw,
+                            float* dbias, int nrep, int64_t rep_stride, hipStream_t s) {
+  const int M = y->N * y->H * y->W, ntiles = (M + PX - 1) / PX;
+  const size_t lds = (size_t)(PX * (COUT + 4) + PX * (CIN + 4) + 3 * CIN + 6 * COUT) * sizeof(float);
+  static LhnKernelCfg cfg;
+  int per_cu = 1;
+  if (!lhn_kernel_cfg(cfg, &k_pw_bwd_wr<CIN, COUT, PX, PF>, lds, 2, &per_cu)) {
+    lhn_set_error("lhn_conv_pw_bwd: cannot reserve %zu B of LDS", lds);
+    return 2;
+  }
+  int grid = lhn_num_cus() * per_cu;
+  if (grid > ntiles) grid = ntiles;
+  hipLaunchKernelGGL((k_pw_bwd_wr<CIN, COUT, PX, PF>), dim3(grid), dim3(256), lds, s, *x, w, *y, *gy, dx, dx_acc, dw, dbias, M, ntiles,
+                     nrep, rep_stride);
+  return 0;
+}
+
+// LHN_PW_BWD_SPLIT=1: the wide shapes take lhn_pw_bwd_split as before k_pw_bwd_wr existed (A/B comparisons)
+static bool pw_bwd_split_forced() {
+  static int on = -1;
+  if (on < 0) {
+    const char* e = getenv("LHN_PW_BWD_SPLIT");
+    on = (e && e[0] == '1') ? 1 : 0;
+  }
+  return on == 1;
+}
+
 int lhn_pw_bwd_split(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate,
                      float* dw, float* dbias, int nrep, int64_t rep_stride, hipStream_t s);
 
@@ -1040,6 +1298,19 @@ extern "C" int lhn_conv_pw_bwd3(const lhn_view* x, const float* w, const lhn_vie
                 wrows, wcols, Cin, Cout);
   const int64_t bstride = (opts && opts->nchw_batch_stride > 0) ? opts->nchw_batch_stride : (int64_t)Cout * HoWo;
   hipStream_t s = (hipStream_t)stream;
+  // wide shapes with both sides <= 128: one register-W launch (decided here, before any launch; LHN_PW_BWD_SPLIT=1 and
+  // LHN_PW_LDSW=1, which means "no register-W kernel", keep the split path)
+  if (!bs.sums && stride == 1 && !dy_nchw && wcols == Cin && wrows == Cout && !pw_bwd_split_forced() && !pw_wr_off()) {
+    int rc = -1;
+    if (Cin == 128 && Cout == 128) rc = launch_pw_bwd_wr<128, 128, 32, 1>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s);
+    else if (Cin == 64 && Cout == 128) rc = launch_pw_bwd_wr<64, 128, 64, 1>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s);
+    else if (Cin == 128 && Cout == 64) rc = launch_pw_bwd_wr<128, 64, 64, 2>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s);
+    if (rc == 0) {
+      LHN_CHECK_LAUNCH("lhn_conv_pw_bwd");
+      return 0;
+    }
+    if (rc > 0) return rc;
+  }
   if (!bs.sums && stride == 1 && !dy_nchw && Cin * Cout >= 64 * 128 && Cout % 32 == 0 && Cin % 32 == 0 && Cout <= 256 && wcols == Cin && wrows == Cout) {
     const int rc = lhn_pw_bwd_split(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s);
     if (rc == 0) {
