@@ -393,7 +393,8 @@ int lhn_att_mlp_bwd(const float* pooled, const float* gamma, const float* beta, 
 int lhn_se_mlp_fwd(const float* pooled, const float* w1 /*[J,C]*/, const float* b1, const float* w2 /*[C,J]*/,
                    const float* b2, float* gate, int gate_stride, int gate_coff, float* save, int N, int C, int J,
                    void* stream);
-/* mode 1: SpatialWeighting of lite_hrnet.py:55-74 -- sigmoid(relu(.)) after both 1x1 convolutions (mode 0 = SEBlock) */
+/* mode 1: SpatialWeighting of lite_hrnet.py:55-74 -- sigmoid(relu(.)) after both 1x1 convolutions (mode 0 = SEBlock).
+ * b1 and b2 (and db1, db2) may both be NULL: the bias-free nn.Linear pair of hourglass_ablation.py:201-209 */
 int lhn_se_mlp_fwd2(const float* pooled, const float* w1, const float* b1, const float* w2, const float* b2, float* gate,
                     int gate_stride, int gate_coff, float* save, int N, int C, int J, int mode, void* stream);
 int lhn_se_mlp_bwd2(const float* pooled, const float* w1, const float* w2, const float* save, const float* dgate,
@@ -515,6 +516,23 @@ int lhn_ca_mlp_bwd(const float* pooled, const float* w3, const float* gamma, con
                    int cstride, int coff, int H, int W, float* dw3, float* dgamma, float* dbeta, float* dw1,
                    float* db1, float* dw2, float* db2, int N, int C, int stage, double* gsum, double count_scale,
                    float pgrad_scale, void* stream);
+
+/* CBAM (attention.py:269-294) between its `pre` convolutions and its final ReLU.  p = pre's output (its VALUE: raw + table), r =
+ * residual_conv(x), out = relu(a * g * p + r) stored plain; g = sigmoid(W2 relu(W1 mean p) + W2 relu(W1 max p)) per (n, c), a =
+ * sigmoid(conv7x7([mean_c, max_c](g p))) per pixel.  w1 [C/16, C], w2 [C, C/16], w7 [1, 2, 7, 7], no biases.  C % 16 == 0, C <= 256,
+ * any N, H, W; anything else is refused before the first launch.  No float atomics: bitwise repeatable in every mode.
+ * `save` (forward writes, backward reads) and `scratch` (backward only) are caller-owned float arrays; lhn_cbam_layout gives the
+ * offsets in floats:  save_off[10] = avg[N][C], mx[N][C], argmax pixel (int32)[N][C], hidden rows after ReLU [N][2][C/16], g[N][C],
+ * s[N][H][W][2], argmax channel (int32)[N][H][W], a[N][H][W], pooling partials, total;  scratch_off[8] = dq, dW7 partials, dg partials,
+ * davg, dmx, dW1 partials, dW2 partials, total.
+ * Backward: dout has out's geometry; dr is STORED with r's geometry; dp (p's geometry) receives d(loss)/d(value of p), STORED; dw1,
+ * dw2, dw7 are ADDED to (one fold in fixed order each). */
+int lhn_cbam_layout(int N, int H, int W, int C, int64_t* save_off /*[10]*/, int64_t* scratch_off /*[8]*/);
+int lhn_cbam_fwd(const lhn_view* p, const lhn_view* r, const float* w1, const float* w2, const float* w7, const lhn_view* out,
+                 float* save, void* stream);
+int lhn_cbam_bwd(const lhn_view* p, const lhn_view* r, const float* w1, const float* w2, const float* w7, const lhn_view* out,
+                 const float* dout, float* dp, float* dr, float* dw1, float* dw2, float* dw7, const float* save, float* scratch,
+                 void* stream);
 
 /* torch.optim.Adam (no amsgrad) over one flat fp32 parameter buffer -- the optimizer of dist_train.py:64-69 for the flat parameter
  * of litehandnet_amd.train.FlatParams: exp_avg / exp_avg_sq are the optimizer state of that one tensor, step = the 1-based count of

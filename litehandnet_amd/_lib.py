@@ -52,6 +52,7 @@ SYMBOLS = [
     "lhn_bn_bwd_reduce", "lhn_bn_bwd_finalize", "lhn_conv_pw_bwd", "lhn_conv_dw_bwd", "lhn_conv_dw_bwd2", "lhn_conv_dw_bwd3", "lhn_conv_stem_bwd",
     "lhn_conv_kxk_bwd", "lhn_ew_bwd", "lhn_ew_bwd2", "lhn_maxpool2_bwd", "lhn_maxpool2_bwd2", "lhn_maxpool2_bwd3", "lhn_ew_bwd3", "lhn_ew_bwd_multi", "lhn_avgpool_bwd3", "lhn_conv_pw_bwd3", "lhn_avgpool_bwd", "lhn_gate_bwd_reduce", "lhn_gate_bwd_reduce2", "lhn_gate_bwd_reduce3", "lhn_adam_step", "lhn_avgpool_fwd3", "lhn_avgpool_fwd4", "lhn_ca_mlp_bwd2",
     "lhn_ca_mlp_bwd", "lhn_reduce_replicas", "lhn_fold_stat_replicas", "lhn_plan_create", "lhn_plan_destroy", "lhn_plan_run", "lhn_plan_run_range",
+    "lhn_cbam_layout", "lhn_cbam_fwd", "lhn_cbam_bwd",
 ]
 
 
@@ -76,7 +77,22 @@ def lib():
         _lib.lhn_msrb_round_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                             C.c_void_p, C.c_void_p]
         _lib.lhn_msrb_round_fwd.restype = C.c_int
+        _lib.lhn_cbam_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.lhn_cbam_layout.restype = C.c_int
+        # (p, r, w1, w2, w7, out, save, stream)
+        _lib.lhn_cbam_fwd.argtypes = [C.c_void_p] * 8
+        _lib.lhn_cbam_fwd.restype = C.c_int
+        # (p, r, w1, w2, w7, out, dout, dp, dr, dw1, dw2, dw7, save, scratch, stream)
+        _lib.lhn_cbam_bwd.argtypes = [C.c_void_p] * 15
+        _lib.lhn_cbam_bwd.restype = C.c_int
     return _lib
+
+
+def cbam_layout(N, H, W, Cc):
+    """(save offsets [10], scratch offsets [8]) of lhn_cbam_fwd / lhn_cbam_bwd in floats (include/lhn.h: lhn_cbam_layout)."""
+    sv, sc = (C.c_int64 * 10)(), (C.c_int64 * 8)()
+    check(lib().lhn_cbam_layout(N, H, W, Cc, sv, sc), "lhn_cbam_layout")
+    return list(sv), list(sc)
 
 
 def check(status, what=""):

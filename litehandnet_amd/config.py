@@ -46,6 +46,10 @@ def litehandnet_cfg(variant="A", channels=128, num_joints=21, image_size=256, **
                      num_stack=2, num_level=4)
     elif variant == "L":            # Lite-HRNet, config/litehrnet/_2_rhd2d_256x256_dark_18.py:4-9 (depth 18; _1_*_30: depth 30)
         model = dict(name="litehrnet", depth=18, output_channel=num_joints)
+    elif variant == "X":            # hourglass_ablation, config/hourglass_ablation/freihand/_1 ... _7_*.py (224x224 there): pass
+        # msrb=, rca=, ca_type=, num_block= (four entries with msrb=False)
+        model = dict(name="hourglass_ablation", num_stage=4, num_block=[2, 2, 2], input_channel=channels,
+                     output_channel=num_joints, msrb=True, rca=False, ca_type="ca")
     else:
         raise ValueError(variant)
     model.update(model_kw)

@@ -278,7 +278,7 @@ __global__ void __launch_bounds__(256) k_se_fwd(const float* __restrict__ pooled
   for (int c = threadIdx.x; c < C; c += blockDim.x) sp[c] = pooled[(int64_t)n * C + c];
   __syncthreads();
   for (int j = threadIdx.x; j < J; j += blockDim.x) {
-    float v = b1[j];
+    float v = b1 ? b1[j] : 0.f;      // (NULL biases: nn.Linear(bias=False) pairs)
     for (int c = 0; c < C; ++c) v += w1[j * C + c] * sp[c];
     v = fmaxf(v, 0.f);
     if (mode == 1) v = 1.f / (1.f + expf(-v));
@@ -287,7 +287,7 @@ __global__ void __launch_bounds__(256) k_se_fwd(const float* __restrict__ pooled
   }
   __syncthreads();
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    float v = b2[c];
+    float v = b2 ? b2[c] : 0.f;
     for (int j = 0; j < J; ++j) v += w2[c * J + j] * sh[j];
     const float g = 1.f / (1.f + expf(-(mode == 1 ? fmaxf(v, 0.f) : v)));
     save[(int64_t)N * J + (int64_t)n * C + c] = g;
@@ -312,7 +312,7 @@ __global__ void __launch_bounds__(256) k_se_bwd(const float* __restrict__ pooled
     float dz = dgate[(int64_t)n * C + c] * g * (1.f - g);
     if (mode == 1 && !(g > 0.5f)) dz = 0.f;
     sdz[c] = dz;
-    atomicAdd(db2 + c, dz);
+    if (db2) atomicAdd(db2 + c, dz);
   }
   for (int j = threadIdx.x; j < J; j += blockDim.x) sh[j] = save[(int64_t)n * J + j];
   __syncthreads();
@@ -324,7 +324,7 @@ __global__ void __launch_bounds__(256) k_se_bwd(const float* __restrict__ pooled
     if (mode == 1) d = sh[j] > 0.5f ? d * sh[j] * (1.f - sh[j]) : 0.f;
     else d = sh[j] > 0.f ? d : 0.f;
     sdh[j] = d;
-    atomicAdd(db1 + j, d);
+    if (db1) atomicAdd(db1 + j, d);
   }
   __syncthreads();
   for (int i = threadIdx.x; i < J * C; i += blockDim.x) atomicAdd(dw1 + i, sdh[i / C] * sp[i % C]);
@@ -346,7 +346,7 @@ extern "C" int lhn_se_mlp_fwd(const float* pooled, const float* w1, const float*
 }
 extern "C" int lhn_se_mlp_fwd2(const float* pooled, const float* w1, const float* b1, const float* w2, const float* b2, float* gate,
                                int gate_stride, int gate_coff, float* save, int N, int C, int J, int mode, void* stream) {
-  LHN_CHECK_ARG(pooled && w1 && b1 && w2 && b2 && gate && save, "lhn_se_mlp_fwd: null pointer");
+  LHN_CHECK_ARG(pooled && w1 && w2 && gate && save && !b1 == !b2, "lhn_se_mlp_fwd: null pointer (b1, b2: both or neither)");
   LHN_CHECK_ARG(C > 0 && C <= 256 && J > 0 && J <= 64 && N > 0, "lhn_se_mlp_fwd: C=%d J=%d (C <= 256, J <= 64)", C, J);
   hipLaunchKernelGGL(k_se_fwd, dim3(N), dim3(128), 0, (hipStream_t)stream, pooled, w1, b1, w2, b2, save, gate, gate_stride, gate_coff,
                      N, C, J, mode);
@@ -365,7 +365,7 @@ extern "C" int lhn_se_mlp_bwd(const float* pooled, const float* w1, const float*
 extern "C" int lhn_se_mlp_bwd2(const float* pooled, const float* w1, const float* w2, const float* save, const float* dgate,
                                float* dpool, int cstride, int coff, int H, int W, float* dw1, float* db1, float* dw2, float* db2,
                                int N, int C, int J, int mode, void* stream) {
-  LHN_CHECK_ARG(pooled && w1 && w2 && save && dgate && dpool && dw1 && db1 && dw2 && db2, "lhn_se_mlp_bwd: null pointer");
+  LHN_CHECK_ARG(pooled && w1 && w2 && save && dgate && dpool && dw1 && dw2 && !db1 == !db2, "lhn_se_mlp_bwd: null pointer (db1, db2: both or neither)");
   LHN_CHECK_ARG(C > 0 && C <= 256 && J > 0 && J <= 64 && N > 0 && H > 0 && W > 0, "lhn_se_mlp_bwd: C=%d J=%d", C, J);
   hipLaunchKernelGGL(k_se_bwd, dim3(lhn_deterministic_mode() ? 1 : N), dim3(256), 0, (hipStream_t)stream, pooled, w1, w2, save, dgate, dpool, cstride, coff,
                      1.f / (float)(H * W), dw1, db1, dw2, db2, N, C, J, mode);

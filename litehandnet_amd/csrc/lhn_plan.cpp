@@ -23,10 +23,10 @@ static lhn_bnsum mkbns(void* ws, int64_t sums_off, int64_t save_off, int C, int 
 enum {
   OP_STEM = 1, OP_PW = 2, OP_DW = 3, OP_KXK = 4, OP_FINALIZE = 5, OP_EW = 6, OP_MAXPOOL = 7, OP_AVGPOOL = 8,
   OP_CA_MLP = 9, OP_TABLE_FILL = 10, OP_MEMSET = 11, OP_ATT_MLP = 12, OP_SE_MLP = 13, OP_SHUFFLE = 14,
-  OP_PWDW = 15, OP_DWPW = 16, OP_MSRB = 17,
+  OP_PWDW = 15, OP_DWPW = 16, OP_MSRB = 17, OP_CBAM = 18,
   OP_STEM_BWD = 101, OP_PW_BWD = 102, OP_DW_BWD = 103, OP_KXK_BWD = 104, OP_BN_BWD = 105, OP_EW_BWD = 106,
   OP_MAXPOOL_BWD = 107, OP_AVGPOOL_BWD = 108, OP_GATE_REDUCE = 109, OP_CA_MLP_BWD = 110, OP_ATT_MLP_BWD = 111, OP_SE_MLP_BWD = 112,
-  OP_SHUFFLE_BWD = 113,
+  OP_SHUFFLE_BWD = 113, OP_CBAM_BWD = 114,
 };
 
 // One captured launch sequence (hipGraph) of a phase for one set of pointers.
@@ -670,6 +670,24 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
                              reinterpret_cast<const float*>(at(ws, o.ws[3])), reinterpret_cast<float*>(at(ws, b.dpool_off)), b.C,
                              o.out_coff, b.H, b.W, prm<float>(grads, o.p[2]), prm<float>(grads, o.p[3]), prm<float>(grads, o.p[4]),
                              prm<float>(grads, o.p[5]), b.N, o.out_C, o.i[0], o.i[1], stream);
+        break;
+      }
+      case OP_CBAM: {  // in: p, r; p: w1, w2, w7; ws: save
+        lhn_view p = mkview(P, ws, o.in_buf[0], o.in_coff[0], o.in_C[0]), r = mkview(P, ws, o.in_buf[1], o.in_coff[1], o.in_C[1]);
+        lhn_view y = mkview(P, ws, o.out_buf, o.out_coff, o.out_C);
+        rc = lhn_cbam_fwd(&p, &r, prm<const float>(params, o.p[0]), prm<const float>(params, o.p[1]), prm<const float>(params, o.p[2]),
+                          &y, reinterpret_cast<float*>(at(ws, o.ws[0])), stream);
+        break;
+      }
+      case OP_CBAM_BWD: {  // in: p, r; p: w1, w2, w7 (params) | dw1, dw2, dw7 (grads); ws: save, scratch
+        lhn_view p = mkview(P, ws, o.in_buf[0], o.in_coff[0], o.in_C[0]), r = mkview(P, ws, o.in_buf[1], o.in_coff[1], o.in_C[1]);
+        lhn_view y = mkview(P, ws, o.out_buf, o.out_coff, o.out_C);
+        rc = lhn_cbam_bwd(&p, &r, prm<const float>(params, o.p[0]), prm<const float>(params, o.p[1]), prm<const float>(params, o.p[2]),
+                          &y, reinterpret_cast<const float*>(at(ws, P->bufs[o.out_buf].grad_off)),
+                          reinterpret_cast<float*>(at(ws, P->bufs[o.in_buf[0]].grad_off)),
+                          reinterpret_cast<float*>(at(ws, P->bufs[o.in_buf[1]].grad_off)), prm<float>(grads, o.p[3]),
+                          prm<float>(grads, o.p[4]), prm<float>(grads, o.p[5]), reinterpret_cast<const float*>(at(ws, o.ws[0])),
+                          reinterpret_cast<float*>(at(ws, o.ws[1])), stream);
         break;
       }
       default:

@@ -1,6 +1,6 @@
 """Model registry -- models/__init__.py:11-26 restricted to the hot path."""
 
-__all__ = ["litehandnet", "litehourglass", "mynet", "hourglass", "litehrnet"]
+__all__ = ["litehandnet", "litehourglass", "mynet", "hourglass", "litehrnet", "hourglass_ablation"]
 
 
 def get_model(cfg):
@@ -18,5 +18,8 @@ def get_model(cfg):
     if name == "litehrnet":
         from .lite_hrnet import LiteHRNet
         return LiteHRNet(cfg)
+    if name == "hourglass_ablation":
+        from .hourglass_ablation import hourglass_ablation
+        return hourglass_ablation(cfg)
     from .liteHandNet import LiteHandNet
     return LiteHandNet(cfg)

@@ -29,7 +29,9 @@ PWDW = 15              # inference plans only: 1x1 -> depthwise 3x3 in one launc
 DWPW = 16              # inference plans only: depthwise 3x3 -> 1x1 in one launch (lhn_conv_dw3_pw_fwd), see PlanBuilder.fuse_dw_pw
 MSRB = 17              # inference plans only: both depthwise branches of an MSRB round (+ its attention's pooling) in one pass
                        # (lhn_msrb_round_fwd), see PlanBuilder.fuse_msrb_round
+CBAM = 18              # the CBAM chain between its `pre` convolutions and its final ReLU (lhn_cbam_fwd), see PlanBuilder.cbam_attention
 STEM_BWD, PW_BWD, DW_BWD, KXK_BWD, BN_BWD, EW_BWD, MAXPOOL_BWD, AVGPOOL_BWD, GATE_REDUCE, CA_MLP_BWD, ATT_MLP_BWD, SE_MLP_BWD, SHUFFLE_BWD = range(101, 114)
+CBAM_BWD = 114
 SLOPE_SILU = 2.0       # LHN_SLOPE_SILU in include/lhn.h: the combine applies SiLU instead of a leaky ReLU
 SLOPE_RELU_SIGMOID = 3.0   # LHN_SLOPE_RELU_SIGMOID: sigmoid(relu(v)) (lite_hrnet.py: nn.ReLU followed by nn.Sigmoid)
 EW_MUL, EW_BILINEAR = 1, 2   # EwSrcs.mode bits: product of the sources / bilinear (align_corners) resampling of smaller ones
@@ -121,7 +123,7 @@ def _reads(rec):
     k = rec["op"]
     if k in (STEM, PW, DW, KXK, MAXPOOL, AVGPOOL):
         return [rec["x"]]
-    return rec["srcs"] if k == EW else [rec["a"], rec["b"]] if k == SHUFFLE else []
+    return rec["srcs"] if k == EW else [rec["a"], rec["b"]] if k == SHUFFLE else [rec["p"], rec["r"]] if k == CBAM else []
 
 
 def _al(n):
@@ -562,13 +564,14 @@ class PlanBuilder:
         b.gate = True
         return y
 
-    def se_attention(self, y, se, convs=None, mode=0):
+    def se_attention(self, y, se, convs=None, mode=0, global_pool=False):
         """SEBlock (common.py:23-37) on the WHOLE buffer behind `y` (square maps: avg_pool2d(kernel=W) is global).
-        convs = (down, up) Conv2d modules when they are not `se.down` / `se.up`; mode 1 = SpatialWeighting of
-        lite_hrnet.py:55-74 (global average pool, sigmoid(relu(.)) after both convolutions)."""
+        convs = (down, up) Conv2d modules when they are not `se.down` / `se.up` -- or nn.Linear ones ([J, C] / [C, J], the
+        same memory), with or without biases; mode 1 = SpatialWeighting of lite_hrnet.py:55-74 (global average pool,
+        sigmoid(relu(.)) after both convolutions); global_pool: mode 0 behind nn.AdaptiveAvgPool2d(1), any map shape."""
         b = self.bufs[y.buf]
         assert y.coff == 0 and y.C == b.C and not b.gate, "attention gates a whole, ungated buffer"
-        if y.H != y.W and mode == 0:
+        if y.H != y.W and mode == 0 and not global_pool:
             raise _lib.LhnError("SEBlock pools with kernel_size = width: only square maps are built")
         down, up = convs if convs is not None else (se.down, se.up)
         Cc, J = y.C, down.weight.shape[0]
@@ -580,6 +583,26 @@ class PlanBuilder:
         self.recs.append(rec)
         b.gate = True
         return y
+
+    def cbam_attention(self, x, mod):
+        """CBAM (attention.py:269-294) of the plain tensor x; `mod` holds pre (biased 3x3 + BN + ReLU + biased 3x3 + BN), residual_conv
+        (a biased 1x1), ca.sharedMLP (two bias-free 1x1 convolutions) and sa.conv (7x7, 2 -> 1).  pre and residual_conv are ordinary
+        convolution records; one CBAM record reads p = pre's output (left UNGATED: its value is raw + table) and r, and writes the
+        block's output into a new plain buffer.  Its backward hands the convolutions' backward d(loss)/d(value) of p and of r."""
+        x = self.real(self.single(x))
+        pre, Cc = mod.pre, mod.pre[3].weight.shape[0]
+        if Cc % 16 or Cc > 256:
+            raise _lib.LhnError(f"CBAM over {Cc} channels: the kernels take multiples of 16 up to 256 (the MLP has C / 16 hidden neurons)")
+        t = self.conv(x, pre[0], pre[1], slope=0.0)
+        p = self.conv(t, pre[3], pre[4])
+        r = self.conv(x, mod.residual_conv, None)
+        out = self.new(p.H, p.W, Cc)
+        sv, sc = _lib.cbam_layout(self.N, p.H, p.W, Cc)
+        rec = dict(op=CBAM, p=p, r=r, out=out, mod=mod, save=self._ws("misc", 4 * sv[-1]))
+        if self.with_backward:
+            rec["scratch"] = self._ws("misc", 4 * sc[-1])
+        self.recs.append(rec)
+        return out
 
     def set_output(self, y):
         """Generic (block-level) output: materialise the consumed value into a plain buffer."""
@@ -978,7 +1001,8 @@ class PlanBuilder:
         emit = {STEM: self._fwd_conv, PW: self._fwd_conv, DW: self._fwd_conv, KXK: self._fwd_conv, PWDW: self._fwd_pwdw, DWPW: self._fwd_dwpw,
                 MSRB: self._fwd_msrb,
                 FINALIZE: self._fwd_table, TABLE_FILL: self._fwd_table, EW: self._fwd_ew, SHUFFLE: self._fwd_pool,
-                MAXPOOL: self._fwd_pool, AVGPOOL: self._fwd_pool, CA_MLP: self._fwd_ca, SE_MLP: self._fwd_se, ATT_MLP: self._fwd_att}
+                MAXPOOL: self._fwd_pool, AVGPOOL: self._fwd_pool, CA_MLP: self._fwd_ca, SE_MLP: self._fwd_se, ATT_MLP: self._fwd_att,
+                CBAM: self._fwd_cbam}
         fwd = [self._mk(MEMSET, ws=(self.arena_base["zf"], self.ar["zf"].size))] if self.ar["zf"].size else []
         for r in self.recs:
             fwd += emit[r["op"]](r)
@@ -1094,6 +1118,13 @@ class PlanBuilder:
                          ws=(self._abs(r["pooled"]), self._abs(r["save"]), self._abs(r["mask"]), self._abs(r["gsum"])),
                          f=(bn.eps, bn.momentum))]
 
+    def _cbam_params(self, r):
+        m = r["mod"]
+        return (self._p(m.ca.sharedMLP[0].weight), self._p(m.ca.sharedMLP[2].weight), self._p(m.sa.conv.weight))
+
+    def _fwd_cbam(self, r):
+        return [self._mk(CBAM, ins=(r["p"], r["r"]), out=r["out"], p=self._cbam_params(r), ws=(self._abs(r["save"]),))]
+
     # ------------------------------------------------------------------ backward lowering
     def _lower_backward(self):
         """The backward op list: the analyses (each one consults the results of those above it), then one emitter per record
@@ -1111,10 +1142,10 @@ class PlanBuilder:
         fz.fused_mp, fz.skip_ew_src, fz.skip_ap = self._pool_grad_fusion(pending_add, fz.bns_of)
         emit = {STEM: self._bwd_conv, PW: self._bwd_conv, DW: self._bwd_conv, KXK: self._bwd_conv, EW: self._bwd_ew,
                 SHUFFLE: self._bwd_shuffle, MAXPOOL: self._bwd_maxpool, AVGPOOL: self._bwd_avgpool,
-                CA_MLP: self._bwd_ca, SE_MLP: self._bwd_se, ATT_MLP: self._bwd_att}
+                CA_MLP: self._bwd_ca, SE_MLP: self._bwd_se, ATT_MLP: self._bwd_att, CBAM: self._bwd_cbam}
         body = []
         for r in reversed(self.recs):
-            if r["op"] in (STEM, PW, DW, KXK, EW, SHUFFLE, MAXPOOL, AVGPOOL) and not (r["op"] == PW and r.get("nchw")) and \
+            if r["op"] in (STEM, PW, DW, KXK, EW, SHUFFLE, MAXPOOL, AVGPOOL, CBAM) and not (r["op"] == PW and r.get("nchw")) and \
                     not (self.out_ref is not None and not isinstance(r["out"], TCat) and r["out"].buf == self.out_ref.buf):
                 self._covered(fz.written, r["out"])      # (the block output's gradient is written by the engine, not by an op)
             body += emit[r["op"]](r, fz)
@@ -1468,6 +1499,14 @@ class PlanBuilder:
         return [self._mk(GATE_REDUCE, out=y, ws=(-1, -1, -1, self._abs(r["dgate"]))),
                 self._mk(SE_MLP_BWD, out=y, p=(P(dn.weight), P(up.weight), P(dn.weight), P(dn.bias), P(up.weight), P(up.bias)),
                          ws=(self._abs(r["pooled"]), self._abs(r["save"]), -1, self._abs(r["dgate"])), i=(r["J"], r["mode"]))]
+
+    def _bwd_cbam(self, r, fz):
+        """d(p) and d(r) are stored: the CBAM record is the only reader of both buffers (cbam_attention made them)."""
+        for t in (r["p"], r["r"]):
+            if self._grad_mode(fz.written, t) != 1:
+                raise _lib.LhnError("CBAM backward stores the gradients of its two inputs: they must have no other reader")
+        pp = self._cbam_params(r)
+        return [self._mk(CBAM_BWD, ins=(r["p"], r["r"]), out=r["out"], p=pp + pp, ws=(self._abs(r["save"]), self._abs(r["scratch"])))]
 
     def _bwd_att(self, r, fz):
         y, att, P = r["y"], r["att"], self._p
