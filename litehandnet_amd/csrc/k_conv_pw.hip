@@ -1027,20 +1027,38 @@ static int launch_pw_bwd(const lhn_view* x, const float* w, const lhn_view* y, c
 // path ran (tests/test_pw_gpu.py pins dz = dy for these shapes).  PX: pixels per tile (64, or 32 where 64 does not fit the registers).
 // PF: what rides in the register prefetch one tile ahead, 0 = x, 1 = x and y, 2 = x, y and dz; the rest is fetched inside commit()
 // four rows at a time, so that its registers are not live across the MFMA phase.
-template <int CIN, int COUT, int PX, int PF>
-__global__ void __launch_bounds__(256, 2) k_pw_bwd_wr(lhn_view x, const float* __restrict__ w, lhn_view y, lhn_gradview gy,
-                                                      float* __restrict__ dx, int dx_acc, float* __restrict__ dw, float* __restrict__ dbias,
-                                                      int M, int ntiles, int nrep, int64_t rep_stride) {
+//
+// The NARROW shapes (64 -> 64, 32 -> 32; k_pw_bwd's largest launches on the big maps) run here too, registers to spare:
+//   DYST = false: dz is only read (the callers of the fused path rely on that), one write pass less per tile.
+//   64 -> 64: as CIN = 64 above with one dW tile per wave.
+//   32 -> 32: one channel tile on each side, PX = 128: wave v takes pixels [32 v, 32 v + 32) of the tile in dX AND in dW (its own
+//       quarter of K for the whole launch, no predicate in the loop); the four partial 32x32 tiles meet in LDS in wave order at the
+//       flush, then one add per element into the workgroup's replica.
+//   BNS: reader-side BatchNorm sums (lhn_bnsum) with the meaning they have in k_pw_bwd: the lane that holds dX[m][ci] adds
+//       du = dX * act'(u) and du * xhat to its channel's sums.  A wave keeps ONE channel tile, so the channel's constants are five
+//       registers; raw x comes from an LDS copy of the staged tile (Xr, written at commit in these instances only) where k_pw_bwd
+//       re-read it from global memory.  Rows beyond M are zero rows of dYs: their dX is exactly 0 and adds nothing.
+// OCC: workgroups per CU the register budget is cut for (waves per SIMD of __launch_bounds__).
+template <int CIN, int COUT, int PX, int PF, bool DYST, bool BNS, int OCC>
+__global__ void __launch_bounds__(256, OCC) k_pw_bwd_wr(lhn_view x, const float* __restrict__ w, lhn_view y, lhn_gradview gy,
+                                                        float* __restrict__ dx, int dx_acc, float* __restrict__ dw, float* __restrict__ dbias,
+                                                        int M, int ntiles, int nrep, int64_t rep_stride, lhn_bnsum bs) {
   constexpr int NTI = CIN / 32, NTO = COUT / 32, LDY = COUT + 4, LDX = CIN + 4;
-  constexpr int NDW = NTO * NTI / 4;            // dW tiles per wave
+  constexpr bool ONE = NTI == 1;                // 32 -> 32: the single dW tile is split over the waves by pixels, not by tiles
+  constexpr int NDW = ONE ? 1 : NTO * NTI / 4;  // dW tiles per wave
+  constexpr int KW = ONE ? 32 : PX;             // pixels of a tile that one wave sums into its dW tiles
   constexpr int NDX = (NTI == 4 && PX == 64) ? 2 : 1;      // 32-pixel sub-tiles of dX per wave
-  static_assert((NTI == 2 || NTI == 4) && (NTO == 2 || NTO == 4) && NDW >= 2 && (PX == 64 || (PX == 32 && NTI == 4)), "wide instances only");
+  constexpr int NWC = 4 / NTI;                  // waves that share an input-channel tile in dX (BNS: partial sums per channel)
+  static_assert(ONE ? (NTO == 1 && PX == 128) : ((NTI == 2 || NTI == 4) && (NTO == 2 || NTO == 4) && (PX == 64 || (PX == 32 && NTI == 4))),
+                "32 -> 32 at 128 pixels; 64 / 128 channels on either side at 64 (or 32) pixels");
+  static_assert(!BNS || NDX == 1, "reader-side sums: one dX sub-tile per wave");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* dYs = smem;                  // [PX][LDY]
   float* Xs = dYs + PX * LDY;         // [PX][LDX]
   float* xt = Xs + PX * LDX;          // [3][CIN]   scale | shift | slope of x
   float* yt = xt + 3 * CIN;           // [3][COUT]  the same of y
   float* cf = yt + 3 * COUT;          // [3][COUT]  A | B | C
+  float* Xr = cf + 3 * COUT;          // [PX][CIN]  raw x of the staged tile (BNS only)
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, lh = lane >> 5;
   const int HoWo = y.H * y.W;
   float* dzw = const_cast<float*>(gy.dz);
@@ -1077,9 +1095,10 @@ __global__ void __launch_bounds__(256, 2) k_pw_bwd_wr(lhn_view x, const float* _
       f4 v = (f4){0.f, 0.f, 0.f, 0.f};
       if (m < M) {
         v = lhn_apply_xf(xraw[p], xxf);
-        if (x.gate) v *= *reinterpret_cast<const f4*>(x.gate + (int64_t)(m / HoWo) * x.cstride + xabs);
+        if (!BNS && x.gate) v *= *reinterpret_cast<const f4*>(x.gate + (int64_t)(m / HoWo) * x.cstride + xabs);      // (sums: no gate, host-checked)
       }
       *reinterpret_cast<f4*>(Xs + row * LDX + 4 * xc4) = v;
+      if (BNS) *reinterpret_cast<f4*>(Xr + row * CIN + 4 * xc4) = m < M ? xraw[p] : (f4){0.f, 0.f, 0.f, 0.f};
     }
     Xf4 yxf;
     Gr4 ygr;
@@ -1112,7 +1131,7 @@ __global__ void __launch_bounds__(256, 2) k_pw_bwd_wr(lhn_view x, const float* _
         const f4 du = lhn_grad_du(y, gy, yxf, yraw[p], ydz[p], n, h, ww, yabs);
         v = ygr.A * du + ygr.B * yraw[p] + ygr.Cc;
         bsum += v;
-        *reinterpret_cast<f4*>(dzw + (int64_t)m * y.cstride + yabs) = v;
+        if (DYST) *reinterpret_cast<f4*>(dzw + (int64_t)m * y.cstride + yabs) = v;
       }
       *reinterpret_cast<f4*>(dYs + row * LDY + 4 * yc4) = v;
     }
@@ -1134,7 +1153,8 @@ __global__ void __launch_bounds__(256, 2) k_pw_bwd_wr(lhn_view x, const float* _
     cf[2 * COUT + i] = gy.coef ? gy.coef[2 * y.cstride + y.coff + i] : 0.f;
   }
   // ---- B fragments of the data gradient: wreg[kc*4 + j] = W[8*kc + 4*lh + j][32*jt + l31]  (K permutation of the dYs reads below)
-  const int jt = NTI == 4 ? wave : wave >> 1;
+  const int jt = NTI == 4 ? wave : NTI == 2 ? wave >> 1 : 0;
+  const int mt0 = NTI == 4 ? 0 : NTI == 2 ? (wave & 1) : wave;      // first 32-pixel sub-tile of the wave in dX
   float wreg[COUT / 2];
 #pragma unroll
   for (int k = 0; k < COUT / 2; ++k) wreg[k] = dx ? w[(int64_t)((k >> 2) * 8 + 4 * lh + (k & 3)) * CIN + 32 * jt + l31] : 0.f;
@@ -1143,18 +1163,33 @@ __global__ void __launch_bounds__(256, 2) k_pw_bwd_wr(lhn_view x, const float* _
   for (int t = 0; t < NDW; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) accw[t][r] = 0.f;
+  // reader-side sums: the constants of this lane's channel 32 jt + l31 and its two partial sums
+  float b_sc = 1.f, b_sh = 0.f, b_sl = 1.f, b_mean = 0.f, b_inv = 0.f, b_s = 0.f, b_q = 0.f;
+  if (BNS) {
+    const int ci = 32 * jt + l31;
+    if (x.table) {
+      b_sc = x.table[x.coff + ci];
+      b_sh = x.table[x.cstride + x.coff + ci];
+      b_sl = x.table[2 * x.cstride + x.coff + ci];
+    }
+    b_mean = bs.save[bs.coff + ci];
+    b_inv = bs.save[bs.C + bs.coff + ci];
+  }
+  // (the flush address of this thread's channel, formed once)
+  double* const bst = BNS ? bs.sums + (size_t)(blockIdx.x % LHN_STAT_REPLICAS) * 2 * bs.C + bs.coff + (tid & (CIN - 1)) : nullptr;
+  const int bsC = BNS ? bs.C : 0;
   __syncthreads();
 
   for (; tile < ntiles; tile += gridDim.x) {
     commit(tile);
     __syncthreads();
     if (tile + (int)gridDim.x < ntiles) issue(tile + gridDim.x);
-    // ---- dW += dY^T X   (K = PX pixels)
+    // ---- dW += dY^T X   (K = KW pixels: the whole tile, or this wave's quarter of it)
     {
-      const float* ap = dYs + lh * LDY + l31 + 32 * (wave / NTI);
-      const float* bp = Xs + lh * LDX + l31 + 32 * (wave % NTI);
+      const float* ap = dYs + ((ONE ? 32 * wave : 0) + lh) * LDY + l31 + (ONE ? 0 : 32 * (wave / NTI));
+      const float* bp = Xs + ((ONE ? 32 * wave : 0) + lh) * LDX + l31 + (ONE ? 0 : 32 * (wave % NTI));
 #pragma unroll 4
-      for (int ks = 0; ks < PX / 2; ++ks) {
+      for (int ks = 0; ks < KW / 2; ++ks) {
         const float b = bp[(2 * ks) * LDX];
         float a[NDW];
 #pragma unroll
@@ -1170,7 +1205,6 @@ __global__ void __launch_bounds__(256, 2) k_pw_bwd_wr(lhn_view x, const float* _
       for (int hh = 0; hh < NDX; ++hh)
 #pragma unroll
         for (int r = 0; r < 16; ++r) accx[hh][r] = 0.f;
-      const int mt0 = NTI == 4 ? 0 : (wave & 1);      // (PX = 32: one sub-tile, every wave its own channel tile)
       const float* arow = dYs + (mt0 * 32 + l31) * LDY + 4 * lh;
 #pragma unroll
       for (int kc = 0; kc < COUT / 8; ++kc) {
@@ -1189,6 +1223,16 @@ __global__ void __launch_bounds__(256, 2) k_pw_bwd_wr(lhn_view x, const float* _
       for (int hh = 0; hh < NDX; ++hh) {
         const int mbase = tile * PX + (mt0 + hh) * 32 + 4 * lh;
         float* o = dx + (int64_t)mbase * cs + x.coff + 32 * jt + l31;
+        if (BNS) {
+          const float* xr = Xr + ((mt0 + hh) * 32 + 4 * lh) * CIN + 32 * jt + l31;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const float raw = xr[((r & 3) + 8 * (r >> 2)) * CIN];
+            const float du = accx[hh][r] * (raw * b_sc + b_sh > 0.f ? 1.f : b_sl);
+            b_s += du;
+            b_q += du * ((raw - b_mean) * b_inv);
+          }
+        }
         if (tile * PX + PX <= M) {        // whole tile inside the tensor: stores off one base pointer, no row predicate
           if (dx_acc) {
 #pragma unroll
@@ -1196,6 +1240,13 @@ __global__ void __launch_bounds__(256, 2) k_pw_bwd_wr(lhn_view x, const float* _
           } else {
 #pragma unroll
             for (int r = 0; r < 16; ++r) o[((r & 3) + 8 * (r >> 2)) * cs] = accx[hh][r];
+          }
+        } else if constexpr (BNS) {      // the tail tile with row offsets per lane: as scalars, next to the sums' own, they spilled 22 SGPRs
+          float* ot = dx + (int64_t)(tile * PX + (mt0 + hh) * 32) * cs + x.coff + 32 * jt + l31;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int ro = (r & 3) + 8 * (r >> 2) + 4 * lh;
+            if (tile * PX + (mt0 + hh) * 32 + ro < M) ot[(int64_t)ro * cs] = dx_acc ? ot[(int64_t)ro * cs] + accx[hh][r] : accx[hh][r];
           }
         } else {
 #pragma unroll
@@ -1209,15 +1260,49 @@ __global__ void __launch_bounds__(256, 2) k_pw_bwd_wr(lhn_view x, const float* _
     __syncthreads();
   }
 
+  if (BNS) {      // lane halves by shuffle, the NWC waves of a channel tile in LDS in wave order (Xs is free now), one add per channel
+    float* bred = Xs;                                   // [NTI][NWC][2][32]
+    const float ss = b_s + __shfl_xor(b_s, 32, 64), qq = b_q + __shfl_xor(b_q, 32, 64);
+    if (lh == 0) {
+      bred[((jt * NWC + mt0) * 2 + 0) * 32 + l31] = ss;
+      bred[((jt * NWC + mt0) * 2 + 1) * 32 + l31] = qq;
+    }
+    __syncthreads();
+    if (tid < CIN) {
+      const int jc = tid >> 5, c = tid & 31;
+      double ds = 0.0, dq = 0.0;
+#pragma unroll
+      for (int v = 0; v < NWC; ++v) {
+        ds += (double)bred[((jc * NWC + v) * 2 + 0) * 32 + c];
+        dq += (double)bred[((jc * NWC + v) * 2 + 1) * 32 + c];
+      }
+      atomicAdd(bst, ds);
+      atomicAdd(bst + bsC, dq);
+    }
+  }
   // ---- flush dW (C/D layout: row = co within the tile, col = lane&31 = ci within the tile): one add per element and workgroup
   dw += (size_t)(blockIdx.x % nrep) * rep_stride;
+  if constexpr (ONE) {      // the four pixel quarters of the one tile: summed in wave order (dYs is free: the loop ended at a barrier)
+    float* wred = dYs;                                  // [4 waves][16][64 lanes] <= PX * LDY floats
 #pragma unroll
-  for (int t = 0; t < NDW; ++t) {
-    const int it = wave / NTI + (4 / NTI) * t, jw = wave % NTI;
+    for (int r = 0; r < 16; ++r) wred[(wave * 16 + r) * 64 + lane] = accw[0][r];
+    __syncthreads();
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int co = 32 * it + (r & 3) + 8 * (r >> 2) + 4 * lh;
-      atomicAdd(dw + (int64_t)co * CIN + 32 * jw + l31, accw[t][r]);
+    for (int q = 0; q < 4; ++q) {
+      const int r = 4 * q + wave, co = (r & 3) + 8 * (r >> 2) + 4 * lh;
+      const float v = ((wred[r * 64 + lane] + wred[(16 + r) * 64 + lane]) + wred[(32 + r) * 64 + lane]) + wred[(48 + r) * 64 + lane];
+      atomicAdd(dw + (int64_t)co * CIN + l31, v);
+    }
+    if (dbias) __syncthreads();      // (dbias stages in dYs as well)
+  } else {
+#pragma unroll
+    for (int t = 0; t < NDW; ++t) {
+      const int it = wave / NTI + (4 / NTI) * t, jw = wave % NTI;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int co = 32 * it + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        atomicAdd(dw + (int64_t)co * CIN + 32 * jw + l31, accw[t][r]);
+      }
     }
   }
   if (dbias) {      // column sums of dy in a fixed order, one add per channel into the workgroup's replica (as k_pw_bwd; dYs is free)
@@ -1240,22 +1325,35 @@ __global__ void __launch_bounds__(256, 2) k_pw_bwd_wr(lhn_view x, const float* _
 //   128 -> 128: PX = 32, x and y prefetched.  With 64-pixel tiles the budget of 64 (W) + 64 (dW) + 32 (dX) + staging does not close:
 //               61..133 registers spill whichever tensors ride in the prefetch (the dX phase with two sub-tiles is the peak).
 //   64 -> 128:  PX = 64, x and y prefetched (dz too: 1 spill).      128 -> 64: PX = 64, x, y and dz prefetched.
-template <int CIN, int COUT, int PX, int PF>
+// Narrow instances (no dy store; plain and with reader-side sums):
+//   64 -> 64:   PX = 64, x, y and dz prefetched, two workgroups per CU (a third costs spills).
+//   32 -> 32:   PX = 128, x, y and dz prefetched.
+template <int CIN, int COUT, int PX, int PF, bool DYST = true, bool BNS = false, int OCC = 2>
 static int launch_pw_bwd_wr(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc, float* dw,
-                            float* dbias, int nrep, int64_t rep_stride, hipStream_t s) {
+                            float* dbias, int nrep, int64_t rep_stride, hipStream_t s, const lhn_bnsum& bs) {
   const int M = y->N * y->H * y->W, ntiles = (M + PX - 1) / PX;
-  const size_t lds = (size_t)(PX * (COUT + 4) + PX * (CIN + 4) + 3 * CIN + 6 * COUT) * sizeof(float);
+  const size_t lds = (size_t)(PX * (COUT + 4) + PX * (CIN + 4) + 3 * CIN + 6 * COUT + (BNS ? PX * CIN : 0)) * sizeof(float);
   static LhnKernelCfg cfg;
   int per_cu = 1;
-  if (!lhn_kernel_cfg(cfg, &k_pw_bwd_wr<CIN, COUT, PX, PF>, lds, 2, &per_cu)) {
+  if (!lhn_kernel_cfg(cfg, &k_pw_bwd_wr<CIN, COUT, PX, PF, DYST, BNS, OCC>, lds, OCC, &per_cu)) {
     lhn_set_error("lhn_conv_pw_bwd: cannot reserve %zu B of LDS", lds);
     return 2;
   }
   int grid = lhn_num_cus() * per_cu;
   if (grid > ntiles) grid = ntiles;
-  hipLaunchKernelGGL((k_pw_bwd_wr<CIN, COUT, PX, PF>), dim3(grid), dim3(256), lds, s, *x, w, *y, *gy, dx, dx_acc, dw, dbias, M, ntiles,
-                     nrep, rep_stride);
+  hipLaunchKernelGGL((k_pw_bwd_wr<CIN, COUT, PX, PF, DYST, BNS, OCC>), dim3(grid), dim3(256), lds, s, *x, w, *y, *gy, dx, dx_acc, dw, dbias,
+                     M, ntiles, nrep, rep_stride, bs);
   return 0;
+}
+
+// LHN_PW_BWD_NARROW=0: 64 -> 64 and 32 -> 32 stay on k_pw_bwd as before the narrow instances existed (A/B comparisons)
+static bool pw_bwd_narrow_off() {
+  static int off = -1;
+  if (off < 0) {
+    const char* e = getenv("LHN_PW_BWD_NARROW");
+    off = (e && e[0] == '0') ? 1 : 0;
+  }
+  return off == 1;
 }
 
 // LHN_PW_BWD_SPLIT=1: the wide shapes take lhn_pw_bwd_split as before k_pw_bwd_wr existed (A/B comparisons)
@@ -1302,14 +1400,28 @@ extern "C" int lhn_conv_pw_bwd3(const lhn_view* x, const float* w, const lhn_vie
   // LHN_PW_LDSW=1, which means "no register-W kernel", keep the split path)
   if (!bs.sums && stride == 1 && !dy_nchw && wcols == Cin && wrows == Cout && !pw_bwd_split_forced() && !pw_wr_off()) {
     int rc = -1;
-    if (Cin == 128 && Cout == 128) rc = launch_pw_bwd_wr<128, 128, 32, 1>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s);
-    else if (Cin == 64 && Cout == 128) rc = launch_pw_bwd_wr<64, 128, 64, 1>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s);
-    else if (Cin == 128 && Cout == 64) rc = launch_pw_bwd_wr<128, 64, 64, 2>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s);
+    if (Cin == 128 && Cout == 128) rc = launch_pw_bwd_wr<128, 128, 32, 1>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs);
+    else if (Cin == 64 && Cout == 128) rc = launch_pw_bwd_wr<64, 128, 64, 1>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs);
+    else if (Cin == 128 && Cout == 64) rc = launch_pw_bwd_wr<128, 64, 64, 2>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs);
     if (rc == 0) {
       LHN_CHECK_LAUNCH("lhn_conv_pw_bwd");
       return 0;
     }
     if (rc > 0) return rc;
+  }
+  // 64 -> 64 and 32 -> 32, with or without reader-side sums: the narrow register-W instances (LHN_PW_BWD_NARROW=0 and
+  // LHN_PW_LDSW=1 keep k_pw_bwd; so do stride 2, the NCHW head and partial channel counts).  The BNS instances compile the
+  // gate on x out: they rely on the `!x->gate` condition for sums checked at the top of this function -- if that check is
+  // ever relaxed, gated sums calls must leave this branch
+  if (stride == 1 && !dy_nchw && wcols == Cin && wrows == Cout && Cin == Cout && (Cin == 64 || Cin == 32) && !pw_bwd_narrow_off() && !pw_wr_off()) {
+    int rc;
+    if (Cin == 64) rc = bs.sums ? launch_pw_bwd_wr<64, 64, 64, 2, false, true>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs)
+                                : launch_pw_bwd_wr<64, 64, 64, 2, false, false>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs);
+    else rc = bs.sums ? launch_pw_bwd_wr<32, 32, 128, 2, false, true>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs)
+                      : launch_pw_bwd_wr<32, 32, 128, 2, false, false, 3>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs);
+    if (rc) return rc;
+    LHN_CHECK_LAUNCH("lhn_conv_pw_bwd");
+    return 0;
   }
   if (!bs.sums && stride == 1 && !dy_nchw && Cin * Cout >= 64 * 128 && Cout % 32 == 0 && Cin % 32 == 0 && Cout <= 256 && wcols == Cin && wrows == Cout) {
     const int rc = lhn_pw_bwd_split(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s);
