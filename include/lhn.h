@@ -70,6 +70,24 @@ typedef struct lhn_bnbwdfin {
   int32_t      cstride, coff, C;
 } lhn_bnbwdfin;
 
+/* BatchNorm-backward finalize on the CONSUMER side.  The (A, B, C) coefficients of  dy = A*du + B*y + C  are read by one kernel only:
+ * the backward of the convolution that owns the BatchNorm (y of that call).  lhn_conv_dw_bwd4 / lhn_conv_pw_bwd4 take the finished
+ * sums instead of a finalized gy->coef: every workgroup folds the replicas of its own channels in its prologue (the order and the
+ * double arithmetic of lhn_bn_bwd_finalize2: same sums, same bits), and one workgroup per channel also stores coef (into gy->coef
+ * at y's cstride / coff) and adds dgamma / dbeta -- memory holds what the separate launch leaves.  The BatchNorm has y->C channels.
+ * Where the launcher picks a kernel without the in-prologue fold it calls lhn_bn_bwd_finalize2 itself first: the result never
+ * depends on the kernel chosen.  NULL pointer to the struct (or sums == NULL): gy->coef is read as it is. */
+typedef struct lhn_bnbwdsrc {
+  const double* sums;              /* [LHN_STAT_REPLICAS][2][stat_channels]: sum du | sum du * xhat, complete before the call */
+  const float*  save_mean_invstd;  /* [2][stat_channels]                                                                     */
+  const float*  gamma;             /* [C] or NULL (= 1)                                                                       */
+  float*        dgamma;            /* [C] added to, or NULL                                                                   */
+  float*        dbeta;             /* [C] added to, or NULL                                                                   */
+  double        count;             /* N*H*W (times the world size under SyncBatchNorm)                                        */
+  float         pgrad_scale;       /* as lhn_bn_bwd_finalize                                                                  */
+  int32_t       stat_channels;     /* channel stride of sums / save, >= y->C                                                  */
+} lhn_bnbwdsrc;
+
 /* BatchNorm-backward sums contributed by a READER.  du = dz * act'(u) is linear in dz, and dz of a convolution output is the sum
  * of what its readers' backward kernels hand back -- so every reader that has its own part of dz in registers can add that
  * part's  sum du  and  sum du * xhat  into the PRODUCER's replicated sums (the reader holds the raw value and the table of its
@@ -477,6 +495,17 @@ int lhn_avgpool_bwd3(const lhn_view* x, const float* dout, int OH, int OW, int o
 int lhn_conv_pw_bwd3(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate,
                      float* dw, float* dbias, int stride, const float* dy_nchw, int nrep, int64_t rep_stride,
                      const lhn_pw_opts* opts, const lhn_bnsum* bns /*fused kernel only: Cin * Cout < 64 * 128, stride 1*/, void* stream);
+/* The two backward calls above with the BatchNorm-backward finalize of y taken in the kernel's prologue (lhn_bnbwdsrc; fin NULL =
+ * the calls above).  gy->coef must point at the coefficient table: it is written.  lhn_conv_dw_bwd4 joins lhn_conv_dw_bwd2 (bns: the
+ * producer's sums, x's first channel at bns->coff) and lhn_conv_dw_bwd3 (addends); bns and addends exclude each other as they do there.
+ * In-prologue fold: k_dw3_bwd_rows (3x3, stride 1, "same" padding, W >= 8) and k_pw_bwd_wr (the shapes listed at lhn_conv_pw_bwd3's
+ * register-W dispatch); every other kernel gets a lhn_bn_bwd_finalize2 launch in front, from this call. */
+int lhn_conv_dw_bwd4(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate,
+                     float* dw, int k, int stride, int pad, int dil, int nrep, int64_t rep_stride, const lhn_bnsum* bns,
+                     const float* dx_add0, const float* dx_add1, const lhn_bnbwdsrc* fin, void* stream);
+int lhn_conv_pw_bwd4(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate,
+                     float* dw, float* dbias, int stride, const float* dy_nchw, int nrep, int64_t rep_stride,
+                     const lhn_pw_opts* opts, const lhn_bnsum* bns, const lhn_bnbwdsrc* fin, void* stream);
 int lhn_avgpool_bwd(const lhn_view* x, const float* dout /*[N,OH,OW,C]*/, int OH, int OW, float* dx,
                     int dx_accumulate, void* stream);
 int lhn_gate_bwd_reduce(const lhn_view* y, const float* dz, float* dgate /*[N][C] dense*/, void* stream);

@@ -413,7 +413,9 @@ static int dws2_fwd(const lhn_view* x, const float* w, const lhn_view* y, double
 static int dws2_bwd(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc, float* dw,
                     int nrep, int64_t rep_stride, hipStream_t s);
 int lhn_dwk_bwd_lds(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc,
-                    float* dw, int k, int dil, int nrep, int64_t rep_stride, hipStream_t s, const DwBnSum* bs);
+                    float* dw, int k, int dil, int nrep, int64_t rep_stride, hipStream_t s, const DwBnSum* bs,
+                    const lhn_bnbwdsrc* fs = nullptr);
+static bool lhn_dw_bwd_v1();
 static bool lhn_dw_force_gather() {
   static int v = -1;
   if (v < 0) {
@@ -994,6 +996,48 @@ extern "C" int lhn_conv_dw_bwd(const lhn_view* x, const float* w, const lhn_view
   return 0;
 }
 
+static int dw_bwd_fin(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc, float* dw, int k,
+                      int dil, int nrep, int64_t rep_stride, const lhn_bnsum* bns, const float* a0, const float* a1, const lhn_bnbwdsrc* fin,
+                      hipStream_t s);
+// the shapes lhn_conv_dw_bwd / _bwd2 / _bwd3 hand to k_dw3_bwd_rows (has_ext: sums or addends, which ignore LHN_DW_GATHER)
+static bool dw_bwd_folds(const lhn_view* x, const float* w, const float* dw, int k, int stride, int pad, int dil, bool has_ext) {
+  return w && dw && k == 3 && stride == 1 && (dil == 1 || dil == 2) && pad == dil && x->C % 4 == 0 && x->W >= 8 && !lhn_dw_bwd_v1() &&
+         (has_ext || !lhn_dw_force_gather());
+}
+extern "C" int lhn_conv_dw_bwd4(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
+                                int dx_accumulate, float* dw, int k, int stride, int pad, int dil, int nrep, int64_t rep_stride,
+                                const lhn_bnsum* bns, const float* dx_add0, const float* dx_add1, const lhn_bnbwdsrc* fin,
+                                void* stream) {
+  const bool has_bns = bns && bns->sums, has_add = dx_add0 || dx_add1;
+  LHN_CHECK_ARG(!(has_bns && has_add), "lhn_conv_dw_bwd4: producer sums and gradient addends exclude each other");
+  const bool folds = fin && fin->sums;
+  if (folds) {
+    LHN_CHECK_ARG(lhn_view_ok(x) && lhn_view_ok(y) && gy && gy->dz && gy->coef && fin->save_mean_invstd && fin->count > 0 &&
+                      fin->stat_channels >= y->C && x->C == y->C && lhn_no_pend(x) && lhn_no_pend(y),
+                  "lhn_conv_dw_bwd4: finalize source needs gy->coef, saved statistics and stat_channels >= C");
+    if (!dw_bwd_folds(x, w, dw, k, stride, pad, dil, has_bns || has_add)) {      // another kernel: the separate finalize launch, then as ever
+      const int rc = lhn_bn_bwd_finalize2(fin->sums, fin->gamma, fin->save_mean_invstd, const_cast<float*>(gy->coef), y->cstride, y->coff,
+                                          y->C, fin->stat_channels, fin->count, fin->dgamma, fin->dbeta, fin->pgrad_scale, stream);
+      if (rc) return rc;
+    }
+  }
+  if (!folds || !dw_bwd_folds(x, w, dw, k, stride, pad, dil, has_bns || has_add)) {
+    if (has_add) return lhn_conv_dw_bwd3(x, w, y, gy, dx, dx_accumulate, dw, k, stride, pad, dil, nrep, rep_stride, dx_add0, dx_add1, stream);
+    return lhn_conv_dw_bwd2(x, w, y, gy, dx, dx_accumulate, dw, k, stride, pad, dil, nrep, rep_stride, has_bns ? bns->sums : nullptr,
+                            has_bns ? bns->save : nullptr, has_bns ? bns->C : 0, has_bns ? bns->coff : 0, stream);
+  }
+  if (nrep < 1) nrep = 1;
+  LHN_CHECK_ARG(x->C <= 512 && (!has_add || dx), "lhn_conv_dw_bwd4: channels / addends without dx");
+  if (has_bns)      // the conditions of lhn_conv_dw_bwd2
+    LHN_CHECK_ARG(dx && bns->save && !dx_accumulate && !x->gate && dil == 1 && x->C % 32 == 0 && bns->coff >= 0 && bns->coff + x->C <= bns->C,
+                  "lhn_conv_dw_bwd4: fused BatchNorm sums need this convolution to be the only, ungated, stride-1 reader of x (dx stored, dilation 1)");
+  const int rc = dw_bwd_fin(x, w, y, gy, dx, dx_accumulate, dw, k, dil, nrep, rep_stride, has_bns ? bns : nullptr, dx_add0 ? dx_add0 : dx_add1,
+                            dx_add0 ? dx_add1 : nullptr, fin, (hipStream_t)stream);
+  LHN_CHECK_ARG(rc == 1, "lhn_conv_dw_bwd4: no row kernel for k=%d dil=%d", k, dil);
+  LHN_CHECK_LAUNCH("lhn_conv_dw_bwd4");
+  return 0;
+}
+
 extern "C" int lhn_conv_stem_bwd(const float* img, const lhn_view* y, const lhn_gradview* gy, float* dw, int Hi, int Wi, int k,
                                  int stride, int pad, int nrep, int64_t rep_stride, void* stream) {
   if (nrep < 1) nrep = 1;
@@ -1485,7 +1529,7 @@ template <int DIL, bool BNS = false>
 __global__ void __launch_bounds__(256, (BNS || DIL > 1) ? 2 : 3) k_dw3_bwd_rows(lhn_view x, const float* __restrict__ w, lhn_view y, lhn_gradview gy,
                                                          float* __restrict__ dx, int dx_acc, float* __restrict__ dw, int nstrips,
                                                          int nchunks, int CH, int cgroups, int nrep, int64_t rep_stride, int ps,
-                                                         DwBnSum bs) {
+                                                         DwBnSum bs, lhn_bnbwdsrc fs) {
   constexpr int P = DIL, R = 2 * P + 2, WW = 32 + 2 * P, KK = 9;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   f4* tdy = reinterpret_cast<f4*>(smem);        // [R][WW][8] dy ring
@@ -1513,7 +1557,7 @@ __global__ void __launch_bounds__(256, (BNS || DIL > 1) ? 2 : 3) k_dw3_bwd_rows(
     const int i = tid - KK * 8, kind = i >> 3, ca = cg * 32 + 4 * min(i & 7, cvalid - 1), j = kind % 3;
     const float* tab = kind < 3 ? x.table : kind < 6 ? y.table : gy.coef;
     const int cs = kind < 3 ? x.cstride : y.cstride, co = kind < 3 ? x.coff : y.coff;
-    cst[i] = tab ? *reinterpret_cast<const f4*>(tab + j * cs + co + ca) : ((kind < 6 ? j != 1 : j == 0) ? one : z);
+    if (kind < 6 || !fs.sums) cst[i] = tab ? *reinterpret_cast<const f4*>(tab + j * cs + co + ca) : ((kind < 6 ? j != 1 : j == 0) ? one : z);
   } else if (BNS && tid < 2 * KK * 8 + 16) {
     const int i = tid - 2 * KK * 8, kind = i >> 3, cc = i & 7;
     tmi[i] = *reinterpret_cast<const f4*>(bs.save + kind * bs.C + bs.coff + cg * 32 + 4 * cc);
@@ -1588,6 +1632,21 @@ __global__ void __launch_bounds__(256, (BNS || DIL > 1) ? 2 : 3) k_dw3_bwd_rows(
   if (t < ntile) {
     const Item nx = decode(t);
     issue(nx, nx.h0 - P);
+  }
+  // BatchNorm-backward finalize of y in the prologue (lhn_bnbwdsrc): A | B | C of this block's channel group straight into cst,
+  // the sums' loads behind the first halo row's, the replicas as loaded in the dy ring (16 KB of it, first written after the item
+  // loop's opening barrier, which also publishes cst).  Blocks 0 .. cgroups-1 (cg = blockIdx.x) also write memory.
+  if (fs.sums) {
+    float* cfA = reinterpret_cast<float*>(cst + 6 * 8);
+    if (tid >= 4 * cvalid && tid < 32) cfA[tid] = cfA[32 + tid] = cfA[64 + tid] = 0.f;
+    double* raw = reinterpret_cast<double*>(tdy);
+    const int nc = 4 * cvalid;
+    const LhnBwdPre pre = lhn_bn_bwd_pre(fs, cg * 32, nc);
+    lhn_bn_bwd_fold_raw(fs.sums, fs.stat_channels, cg * 32, nc, raw);
+    __syncthreads();
+    if (tid < nc)
+      lhn_bn_bwd_coef_put(lhn_bn_bwd_coef_raw(raw, nc, lhn_fin_groups(y.C), tid, pre, fs.count), fs, const_cast<float*>(gy.coef), y.cstride,
+                          y.coff, cg * 32 + tid, cfA, 32, tid, (int)blockIdx.x < cgroups);
   }
 #pragma unroll 1
   for (; t < ntile; t += gridDim.x) {
@@ -1733,10 +1792,14 @@ static void launch_dwk_bwd(const lhn_view* x, const float* w, const lhn_view* y,
 }
 template <int DIL, bool BNS = false>
 static void launch_dw3_bwd_rows(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc,
-                                float* dw, int nrep, int64_t rep_stride, hipStream_t s, int ps = 1, const DwBnSum* bsp = nullptr) {
+                                float* dw, int nrep, int64_t rep_stride, hipStream_t s, int ps = 1, const DwBnSum* bsp = nullptr,
+                                const lhn_bnbwdsrc* fsp = nullptr) {
   constexpr int P = DIL, R = 2 * P + 2, WW = 32 + 2 * P;
   DwBnSum bs;
   if (bsp) bs = *bsp; else { bs.sums = nullptr; bs.save = nullptr; bs.C = bs.coff = 0; bs.add[0] = bs.add[1] = nullptr; }
+  lhn_bnbwdsrc fs;      // the fold's scratch is 16 KB of the dy ring (17,408 B at DIL = 1)
+  if (fsp) fs = *fsp; else memset(&fs, 0, sizeof(fs));
+  static_assert(R * WW * 8 * 16 >= 2 * LHN_FIN_THREADS * 8, "dy ring holds the replica fold's partials");
   const int cg = (x->C + 31) / 32;
   const int sh = (x->H + ps - 1) / ps, sw = (x->W + ps - 1) / ps;     // largest parity sub-lattice
   const int nstrips = (sw + 31) / 32;
@@ -1753,7 +1816,7 @@ static void launch_dw3_bwd_rows(const lhn_view* x, const float* w, const lhn_vie
   const int ntile = base * nch;
   const int grid = dw3_grid(ntile, cg, per_cu);       // one round of resident workgroups
   hipLaunchKernelGGL((k_dw3_bwd_rows<DIL, BNS>), dim3(grid), dim3(256), lds, s, *x, w, *y, *gy, dx, dx_acc, dw, nstrips, nch, CH, cg,
-                     nrep, rep_stride, ps, bs);
+                     nrep, rep_stride, ps, bs, fs);
 }
 // LHN_DW_BWD_V1=1 (read once): the 3x3 backward runs the 8 x 16 tile kernel k_dwk_bwd_lds instead of k_dw3_bwd_rows
 static bool lhn_dw_bwd_v1() {
@@ -2043,23 +2106,26 @@ int lhn_dwk_fwd_lds(const lhn_view* x, const float* w, const lhn_view* y, double
   return 1;
 }
 int lhn_dwk_bwd_lds(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc,
-                    float* dw, int k, int dil, int nrep, int64_t rep_stride, hipStream_t s, const DwBnSum* bs) {
+                    float* dw, int k, int dil, int nrep, int64_t rep_stride, hipStream_t s, const DwBnSum* bs,
+                    const lhn_bnbwdsrc* fs) {
+  // fs (the BatchNorm-backward finalize of y in the prologue): k_dw3_bwd_rows only -- dw_bwd_folds() is the callers' test
+  if (fs && (lhn_dw_bwd_v1() || k != 3)) return 0;
   if (bs && bs->sums) {        // fused BatchNorm-backward sums of the producer: the 3x3 / dilation 1 instance only
     if (!(k == 3 && dil == 1 && dx && !dx_acc)) return 0;
     if (lhn_dw_bwd_v1()) launch_dwk_bwd<3, 1, true>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs);
-    else launch_dw3_bwd_rows<1, true>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs);
+    else launch_dw3_bwd_rows<1, true>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs, fs);
     return 1;
   }
   const bool v1 = lhn_dw_bwd_v1();
   if (k == 3 && dil == 1) {
     if (v1) launch_dwk_bwd<3, 1>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs);
-    else launch_dw3_bwd_rows<1>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs);
+    else launch_dw3_bwd_rows<1>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs, fs);
   } else if (k == 3 && dil == 2 && x->W >= 16) {       // parity sub-lattices
     if (v1) launch_dwk_bwd<3, 1>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 2, bs);
-    else launch_dw3_bwd_rows<1>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 2, bs);
+    else launch_dw3_bwd_rows<1>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 2, bs, fs);
   } else if (k == 3 && dil == 2) {
     if (v1) launch_dwk_bwd<3, 2>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs);
-    else launch_dw3_bwd_rows<2>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs);
+    else launch_dw3_bwd_rows<2>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs, fs);
   } else if (k == 7 && dil == 1) launch_dwk_bwd<7, 1>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs);     // K = 7: tile kernel
   else return 0;
   return 1;
@@ -2089,6 +2155,19 @@ static int dw_bwd_addends(const lhn_view* x, const float* w, const lhn_view* y, 
   bs.add[0] = a0;
   bs.add[1] = a1;
   return lhn_dwk_bwd_lds(x, w, y, gy, dx, dx_acc, dw, k, dil, nrep, rep_stride, s, &bs);
+}
+
+static int dw_bwd_fin(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc, float* dw, int k,
+                      int dil, int nrep, int64_t rep_stride, const lhn_bnsum* bns, const float* a0, const float* a1, const lhn_bnbwdsrc* fin,
+                      hipStream_t s) {
+  DwBnSum bs;
+  bs.sums = bns ? bns->sums : nullptr;
+  bs.save = bns ? bns->save : nullptr;
+  bs.C = bns ? bns->C : 0;
+  bs.coff = bns ? bns->coff : 0;
+  bs.add[0] = a0;
+  bs.add[1] = a1;
+  return lhn_dwk_bwd_lds(x, w, y, gy, dx, dx_acc, dw, k, dil, nrep, rep_stride, s, &bs, fin);
 }
 
 static int dw_bwd_fused(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, float* dw, int k,

@@ -1042,7 +1042,7 @@ static int launch_pw_bwd(const lhn_view* x, const float* w, const lhn_view* y, c
 template <int CIN, int COUT, int PX, int PF, bool DYST, bool BNS, int OCC>
 __global__ void __launch_bounds__(256, OCC) k_pw_bwd_wr(lhn_view x, const float* __restrict__ w, lhn_view y, lhn_gradview gy,
                                                         float* __restrict__ dx, int dx_acc, float* __restrict__ dw, float* __restrict__ dbias,
-                                                        int M, int ntiles, int nrep, int64_t rep_stride, lhn_bnsum bs) {
+                                                        int M, int ntiles, int nrep, int64_t rep_stride, lhn_bnsum bs, lhn_bnbwdsrc fs) {
   constexpr int NTI = CIN / 32, NTO = COUT / 32, LDY = COUT + 4, LDX = CIN + 4;
   constexpr bool ONE = NTI == 1;                // 32 -> 32: the single dW tile is split over the waves by pixels, not by tiles
   constexpr int NDW = ONE ? 1 : NTO * NTI / 4;  // dW tiles per wave
@@ -1139,6 +1139,14 @@ __global__ void __launch_bounds__(256, OCC) k_pw_bwd_wr(lhn_view x, const float*
 
   int tile = blockIdx.x;
   if (tile < ntiles) issue(tile);     // the first tile's loads are in flight while the tables and W are fetched
+  // BatchNorm-backward finalize of y in the prologue (lhn_bnbwdsrc): the replica fold's loads go out behind the tile's, its 1,024
+  // group partials wait in dYs (16 KB; commit() writes it only after the barrier below) while the tables and W are fetched
+  static_assert(PX * LDY * sizeof(float) >= 2 * LHN_FIN_THREADS * sizeof(double), "dYs holds the replica fold's partials");
+  LhnBwdPre fpre;
+  if (fs.sums) {
+    fpre = lhn_bn_bwd_pre(fs, 0, COUT);
+    lhn_bn_bwd_fold_part_ct<COUT>(fs.sums, fs.stat_channels, reinterpret_cast<double*>(dYs));
+  }
   for (int i = tid; i < CIN; i += 256) {
     xt[i] = x.table ? x.table[x.coff + i] : 1.f;
     xt[CIN + i] = x.table ? x.table[x.cstride + x.coff + i] : 0.f;
@@ -1148,6 +1156,7 @@ __global__ void __launch_bounds__(256, OCC) k_pw_bwd_wr(lhn_view x, const float*
     yt[i] = y.table ? y.table[y.coff + i] : 1.f;
     yt[COUT + i] = y.table ? y.table[y.cstride + y.coff + i] : 0.f;
     yt[2 * COUT + i] = y.table ? y.table[2 * y.cstride + y.coff + i] : 1.f;
+    if (fs.sums) continue;            // A | B | C come out of the fold below
     cf[i] = gy.coef ? gy.coef[y.coff + i] : 1.f;
     cf[COUT + i] = gy.coef ? gy.coef[y.cstride + y.coff + i] : 0.f;
     cf[2 * COUT + i] = gy.coef ? gy.coef[2 * y.cstride + y.coff + i] : 0.f;
@@ -1178,6 +1187,13 @@ __global__ void __launch_bounds__(256, OCC) k_pw_bwd_wr(lhn_view x, const float*
   // (the flush address of this thread's channel, formed once)
   double* const bst = BNS ? bs.sums + (size_t)(blockIdx.x % LHN_STAT_REPLICAS) * 2 * bs.C + bs.coff + (tid & (CIN - 1)) : nullptr;
   const int bsC = BNS ? bs.C : 0;
+  if (fs.sums) {      // thread c: the groups in order, the coefficients into cf; workgroup 0 also leaves them (and dgamma, dbeta) in memory
+    __syncthreads();
+    if (tid < COUT)
+      lhn_bn_bwd_coef_put(lhn_bn_bwd_coef(reinterpret_cast<const double*>(dYs), COUT, LHN_FIN_THREADS / COUT, tid, fpre.gamma, fpre.mean,
+                                          fpre.inv, fs.count),
+                          fs, const_cast<float*>(gy.coef), y.cstride, y.coff, tid, cf, COUT, tid, blockIdx.x == 0);
+  }
   __syncthreads();
 
   for (; tile < ntiles; tile += gridDim.x) {
@@ -1330,8 +1346,10 @@ __global__ void __launch_bounds__(256, OCC) k_pw_bwd_wr(lhn_view x, const float*
 //   32 -> 32:   PX = 128, x, y and dz prefetched.
 template <int CIN, int COUT, int PX, int PF, bool DYST = true, bool BNS = false, int OCC = 2>
 static int launch_pw_bwd_wr(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc, float* dw,
-                            float* dbias, int nrep, int64_t rep_stride, hipStream_t s, const lhn_bnsum& bs) {
+                            float* dbias, int nrep, int64_t rep_stride, hipStream_t s, const lhn_bnsum& bs, const lhn_bnbwdsrc* fsp = nullptr) {
   const int M = y->N * y->H * y->W, ntiles = (M + PX - 1) / PX;
+  lhn_bnbwdsrc fs;
+  if (fsp) fs = *fsp; else memset(&fs, 0, sizeof(fs));
   const size_t lds = (size_t)(PX * (COUT + 4) + PX * (CIN + 4) + 3 * CIN + 6 * COUT + (BNS ? PX * CIN : 0)) * sizeof(float);
   static LhnKernelCfg cfg;
   int per_cu = 1;
@@ -1342,7 +1360,7 @@ static int launch_pw_bwd_wr(const lhn_view* x, const float* w, const lhn_view* y
   int grid = lhn_num_cus() * per_cu;
   if (grid > ntiles) grid = ntiles;
   hipLaunchKernelGGL((k_pw_bwd_wr<CIN, COUT, PX, PF, DYST, BNS, OCC>), dim3(grid), dim3(256), lds, s, *x, w, *y, *gy, dx, dx_acc, dw, dbias,
-                     M, ntiles, nrep, rep_stride, bs);
+                     M, ntiles, nrep, rep_stride, bs, fs);
   return 0;
 }
 
@@ -1377,7 +1395,15 @@ extern "C" int lhn_conv_pw_bwd2(const lhn_view* x, const float* w, const lhn_vie
 extern "C" int lhn_conv_pw_bwd3(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
                                 int dx_accumulate, float* dw, float* dbias, int stride, const float* dy_nchw, int nrep,
                                 int64_t rep_stride, const lhn_pw_opts* opts, const lhn_bnsum* bns, void* stream) {
+  return lhn_conv_pw_bwd4(x, w, y, gy, dx, dx_accumulate, dw, dbias, stride, dy_nchw, nrep, rep_stride, opts, bns, nullptr, stream);
+}
+// fin: the BatchNorm-backward finalize of y (lhn_bnbwdsrc).  The register-W instances fold it in their prologue; every other path gets
+// the separate launch from here, before its own first launch.
+extern "C" int lhn_conv_pw_bwd4(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
+                                int dx_accumulate, float* dw, float* dbias, int stride, const float* dy_nchw, int nrep,
+                                int64_t rep_stride, const lhn_pw_opts* opts, const lhn_bnsum* bns, const lhn_bnbwdsrc* fin, void* stream) {
   if (nrep < 1) nrep = 1;
+  if (fin && !fin->sums) fin = nullptr;
   lhn_bnsum bs;
   memset(&bs, 0, sizeof(bs));
   if (bns && bns->sums) {
@@ -1396,13 +1422,27 @@ extern "C" int lhn_conv_pw_bwd3(const lhn_view* x, const float* w, const lhn_vie
                 wrows, wcols, Cin, Cout);
   const int64_t bstride = (opts && opts->nchw_batch_stride > 0) ? opts->nchw_batch_stride : (int64_t)Cout * HoWo;
   hipStream_t s = (hipStream_t)stream;
+  const bool wr_wide = !bs.sums && stride == 1 && !dy_nchw && wcols == Cin && wrows == Cout && !pw_bwd_split_forced() && !pw_wr_off() &&
+                       ((Cin == 128 && Cout == 128) || (Cin == 64 && Cout == 128) || (Cin == 128 && Cout == 64));
+  const bool wr_narrow = stride == 1 && !dy_nchw && wcols == Cin && wrows == Cout && Cin == Cout && (Cin == 64 || Cin == 32) &&
+                         !pw_bwd_narrow_off() && !pw_wr_off();
+  if (fin) {
+    LHN_CHECK_ARG(!dy_nchw && gy->coef && fin->save_mean_invstd && fin->count > 0 && fin->stat_channels >= Cout,
+                  "lhn_conv_pw_bwd4: finalize source needs gy->coef, saved statistics and stat_channels >= Cout");
+    if (!wr_wide && !wr_narrow) {      // no in-prologue fold on this path: the separate launch, then as ever
+      const int rc = lhn_bn_bwd_finalize2(fin->sums, fin->gamma, fin->save_mean_invstd, const_cast<float*>(gy->coef), y->cstride, y->coff,
+                                          Cout, fin->stat_channels, fin->count, fin->dgamma, fin->dbeta, fin->pgrad_scale, stream);
+      if (rc) return rc;
+      fin = nullptr;
+    }
+  }
   // wide shapes with both sides <= 128: one register-W launch (decided here, before any launch; LHN_PW_BWD_SPLIT=1 and
   // LHN_PW_LDSW=1, which means "no register-W kernel", keep the split path)
-  if (!bs.sums && stride == 1 && !dy_nchw && wcols == Cin && wrows == Cout && !pw_bwd_split_forced() && !pw_wr_off()) {
+  if (wr_wide) {
     int rc = -1;
-    if (Cin == 128 && Cout == 128) rc = launch_pw_bwd_wr<128, 128, 32, 1>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs);
-    else if (Cin == 64 && Cout == 128) rc = launch_pw_bwd_wr<64, 128, 64, 1>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs);
-    else if (Cin == 128 && Cout == 64) rc = launch_pw_bwd_wr<128, 64, 64, 2>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs);
+    if (Cin == 128 && Cout == 128) rc = launch_pw_bwd_wr<128, 128, 32, 1>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs, fin);
+    else if (Cin == 64 && Cout == 128) rc = launch_pw_bwd_wr<64, 128, 64, 1>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs, fin);
+    else if (Cin == 128 && Cout == 64) rc = launch_pw_bwd_wr<128, 64, 64, 2>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs, fin);
     if (rc == 0) {
       LHN_CHECK_LAUNCH("lhn_conv_pw_bwd");
       return 0;
@@ -1413,12 +1453,12 @@ extern "C" int lhn_conv_pw_bwd3(const lhn_view* x, const float* w, const lhn_vie
   // LHN_PW_LDSW=1 keep k_pw_bwd; so do stride 2, the NCHW head and partial channel counts).  The BNS instances compile the
   // gate on x out: they rely on the `!x->gate` condition for sums checked at the top of this function -- if that check is
   // ever relaxed, gated sums calls must leave this branch
-  if (stride == 1 && !dy_nchw && wcols == Cin && wrows == Cout && Cin == Cout && (Cin == 64 || Cin == 32) && !pw_bwd_narrow_off() && !pw_wr_off()) {
+  if (wr_narrow) {
     int rc;
-    if (Cin == 64) rc = bs.sums ? launch_pw_bwd_wr<64, 64, 64, 2, false, true>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs)
-                                : launch_pw_bwd_wr<64, 64, 64, 2, false, false>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs);
-    else rc = bs.sums ? launch_pw_bwd_wr<32, 32, 128, 2, false, true>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs)
-                      : launch_pw_bwd_wr<32, 32, 128, 2, false, false, 3>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs);
+    if (Cin == 64) rc = bs.sums ? launch_pw_bwd_wr<64, 64, 64, 2, false, true>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs, fin)
+                                : launch_pw_bwd_wr<64, 64, 64, 2, false, false>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs, fin);
+    else rc = bs.sums ? launch_pw_bwd_wr<32, 32, 128, 2, false, true>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs, fin)
+                      : launch_pw_bwd_wr<32, 32, 128, 2, false, false, 3>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs, fin);
     if (rc) return rc;
     LHN_CHECK_LAUNCH("lhn_conv_pw_bwd");
     return 0;

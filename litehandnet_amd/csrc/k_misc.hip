@@ -16,8 +16,7 @@ static inline bool pow2i(int v) { return v > 0 && (v & (v - 1)) == 0; }
 // One workgroup of up to 1024 threads: thread (c, g) folds replicas g, g + G, ... of channel c (all of its loads in flight
 // together), the G partial sums of a channel meet in LDS in a fixed order (run-to-run reproducible), one thread per channel
 // does the arithmetic.  (The first version walked one thread per channel through 64 dependent double loads: 6 us per launch,
-// 52 launches per forward of the MSRB hourglass.)
-#define LHN_FIN_THREADS 1024
+// 52 launches per forward of the MSRB hourglass.)  LHN_FIN_THREADS = 1024: lhn_common.h.
 __global__ void __launch_bounds__(LHN_FIN_THREADS) k_bn_finalize(const double* __restrict__ stats, const float* __restrict__ gamma,
                               const float* __restrict__ beta, float* __restrict__ rmean, float* __restrict__ rvar,
                               int64_t* __restrict__ nbt, float* __restrict__ table, int cs, int coff, int C,
@@ -1128,37 +1127,19 @@ __global__ void __launch_bounds__(256) k_bn_bwd_reduce(lhn_view y, lhn_gradview 
 __global__ void __launch_bounds__(LHN_FIN_THREADS) k_bn_bwd_finalize(const double* __restrict__ sums, const float* __restrict__ gamma,
                                   const float* __restrict__ save, float* __restrict__ coef, int cs, int coff, int C,
                                   double count, float* __restrict__ dgamma, float* __restrict__ dbeta, float pgrad_scale, int SC) {
-  // replica fold as in k_bn_finalize
+  // replica fold as in k_bn_finalize, through the helpers the convolution backward prologues use (lhn_common.h): the launch has
+  // G * C threads (C < LHN_FIN_THREADS: one chunk) or LHN_FIN_THREADS with G = 1
   __shared__ double part[2 * LHN_FIN_THREADS];
-  const int nt = blockDim.x;
-  int G = nt / C;
-  G = G < 1 ? 1 : (G > LHN_STAT_REPLICAS ? LHN_STAT_REPLICAS : G);
+  const int nt = blockDim.x, G = lhn_fin_groups(C);
   for (int c0 = 0; c0 < C; c0 += nt) {
-    const int g = threadIdx.x / C, c = c0 + (G > 1 ? threadIdx.x - g * C : threadIdx.x);
+    const int nc = min(G > 1 ? C : nt, C - c0);
     if (c0) __syncthreads();
-    if (g < G && c < C) {
-      double s1 = 0, s2 = 0;
-#pragma unroll 4
-      for (int r = g; r < LHN_STAT_REPLICAS; r += G) {
-        s1 += sums[(size_t)r * 2 * SC + c];
-        s2 += sums[(size_t)r * 2 * SC + SC + c];
-      }
-      part[2 * threadIdx.x] = s1;
-      part[2 * threadIdx.x + 1] = s2;
-    }
+    lhn_bn_bwd_fold_part(sums, SC, c0, nc, G, part);
     __syncthreads();
-    if (g != 0 || c >= C) continue;
-    double db = 0, dg = 0;
-    for (int k = 0; k < G; ++k) {
-      db += part[2 * (k * C + threadIdx.x)];
-      dg += part[2 * (k * C + threadIdx.x) + 1];
-    }
-    const double mean = save[c], inv = save[SC + c], s = (double)(gamma ? gamma[c] : 1.f) * inv;
-    coef[coff + c] = (float)s;
-    coef[cs + coff + c] = (float)(-s * inv * dg / count);
-    coef[2 * cs + coff + c] = (float)(-s * db / count + s * inv * mean * dg / count);
-    if (dgamma) dgamma[c] += (float)dg * pgrad_scale;
-    if (dbeta) dbeta[c] += (float)db * pgrad_scale;
+    if ((int)threadIdx.x >= nc) continue;
+    const int c = c0 + threadIdx.x;
+    const LhnBwdCoef r = lhn_bn_bwd_coef(part, nc, G, threadIdx.x, gamma ? gamma[c] : 1.f, save[c], save[SC + c], count);
+    lhn_bn_bwd_coef_store(r, coef, cs, coff, c, dgamma, dbeta, pgrad_scale);
   }
 }
 

@@ -344,6 +344,148 @@ __device__ __forceinline__ void lhn_bn_bwd_finalize_block(const lhn_bnbwdfin& f,
     if (f.dbeta) f.dbeta[c] += (float)db;
   }
 }
+// ---- BatchNorm-backward finalize, shared by k_bn_bwd_finalize and the prologues of the convolution backward kernels that fold
+// their own channels (lhn_bnbwdsrc).  Replica order of the separate launch: G = clamp(LHN_FIN_THREADS / C_bn, 1, 32) groups, group
+// g adds replicas g, g + G, ... in turn, the groups are then added in the order 0 .. G-1; plain loads (the sums were completed by
+// an earlier launch).  Same sums in memory, same bits out, whoever calls.
+#define LHN_FIN_THREADS 1024
+__device__ __forceinline__ int lhn_fin_groups(int C_bn) {
+  const int G = LHN_FIN_THREADS / C_bn;
+  return G < 1 ? 1 : (G > LHN_STAT_REPLICAS ? LHN_STAT_REPLICAS : G);
+}
+// first half: the group partials of channels [c0, c0 + nc) into part[2 * (g * nc + cl)] (sum du), [.. + 1] (sum du * xhat);
+// part = 2 * G * nc doubles of LDS.  A barrier separates it from lhn_bn_bwd_coef.
+__device__ __forceinline__ void lhn_bn_bwd_fold_part(const double* __restrict__ sums, int SC, int c0, int nc, int G, double* part) {
+  for (int i = threadIdx.x; i < G * nc; i += blockDim.x) {
+    const int g = i / nc, c = c0 + (i - g * nc);
+    double s1 = 0, s2 = 0;
+#pragma unroll 4
+    for (int r = g; r < LHN_STAT_REPLICAS; r += G) {
+      s1 += sums[(size_t)r * 2 * SC + c];
+      s2 += sums[(size_t)r * 2 * SC + SC + c];
+    }
+    part[2 * i] = s1;
+    part[2 * i + 1] = s2;
+  }
+}
+// second half, one thread per channel cl of the nc: dy = A*du + B*y + C with  A = s, B = -s*invstd*dgamma/n,
+// C = -s*dbeta/n + s*invstd*mean*dgamma/n, s = gamma*invstd
+struct LhnBwdCoef {
+  float A, B, C;
+  double db, dg;      // sum du, sum du * xhat
+};
+__device__ __forceinline__ LhnBwdCoef lhn_bn_bwd_coef_of(double db, double dg, float gamma, float save_mean, float save_invstd, double count) {
+  LhnBwdCoef r;
+  const double mean = save_mean, inv = save_invstd, s = (double)gamma * inv;
+  r.A = (float)s;
+  r.B = (float)(-s * inv * dg / count);
+  r.C = (float)(-s * db / count + s * inv * mean * dg / count);
+  r.db = db;
+  r.dg = dg;
+  return r;
+}
+__device__ __forceinline__ LhnBwdCoef lhn_bn_bwd_coef(const double* part, int nc, int G, int cl, float gamma, float save_mean,
+                                                      float save_invstd, double count) {
+  double db = 0, dg = 0;
+  for (int k = 0; k < G; ++k) {
+    db += part[2 * (k * nc + cl)];
+    dg += part[2 * (k * nc + cl) + 1];
+  }
+  return lhn_bn_bwd_coef_of(db, dg, gamma, save_mean, save_invstd, count);
+}
+// what the finalize leaves in memory for BatchNorm channel c (coef at absolute channel coff + c of a [3][cs] table)
+__device__ __forceinline__ void lhn_bn_bwd_coef_store(const LhnBwdCoef& r, float* __restrict__ coef, int cs, int coff, int c,
+                                                      float* __restrict__ dgamma, float* __restrict__ dbeta, float pgrad_scale) {
+  coef[coff + c] = r.A;
+  coef[cs + coff + c] = r.B;
+  coef[2 * cs + coff + c] = r.C;
+  if (dgamma) dgamma[c] += (float)r.dg * pgrad_scale;
+  if (dbeta) dbeta[c] += (float)r.db * pgrad_scale;
+}
+// ---- the same inside a convolution backward prologue (256 threads, channels [c0, c0 + nc) of the BatchNorm of y).  A prologue is
+// memory latency end to end, so each thread issues ALL of its loads -- its share of the sums, and the gamma / mean / invstd of the
+// channel it finishes -- before the first add: one latency, where a loop over entries pays one per trip.
+struct LhnBwdPre {
+  float gamma, mean, inv;
+};
+__device__ __forceinline__ LhnBwdPre lhn_bn_bwd_pre(const lhn_bnbwdsrc& f, int c0, int nc) {
+  LhnBwdPre p;
+  const int c = c0 + min((int)threadIdx.x, nc - 1);
+  p.gamma = f.gamma ? f.gamma[c] : 1.f;
+  p.mean = f.save_mean_invstd[c];
+  p.inv = f.save_mean_invstd[f.stat_channels + c];
+  return p;
+}
+// first half, G and NC known at compile time with G * NC = 1,024 entries (the register-W 1x1: NC = COUT): group partials as
+// lhn_bn_bwd_fold_part leaves them, 32 * NC / 128 loads per thread in flight together
+template <int NC>
+__device__ __forceinline__ void lhn_bn_bwd_fold_part_ct(const double* __restrict__ sums, int SC, double* part) {
+  constexpr int G = LHN_FIN_THREADS / NC, NE = 4, NR = LHN_STAT_REPLICAS / G;
+  static_assert(G * NC == LHN_FIN_THREADS && G <= LHN_STAT_REPLICAS && G * NR == LHN_STAT_REPLICAS, "NC in {32, 64, 128}");
+  double a[NE][NR], b[NE][NR];
+#pragma unroll
+  for (int j = 0; j < NE; ++j) {
+    const int i = threadIdx.x + 256 * j, g = i / NC, c = i % NC;
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+      a[j][k] = sums[(size_t)(g + k * G) * 2 * SC + c];
+      b[j][k] = sums[(size_t)(g + k * G) * 2 * SC + SC + c];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NE; ++j) {
+    double s1 = 0, s2 = 0;
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+      s1 += a[j][k];
+      s2 += b[j][k];
+    }
+    part[2 * (threadIdx.x + 256 * j)] = s1;
+    part[2 * (threadIdx.x + 256 * j) + 1] = s2;
+  }
+}
+// first half for nc <= 32 channels and any C_bn (the depthwise rows kernel): the 32 * nc (sum du, sum du * xhat) pairs go to LDS as
+// they are, raw[2 * (r * nc + cl)] (512 * nc bytes), at most 4 pairs per thread
+__device__ __forceinline__ void lhn_bn_bwd_fold_raw(const double* __restrict__ sums, int SC, int c0, int nc, double* raw) {
+  double a[4], b[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int p = min((int)threadIdx.x + 256 * q, LHN_STAT_REPLICAS * nc - 1), r = p / nc, cl = p - r * nc;
+    a[q] = sums[(size_t)r * 2 * SC + c0 + cl];
+    b[q] = sums[(size_t)r * 2 * SC + SC + c0 + cl];
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int p = threadIdx.x + 256 * q;
+    if (p < LHN_STAT_REPLICAS * nc) {
+      raw[2 * p] = a[q];
+      raw[2 * p + 1] = b[q];
+    }
+  }
+}
+// ... and its second half: thread cl adds the replicas of its channel in the finalize's order (groups of C_bn, then the groups)
+__device__ __forceinline__ LhnBwdCoef lhn_bn_bwd_coef_raw(const double* raw, int nc, int G, int cl, const LhnBwdPre& p, double count) {
+  double db = 0, dg = 0;
+  for (int g = 0; g < G; ++g) {
+    double s1 = 0, s2 = 0;
+    for (int r = g; r < LHN_STAT_REPLICAS; r += G) {
+      s1 += raw[2 * (r * nc + cl)];
+      s2 += raw[2 * (r * nc + cl) + 1];
+    }
+    db += s1;
+    dg += s2;
+  }
+  return lhn_bn_bwd_coef_of(db, dg, p.gamma, p.mean, p.inv, count);
+}
+// the LDS slots A | B | C of channel cl (cfA[cl], cfA[ld + cl], cfA[2 * ld + cl]); `lead` (block-uniform): this workgroup also
+// writes memory.  No barrier here: the caller's next one publishes the slots (and frees the fold's scratch).
+__device__ __forceinline__ void lhn_bn_bwd_coef_put(const LhnBwdCoef& r, const lhn_bnbwdsrc& f, float* __restrict__ coef, int cs, int coff,
+                                                    int c, float* cfA, int ld, int cl, bool lead) {
+  cfA[cl] = r.A;
+  cfA[ld + cl] = r.B;
+  cfA[2 * ld + cl] = r.C;
+  if (lead) lhn_bn_bwd_coef_store(r, coef, cs, coff, c, f.dgamma, f.dbeta, f.pgrad_scale);
+}
 static __device__ __forceinline__ lhn_bnfin lhn_nofin() {
   lhn_bnfin f;
   f.counter = nullptr;

@@ -120,6 +120,20 @@ static bool fuse_finalize() {
   }
   return v == 1;
 }
+// LHN_BWD_FIN_CONSUMER (default 1, read once; 0 = the separate launches, for A/B runs): a BN_BWD op that stands directly in front of
+// the backward of the convolution that owns the BatchNorm does not launch k_bn_bwd_finalize; the finished sums go to that
+// convolution's entry point (lhn_bnbwdsrc: lhn_conv_dw_bwd4 / lhn_conv_pw_bwd4), whose kernel folds them in its prologue -- the
+// coefficients have no other reader.  Unlike the producer-side fusion above this takes a launch AND its boundary out of the
+// dependent chain, without tickets: the kernel boundary in front of the convolution orders the sums' atomics.  Whole-plan runs
+// only, no padded channels; the op lists do not change.  Variant B: 50 of 52 pairs.
+static bool bwd_fin_consumer() {
+  static int v = -1;
+  if (v < 0) {
+    const char* e = getenv("LHN_BWD_FIN_CONSUMER");
+    v = (e && e[0] == '0') ? 0 : 1;
+  }
+  return v == 1;
+}
 // creal: channels the BatchNorm really has when the convolution's output view is padded to a multiple of 4 (f.C then is the
 // layout of the statistics); repeat: the reference evaluates some units twice per forward (lite_hrnet.py:192-197), which
 // moves their running statistics twice -- the table is the same both times.
@@ -180,6 +194,8 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
   hipStream_t s = static_cast<hipStream_t>(stream);
   int rc = 0;
   const bool whole = (sb == 0 && se >= 2 * ops.size());
+  lhn_bnbwdsrc cfin;                    // finalize source of the BN_BWD op in front of op cfin_for (consumer-side finalize)
+  size_t cfin_for = (size_t)-1;
   for (size_t oi = 0; oi < ops.size() && rc == 0; ++oi) {
     const lhn_op& o = ops[oi];
     const bool deferred = false;      // (round 2's deferred finalize is gone)
@@ -494,8 +510,9 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
           po.nchw_batch_stride = (int64_t)o.i[7] * khw;
         }
         const lhn_bnsum bs = mkbns(ws, o.ws[0], o.ws[1], (int)o.f[6], (int)o.f[7]);      // ws[0..1], f[6..7]: the input's producer
-        rc = lhn_conv_pw_bwd3(&x, prm<const float>(params, o.p[0]), &y, &g, dx, o.i[2] == 2, prm<float>(grads, o.p[1]),
-                              prm<float>(grads, o.p[2]), o.i[0], nchw, nrep, rstr, &po, bs.sums ? &bs : nullptr, stream);
+        rc = lhn_conv_pw_bwd4(&x, prm<const float>(params, o.p[0]), &y, &g, dx, o.i[2] == 2, prm<float>(grads, o.p[1]),
+                              prm<float>(grads, o.p[2]), o.i[0], nchw, nrep, rstr, &po, bs.sums ? &bs : nullptr,
+                              cfin_for == oi ? &cfin : nullptr, stream);
         break;
       }
       case OP_DW_BWD: {
@@ -506,6 +523,15 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
         // ws[4], ws[5] >= 0: BatchNorm-backward sums / saved statistics of the convolution that produced x, i[6] its channel
         // count, i[7] the producer channel of x's first channel (see lhn_conv_dw_bwd2)
         // ws[2], ws[3] >= 0: gradients of residual sums that read x, added to the stored dx (lhn_conv_dw_bwd3)
+        if (cfin_for == oi) {          // the BatchNorm-backward finalize of y rides in this launch (see bwd_fin_consumer)
+          const bool adds = o.ws[2] >= 0 || o.ws[3] >= 0;
+          const lhn_bnsum bs = mkbns(ws, adds ? -1 : o.ws[4], adds ? -1 : o.ws[5], o.i[6], o.i[7]);
+          rc = lhn_conv_dw_bwd4(&x, prm<const float>(params, o.p[0]), &y, &g, dx, o.i[4] == 2, prm<float>(grads, o.p[1]), o.i[0], o.i[1],
+                                o.i[2], o.i[3], nrep, rstr, bs.sums ? &bs : nullptr,
+                                o.ws[2] >= 0 ? reinterpret_cast<const float*>(at(ws, o.ws[2])) : nullptr,
+                                o.ws[3] >= 0 ? reinterpret_cast<const float*>(at(ws, o.ws[3])) : nullptr, &cfin, stream);
+          break;
+        }
         if (o.ws[2] >= 0 || o.ws[3] >= 0) {
           rc = lhn_conv_dw_bwd3(&x, prm<const float>(params, o.p[0]), &y, &g, dx, o.i[4] == 2, prm<float>(grads, o.p[1]), o.i[0], o.i[1],
                                 o.i[2], o.i[3], nrep, rstr, o.ws[2] >= 0 ? reinterpret_cast<const float*>(at(ws, o.ws[2])) : nullptr,
@@ -544,7 +570,21 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
           rc = lhn_bn_bwd_reduce(&y, &g, save, sums, &fin, stream);
         } else {
           if (h0 && !o.i[1]) rc = lhn_bn_bwd_reduce(&y, &g, save, sums, nullptr, stream);      // i[1]: sums come from the reader's backward
-          if (!rc && h1)
+          // consumer-side finalize: the next op is the backward of the convolution that owns this BatchNorm and reads coef
+          const lhn_op* nx = oi + 1 < ops.size() ? &ops[oi + 1] : nullptr;
+          if (!rc && h1 && whole && bwd_fin_consumer() && !fuse_finalize() && o.i[0] == 0 && nx &&
+              (nx->kind == OP_DW_BWD || (nx->kind == OP_PW_BWD && !nx->i[1])) && nx->out_buf == o.out_buf && nx->out_coff == o.out_coff &&
+              nx->out_C == o.out_C && nx->i[5] != 0) {
+            cfin.sums = sums;
+            cfin.save_mean_invstd = save;
+            cfin.gamma = fin.gamma;
+            cfin.dgamma = fin.dgamma;
+            cfin.dbeta = fin.dbeta;
+            cfin.count = fin.count;
+            cfin.pgrad_scale = pscale;
+            cfin.stat_channels = o.out_C;
+            cfin_for = oi + 1;
+          } else if (!rc && h1)
             rc = lhn_bn_bwd_finalize2(sums, fin.gamma, save, fin.coef, b.C, o.out_coff, o.i[0] > 0 ? o.i[0] : o.out_C, o.out_C, fin.count,
                                       fin.dgamma, fin.dbeta, pscale, stream);      // i[0]: real channels of a padded output
         }
