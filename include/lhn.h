@@ -528,6 +528,26 @@ int lhn_gate_bwd_reduce2(const lhn_view* y, const float* dz, float* dgate /*[3][
 /* prezeroed != 0: dgate (and tsum) are already zero (the caller zeroes many such buffers with one memset) */
 int lhn_gate_bwd_reduce3(const lhn_view* y, const float* dz, float* dgate, float* tsum, const lhn_bn_slices* slices, int prezeroed,
                          void* stream);
+/* Gate-gradient sums of x's buffer from the backward of the heatmap head (litehourglass.py:159-166: the 128 -> 21 head is the only
+ * reader of neck[1]'s gated buffer; common.py:40-66 is the attention whose gate it is).  The head's backward forms the complete dz
+ * of that buffer (= its dx) in registers and holds the raw x for dW anyway, and dgate, T0, T1 are linear in dz -- so it adds, per
+ * (image n, channel c of the buffer), with u = scale*raw + shift:
+ *   dgate[n][c] += dx * act(u),   T0[n][c] += dx * act'(u),   T1[n][c] += dx * act'(u) * (raw - mean_c) * invstd_c
+ * which is what lhn_gate_bwd_reduce3 leaves (same layout: dgate[N][cstride], tsum = dgate + N*cstride as [N][2][cstride], channels at
+ * their index in the buffer; mean | invstd by the lhn_bn_slices rule, channels outside every slice use 0 and 1).  The buffers must be
+ * zero before the call (the plan keeps them in the arena its backward zeroes).  The sums are those of the buffer only when this call's
+ * dx is its whole gradient (no other reader); dx must be STORED: gs with dx_accumulate != 0 is refused.
+ * lhn_conv_pw_bwd5 = lhn_conv_pw_bwd4 + gs (NULL: no sums).  The streaming head kernel (k_head_bwd: Cin = 128 whole weight rows,
+ * Cout <= 32, stride 1, dy_nchw, H*W % 64 == 0) adds them in its own launch; for every other shape, under LHN_HEAD_STREAM=0 and in
+ * deterministic mode the call runs the present kernels and then the lhn_gate_bwd_reduce3 launch itself (x must then be the whole
+ * buffer): the result never depends on the kernel chosen. */
+typedef struct lhn_gatesum {
+  float*               dgate;    /* [3][N][cstride]: dgate | T0,T1 interleaved per image as [N][2][cstride] */
+  const lhn_bn_slices* slices;   /* saved statistics of the buffer's BatchNorm slices (sums unused), or NULL */
+} lhn_gatesum;
+int lhn_conv_pw_bwd5(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate,
+                     float* dw, float* dbias, int stride, const float* dy_nchw, int nrep, int64_t rep_stride,
+                     const lhn_pw_opts* opts, const lhn_bnsum* bns, const lhn_bnbwdsrc* fin, const lhn_gatesum* gs, void* stream);
 int lhn_avgpool_fwd3(const lhn_view* x, float* out /*[N,OH,OW,C]*/, int OH, int OW, float* pstat /*[N*OH*OW][2][C] or NULL*/,
                      const lhn_bn_slices* slices, void* stream);
 int lhn_ca_mlp_bwd2(const float* pooled, const float* w3, const float* gamma, const float* w1, const float* w2,
@@ -591,6 +611,10 @@ typedef struct lhn_buf {
 
 void* lhn_plan_create(const lhn_buf* bufs, int nbufs, const lhn_op* fwd, int nfwd, const lhn_op* bwd, int nbwd);
 void  lhn_plan_destroy(void* plan);
+/* Index of the backward op (a GATE_REDUCE) that a whole-plan run does NOT launch because the head's backward in front of it adds the
+ * same sums (lhn_gatesum: the op before it is the backward of an NCHW 1x1 that stores the gradient of the whole gated buffer), or -1:
+ * no such pair, LHN_HEAD_STREAM=0, or deterministic mode.  The op lists themselves are the same either way. */
+int   lhn_plan_head_gate_fold(void* plan);
 /* io: phase 0 {image NCHW, heatmap NCHW out}; phase 1 {image NCHW, d(heatmap) NCHW}.
  * training: a bit set -- bit 0 = train-mode BatchNorm (batch statistics, running statistics updated); bit 1 (LHN_RUN_TABLES_CURRENT,
  * eval only) = the workspace's per-buffer BatchNorm tables were built by an earlier eval run of THIS plan and no parameter

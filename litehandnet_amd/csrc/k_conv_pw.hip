@@ -534,6 +534,13 @@ int lhn_pw_dgrad_wr(const lhn_view* dyv, const float* w, const lhn_view* dxv, in
   return pw_fwd_wr(dyv, w, nullptr, dxv, nullptr, dxv->C, s, nullptr, g, 1);
 }
 
+// the streaming kernels of the heatmap head (k_conv_head.hip)
+constexpr int HEAD_CIN = 128;
+bool lhn_head_stream_on();
+int lhn_head_fwd(const lhn_view* x, const float* w, const float* bias, float* y_nchw, int cout, int HoWo, int64_t bstride, hipStream_t s);
+int lhn_head_bwd(const lhn_view* x, const float* w, const float* dy, float* dx, int dx_acc, float* dw, float* dbias, int cout, int HoWo,
+                 int64_t bstride, int nrep, int64_t rep_stride, const lhn_gatesum* gs, hipStream_t s);
+
 // smallest tile width (16/32/64/128) that holds `c` input channels; 0 = none
 static inline int pw_cin_tile(int c) { return c <= 16 ? 16 : c <= 32 ? 32 : c <= 64 ? 64 : c <= 128 ? 128 : 0; }
 
@@ -591,6 +598,16 @@ extern "C" int lhn_conv_pw_fwd2(const lhn_view* x, const float* w, const float* 
   ex.sum_out = nullptr;
   ex.so_cstride = ex.so_coff = 0;
   LHN_CHECK_ARG(lhn_no_pend(x), "lhn_conv_pw_fwd: lhn_view.pend is reserved (NULL)");
+  // the heatmap head (128 -> <= 32 features, NCHW, bias, no statistics, one source) on its streaming kernel (k_conv_head.hip);
+  // LHN_HEAD_STREAM=0, LHN_PW_LDSW=1 ("no register-W kernel") and every other NCHW shape (H's stacked 256 -> 21, padded heads,
+  // K slices) keep k_pw_fwd below
+  if (y_nchw && lhn_head_stream_on() && !pw_wr_off() && stride == 1 && Cin == HEAD_CIN && wcols == Cin && Cout <= 32 && wrows == Cout && !(opts && (opts->n_extra > 0 || opts->sum_out)) &&
+      bstride % 4 == 0 && ((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(y_nchw)) & 15) == 0) {
+    const int rc = lhn_head_fwd(x, w, bias, y_nchw, Cout, HoWo, bstride, s);
+    if (rc) return rc;
+    LHN_CHECK_LAUNCH("lhn_conv_pw_fwd");
+    return 0;
+  }
   if (opts && opts->n_extra > 0) {
     LHN_CHECK_ARG(opts->n_extra <= 2 && opts->extra && single && stride == 1, "lhn_conv_pw_fwd: extra sources need stride 1 and <= 128 channels");
     ex.n = opts->n_extra;
@@ -1402,6 +1419,32 @@ extern "C" int lhn_conv_pw_bwd3(const lhn_view* x, const float* w, const lhn_vie
 extern "C" int lhn_conv_pw_bwd4(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
                                 int dx_accumulate, float* dw, float* dbias, int stride, const float* dy_nchw, int nrep,
                                 int64_t rep_stride, const lhn_pw_opts* opts, const lhn_bnsum* bns, const lhn_bnbwdsrc* fin, void* stream) {
+  return lhn_conv_pw_bwd5(x, w, y, gy, dx, dx_accumulate, dw, dbias, stride, dy_nchw, nrep, rep_stride, opts, bns, fin, nullptr, stream);
+}
+static int pw_bwd_run(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate, float* dw,
+                      float* dbias, int stride, const float* dy_nchw, int nrep, int64_t rep_stride, const lhn_pw_opts* opts,
+                      const lhn_bnsum* bns, const lhn_bnbwdsrc* fin, const lhn_gatesum* gs, bool* gs_done, void* stream);
+// gs: gate-gradient sums of x's buffer (lhn_gatesum).  The streaming head kernel adds them in its launch; any other kernel is
+// followed by the lhn_gate_bwd_reduce3 launch over (x, dx) from here, so the caller finds the same sums whichever kernel ran.
+extern "C" int lhn_conv_pw_bwd5(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
+                                int dx_accumulate, float* dw, float* dbias, int stride, const float* dy_nchw, int nrep,
+                                int64_t rep_stride, const lhn_pw_opts* opts, const lhn_bnsum* bns, const lhn_bnbwdsrc* fin,
+                                const lhn_gatesum* gs, void* stream) {
+  if (gs && !gs->dgate) gs = nullptr;
+  // (dx accumulated: the head kernel would sum this call's part of dx, the reduce launch the whole buffer -- refused, so the
+  // result cannot depend on the route; the executor only ever passes the stored mode)
+  if (gs) LHN_CHECK_ARG(lhn_view_ok(x) && dx && !dx_accumulate && stride == 1 && (!gs->slices || (gs->slices->n >= 0 && gs->slices->n <= 2)),
+                        "lhn_conv_pw_bwd5: gate sums need a stored dx (no accumulate), stride 1 and 0..2 BatchNorm slices");
+  bool gs_done = false;
+  const int rc = pw_bwd_run(x, w, y, gy, dx, dx_accumulate, dw, dbias, stride, dy_nchw, nrep, rep_stride, opts, bns, fin, gs, &gs_done, stream);
+  if (rc || !gs || gs_done) return rc;
+  lhn_view xv = *x;
+  xv.gate = nullptr;
+  return lhn_gate_bwd_reduce3(&xv, dx, gs->dgate, gs->dgate + (size_t)x->N * x->cstride, gs->slices, 1, stream);
+}
+static int pw_bwd_run(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate, float* dw,
+                      float* dbias, int stride, const float* dy_nchw, int nrep, int64_t rep_stride, const lhn_pw_opts* opts,
+                      const lhn_bnsum* bns, const lhn_bnbwdsrc* fin, const lhn_gatesum* gs, bool* gs_done, void* stream) {
   if (nrep < 1) nrep = 1;
   if (fin && !fin->sums) fin = nullptr;
   lhn_bnsum bs;
@@ -1426,6 +1469,18 @@ extern "C" int lhn_conv_pw_bwd4(const lhn_view* x, const float* w, const lhn_vie
                        ((Cin == 128 && Cout == 128) || (Cin == 64 && Cout == 128) || (Cin == 128 && Cout == 64));
   const bool wr_narrow = stride == 1 && !dy_nchw && wcols == Cin && wrows == Cout && Cin == Cout && (Cin == 64 || Cin == 32) &&
                          !pw_bwd_narrow_off() && !pw_wr_off();
+  // the heatmap head (128 -> <= 32 features from NCHW planes) on its streaming kernel: dx, dW, dbias and the gate sums of x's buffer
+  // in ONE launch (k_conv_head.hip).  Not under LHN_HEAD_STREAM=0 or LHN_PW_LDSW=1.  Gate sums only where a tile stays inside an image, and not in
+  // deterministic mode: an image's sums have several writers there (dW and dbias have one writer per replica: at most 4 workgroups).
+  if (dy_nchw && lhn_head_stream_on() && !pw_wr_off() && stride == 1 && !bs.sums && !fin && Cin == HEAD_CIN && wcols == Cin && Cout <= 32 && wrows == Cout &&
+      HoWo % 4 == 0 && bstride % 4 == 0 && (!gs || (HoWo % 64 == 0 && !lhn_deterministic_mode())) &&
+      ((reinterpret_cast<uintptr_t>(dy_nchw) | reinterpret_cast<uintptr_t>(x->data)) & 15) == 0) {
+    const int rc = lhn_head_bwd(x, w, dy_nchw, dx, dx_accumulate, dw, dbias, Cout, HoWo, bstride, nrep, rep_stride, gs, s);
+    if (rc) return rc;
+    LHN_CHECK_LAUNCH("lhn_conv_pw_bwd");
+    *gs_done = gs != nullptr;
+    return 0;
+  }
   if (fin) {
     LHN_CHECK_ARG(!dy_nchw && gy->coef && fin->save_mean_invstd && fin->count > 0 && fin->stat_channels >= Cout,
                   "lhn_conv_pw_bwd4: finalize source needs gy->coef, saved statistics and stat_channels >= Cout");

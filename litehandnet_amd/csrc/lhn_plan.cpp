@@ -134,6 +134,24 @@ static bool bwd_fin_consumer() {
   }
   return v == 1;
 }
+// Gate-gradient sums in the head's backward (lhn_gatesum, LHN_HEAD_STREAM, default on; not in deterministic mode): when the backward
+// of an NCHW 1x1 (stride 1) STORES the gradient of its whole input buffer and the next op is the GATE_REDUCE of that buffer with
+// T0 | T1, the 1x1 is the buffer's only reader -- any other reader's backward would stand between the two and accumulate -- and its
+// dx is the buffer's complete dz.  lhn_conv_pw_bwd5 then adds dgate | T0 | T1 (in the head kernel's launch where it serves the shape,
+// else by the same lhn_gate_bwd_reduce3 launch) and the GATE_REDUCE op is not launched.  CA_MLP_BWD reads the same arena.  Like the
+// consumer-side finalize above this is decided here and not in the plan compiler: the op lists do not change.  Whole-plan runs only.
+// Variant B: the pass over neck[1]'s buffer, 8 -> 7 k_gate_bwd_reduce launches per step.
+bool lhn_head_stream_on();
+static bool head_gate_fold_at(const Plan* P, const std::vector<lhn_op>& ops, size_t oi) {
+  if (!lhn_head_stream_on() || lhn_deterministic_mode() || oi + 1 >= ops.size()) return false;
+  const lhn_op &o = ops[oi], &nx = ops[oi + 1];
+  if (o.kind != OP_PW_BWD || !o.i[1] || o.i[0] != 1 || o.i[2] != 1 || o.in_buf[0] < 0) return false;
+  if (o.in_C[0] != 128 || o.out_C > 32 || o.i[3] || o.i[4]) return false;      // the shapes k_head_bwd serves: every other head keeps its GATE_REDUCE op
+  const lhn_buf& b = P->bufs[o.in_buf[0]];
+  return o.in_coff[0] == 0 && o.in_C[0] == b.C && b.gate_off >= 0 && nx.kind == OP_GATE_REDUCE && nx.out_buf == o.in_buf[0] &&
+         nx.out_coff == 0 && nx.out_C == b.C && nx.ws[3] >= 0 && nx.ws[4] >= 0;
+}
+
 // creal: channels the BatchNorm really has when the convolution's output view is padded to a multiple of 4 (f.C then is the
 // layout of the statistics); repeat: the reference evaluates some units twice per forward (lite_hrnet.py:192-197), which
 // moves their running statistics twice -- the table is the same both times.
@@ -170,6 +188,14 @@ void* lhn_plan_create(const lhn_buf* bufs, int nbufs, const lhn_op* fwd, int nfw
   return p;
 }
 
+int lhn_plan_head_gate_fold(void* plan) {
+  const Plan* p = static_cast<const Plan*>(plan);
+  if (!p) return -1;
+  for (size_t oi = 0; oi + 1 < p->bwd.size(); ++oi)
+    if (head_gate_fold_at(p, p->bwd, oi)) return (int)oi + 1;
+  return -1;
+}
+
 void lhn_plan_destroy(void* plan) {
   Plan* p = static_cast<Plan*>(plan);
   if (!p) return;
@@ -196,6 +222,7 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
   const bool whole = (sb == 0 && se >= 2 * ops.size());
   lhn_bnbwdsrc cfin;                    // finalize source of the BN_BWD op in front of op cfin_for (consumer-side finalize)
   size_t cfin_for = (size_t)-1;
+  size_t gfold_at = (size_t)-1;         // the GATE_REDUCE op whose sums the head's backward in front of it added (head_gate_fold_at)
   for (size_t oi = 0; oi < ops.size() && rc == 0; ++oi) {
     const lhn_op& o = ops[oi];
     const bool deferred = false;      // (round 2's deferred finalize is gone)
@@ -510,9 +537,19 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
           po.nchw_batch_stride = (int64_t)o.i[7] * khw;
         }
         const lhn_bnsum bs = mkbns(ws, o.ws[0], o.ws[1], (int)o.f[6], (int)o.f[7]);      // ws[0..1], f[6..7]: the input's producer
-        rc = lhn_conv_pw_bwd4(&x, prm<const float>(params, o.p[0]), &y, &g, dx, o.i[2] == 2, prm<float>(grads, o.p[1]),
+        lhn_gatesum gsum;               // the next op's gate-gradient sums ride in this call (see head_gate_fold_at)
+        lhn_bn_slices gsl;
+        memset(&gsum, 0, sizeof(gsum));
+        if (phase == 1 && whole && head_gate_fold_at(P, ops, oi)) {
+          const lhn_op& nx = ops[oi + 1];
+          gsl = mkslices(ws, &nx.i[0], &nx.ws[5], nullptr);
+          gsum.dgate = reinterpret_cast<float*>(at(ws, nx.ws[3]));
+          gsum.slices = &gsl;
+          gfold_at = oi + 1;
+        }
+        rc = lhn_conv_pw_bwd5(&x, prm<const float>(params, o.p[0]), &y, &g, dx, o.i[2] == 2, prm<float>(grads, o.p[1]),
                               prm<float>(grads, o.p[2]), o.i[0], nchw, nrep, rstr, &po, bs.sums ? &bs : nullptr,
-                              cfin_for == oi ? &cfin : nullptr, stream);
+                              cfin_for == oi ? &cfin : nullptr, gsum.dgate ? &gsum : nullptr, stream);
         break;
       }
       case OP_DW_BWD: {
@@ -664,6 +701,7 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
         break;
       }
       case OP_GATE_REDUCE: {
+        if (gfold_at == oi) break;      // dgate | T0 | T1 are in the arena already
         lhn_view y = mkview(P, ws, o.out_buf, o.out_coff, o.out_C, false);
         float* dg = reinterpret_cast<float*>(at(ws, o.ws[3]));
         const lhn_bn_slices sl = mkslices(ws, &o.i[0], &o.ws[5], nullptr);
