@@ -368,6 +368,7 @@ int lhn_ew_fwd2(const lhn_view* srcs, int nsrc, const float* coef, const lhn_vie
 int lhn_ew_fwd3(const lhn_view* srcs, int nsrc, const float* coef, const lhn_view* dst, float out_slope, int mode, void* stream);
 int lhn_ew_mul_bwd(const lhn_view* src, const lhn_view* other, const lhn_view* dst, const float* ddst, float* dsrc,
                    int accumulate, void* stream);
+/* out_slope: a leaky slope (its derivative is read from the stored dst); LHN_SLOPE_SILU / LHN_SLOPE_RELU_SIGMOID are refused */
 int lhn_bilinear_bwd(const lhn_view* src, const lhn_view* dst, const float* ddst, float* dsrc, int accumulate, float out_slope,
                      void* stream);
 /* channel_shuffle(torch.cat([a, b], 1), groups = 2) (lite_hrnet.py:29-52,141-142,246-247): dst[2j] = value(a)[j],
@@ -490,6 +491,7 @@ int lhn_ew_bwd3(const lhn_view* src, const lhn_view* dst, const float* ddst, con
  * lhn_bnsum pointers or NULL */
 int lhn_ew_bwd_multi(const lhn_view* srcs, int nsrc, const lhn_view* dst, const float* ddst, const float* dst_dpool, float out_slope,
                      float* const* dsrcs, const int* accumulate, const lhn_bnsum* const* bns, void* stream);
+/* 1 <= OH <= x.H and 1 <= OW <= x.W (the kernel visits the bins floor(h*OH/H) +- 1); out_cstride and out_coff are multiples of 4 */
 int lhn_avgpool_bwd3(const lhn_view* x, const float* dout, int OH, int OW, int out_cstride, int out_coff, float* dx,
                      int dx_accumulate, const lhn_bnsum* bns, void* stream);
 int lhn_conv_pw_bwd3(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate,

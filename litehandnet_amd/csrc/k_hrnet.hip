@@ -211,6 +211,8 @@ int lhn_bilinear_bwd(const lhn_view* src, const lhn_view* dst, const float* ddst
   LHN_CHECK_ARG(lhn_view_ok(src) && lhn_view_ok(dst) && ddst && dsrc && src->C == dst->C && src->C <= 1024 && lhn_no_pend(src),
                 "lhn_bilinear_bwd: bad args");
   LHN_CHECK_ARG(src->H <= dst->H && src->W <= dst->W, "lhn_bilinear_bwd: the source must not be larger than the destination");
+  LHN_CHECK_ARG(out_slope != LHN_SLOPE_SILU && out_slope != LHN_SLOPE_RELU_SIGMOID,
+                "lhn_bilinear_bwd: SiLU / ReLU-sigmoid need a single same-size source (lhn_ew_bwd3)");
   hipLaunchKernelGGL(k_bilinear_bwd, dim3(grid_cap((int64_t)src->N * src->H, 8)), dim3(256), 0, (hipStream_t)stream, *src, *dst, ddst,
                      dsrc, accumulate, out_slope);
   LHN_CHECK_LAUNCH("lhn_bilinear_bwd");

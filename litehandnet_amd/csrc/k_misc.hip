@@ -1250,12 +1250,18 @@ int lhn_ew_fwd3(const lhn_view* srcs, int nsrc, const float* coef, const lhn_vie
 int lhn_ew_bwd(const lhn_view* srcs, int nsrc, const lhn_view* dst, const float* ddst, float out_slope,
                float* const* dsrcs, const int* accumulate, void* stream) {
   LHN_CHECK_ARG(srcs && nsrc >= 1 && nsrc <= 3 && lhn_view_ok(dst) && ddst && dsrcs && accumulate, "lhn_ew_bwd: bad args");
-  for (int i = 0; i < nsrc; ++i) {
+  for (int i = 0; i < nsrc; ++i) {      // every source is checked before the first launch: a refused call writes nothing
     if (!dsrcs[i]) continue;
     const lhn_view* s = &srcs[i];
     LHN_CHECK_ARG(lhn_view_ok(s) && s->C == dst->C, "lhn_ew_bwd: source %d mismatch", i);
     LHN_CHECK_ARG(dst->H % s->H == 0 && dst->W % s->W == 0, "lhn_ew_bwd: non-integer upsample %dx%d -> %dx%d", s->H, s->W, dst->H, dst->W);
     LHN_CHECK_ARG(s->C % 4 == 0 && s->C <= 1024, "lhn_ew_bwd: C=%d", s->C);
+    LHN_CHECK_ARG((out_slope != LHN_SLOPE_SILU && out_slope != LHN_SLOPE_RELU_SIGMOID) || (dst->H == s->H && dst->W == s->W),
+                  "lhn_ew_bwd: SiLU / ReLU-sigmoid need a single same-size source (source %d)", i);
+  }
+  for (int i = 0; i < nsrc; ++i) {
+    if (!dsrcs[i]) continue;
+    const lhn_view* s = &srcs[i];
     lhn_bnsum nob;
     memset(&nob, 0, sizeof(nob));
     hipLaunchKernelGGL(k_ew_bwd_src, dim3(grid_cap((int64_t)s->N * s->H, 8)), dim3(256), 0, (hipStream_t)stream, *s, *dst, ddst,
@@ -1431,6 +1437,10 @@ int lhn_avgpool_bwd2(const lhn_view* x, const float* dout, int OH, int OW, int o
 int lhn_avgpool_bwd3(const lhn_view* x, const float* dout, int OH, int OW, int out_cstride, int out_coff, float* dx,
                      int dx_accumulate, const lhn_bnsum* bns, void* stream) {
   LHN_CHECK_ARG(lhn_view_ok(x) && dout && dx && out_coff >= 0 && out_coff + x->C <= out_cstride, "lhn_avgpool_bwd: bad args");
+  LHN_CHECK_ARG(out_cstride % 4 == 0 && out_coff % 4 == 0, "lhn_avgpool_bwd: pooled gradient layout (stride %d, offset %d: multiples of 4)",
+                out_cstride, out_coff);
+  // k_avgpool_bwd looks at the bins floor(h*OH/H) +- 1: every bin that holds a pixel only while a bin is at least one pixel wide
+  LHN_CHECK_ARG(OH >= 1 && OW >= 1 && OH <= x->H && OW <= x->W, "lhn_avgpool_bwd: pooled size %dx%d must be 1..%dx%d", OH, OW, x->H, x->W);
   LHN_CHECK_ARG(x->C % 4 == 0 && x->C <= 1024, "lhn_avgpool_bwd: C=%d", x->C);
   lhn_bnsum bs;
   if (bns_of(bns, x, &bs, "lhn_avgpool_bwd3")) return 1;

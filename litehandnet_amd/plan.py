@@ -1413,6 +1413,8 @@ class PlanBuilder:
         md, srcs, ops = r.get("mode", 0), r["srcs"], []
         if r.get("coefs") is not None and any(c != 1.0 for c in r["coefs"]):
             raise _lib.LhnError("a combine with coefficients is forward-only")
+        if (md & EW_MUL) and r["slope"] != 1.0:
+            raise _lib.LhnError("a product combine with an output activation is forward-only (lhn_ew_mul_bwd takes no slope)")
         for j, s in enumerate(srcs):
             if s.buf == self._no_grad_buf:
                 continue

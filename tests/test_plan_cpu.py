@@ -288,3 +288,26 @@ def test_residual_sums_share_one_backward_pass(monkeypatch):
         assert nb0 == nb + sum(len([q for q in range(3) if o.in_buf[q] >= 0]) - 1 for o in multi)
         monkeypatch.delenv("LHN_EW_BWD_MULTI")
 
+
+
+def test_product_combine_with_activation_is_forward_only():
+    """The backward of a product combine goes to lhn_ew_mul_bwd, which takes no slope: a product with an output activation must
+    not compile a backward that drops the activation's derivative.  The plain product (lite_hrnet.py:105-107) still does."""
+    from litehandnet_amd._lib import LhnError
+    from litehandnet_amd.plan import EW_MUL
+
+    def build(slope):
+        pb = PlanBuilder(2, {}, image_hw=(16, 16), with_backward=True, p_drop=0.0)
+        out = pb.ew([pb.new(8, 8, 16), pb.new(2, 2, 16)], out_slope=slope, mode=EW_MUL)
+        pb.set_output(out)
+        return pb
+
+    for slope in (0.1, 0.0, 2.0, 3.0):
+        with pytest.raises(LhnError, match="product combine with an output activation"):
+            build(slope).finalize()
+    pb = build(1.0)
+    assert pb.finalize()[4] == 2                              # one lhn_ew_mul_bwd launch per operand
+    # a forward-only plan takes any activation
+    pf = PlanBuilder(2, {}, image_hw=(16, 16), with_backward=False, p_drop=0.0)
+    pf.set_output(pf.ew([pf.new(8, 8, 16), pf.new(2, 2, 16)], out_slope=0.1, mode=EW_MUL))
+    assert pf.finalize()[4] == 0
