@@ -298,6 +298,25 @@ int lhn_conv_pw_dw3_fwd(const lhn_view* x, const float* w1 /*[Cm,Cin]*/, const f
  * shape") and writes nothing. */
 int lhn_conv_dw3_pw_fwd(const lhn_view* x, const float* w_dw /*[Cin,1,3,3]*/, int dil, const float* t_table /*[3][Cin] or NULL*/,
                         const float* w_pw /*[Cout,Cin]*/, const float* bias /*[Cout] or NULL*/, const lhn_view* y, void* stream);
+/* Inference only: BottleNeck (liteHandNet.py:23-37 over repblocks.py:8-44) in one launch -- the three intermediate tensors never
+ * reach memory.  Per image:
+ *   t1 = act1(w1 . value(x) (+ b1))      1x1, C -> Cm          act_i(v) = t_i ? lrelu_{slope_i}(scale_i*v + shift_i) : v
+ *   t2 = act2(conv3x3(t1))               Cm -> Cm, stride 1, t1 padded with ZEROS (not with act1(shift))
+ *   t3 = act3(w3 . t2 (+ b3))            1x1, Cm -> C
+ *   y  = lrelu_{out_slope}(value(x) + t3)   stored PLAIN into channels [y.coff, y.coff + C) of y, as lhn_ew_fwd leaves it
+ * value(x) is the view's own table and gate applied on load, as lhn_conv_dw3_pw_fwd does.  t1, t2 = [3][Cm], t3 = [3][C] scale | shift |
+ * slope tables (NULL = identity); Cm is the middle channel count (the weights carry no shape).  All three convolutions run on the
+ * fp32 MFMA; no statistics, no atomics: repeated calls give identical bits, with or without LHN_DETERMINISTIC.
+ * wt_scratch: optional 9*Cm*Cm floats of caller-owned scratch; the call re-lays w2 tap-major into it with one small launch of its own
+ * (16-byte weight loads per tap), as lhn_conv_kxk_fwd does.  NULL = the kernel reads the OIHW tensor directly and the call is ONE
+ * launch.  (The plan executor skips the re-lay when the parameters have not changed since the run that wrote the scratch.)
+ * Built for C == 128 and Cm in {32, 64}, any N, H, W.  Any other channel pair, an out_slope outside [0, 1] (LHN_SLOPE_SILU /
+ * LHN_SLOPE_RELU_SIGMOID) or a y view that overlaps x's channels in the same buffer returns the invalid-argument status
+ * ("unsupported shape") before any launch and writes nothing. */
+int lhn_bottleneck_fwd(const lhn_view* x, int Cm, const float* w1 /*[Cm,C]*/, const float* b1 /*[Cm] or NULL*/, const float* t1 /*[3][Cm] or NULL*/,
+                       const float* w2 /*[Cm,Cm,3,3]*/, const float* t2 /*[3][Cm] or NULL*/,
+                       const float* w3 /*[C,Cm]*/, const float* b3 /*[C] or NULL*/, const float* t3 /*[3][C] or NULL*/,
+                       float out_slope, const lhn_view* y, float* wt_scratch /*9*Cm*Cm floats or NULL*/, void* stream);
 /* Inference only: one round of an MSRB (litehourglass.py:13-50 over repblocks.py:8-44, common.py:23-66) as one pass over the
  * feature map -- both dilated depthwise 3x3 branches in one launch and, with pooled != NULL, the adaptive-average-pool means the
  * round's ChannelAttension (OH = OW = 3) or SEBlock (OH = OW = 1) reads.  Half k (k = 0: dilation 1, padding 1; k = 1: dilation 2,

@@ -53,6 +53,10 @@ static inline int lhn_device_slot() {
 }
 int lhn_num_cus();   // lhn_api.cpp: CUs of the current device; grid caps for persistent grid-stride kernels
 bool lhn_deterministic_mode();   // LHN_DETERMINISTIC=1, see lhn_api.cpp
+// k_bottleneck.hip: lhn_bottleneck_fwd with the choice of skipping the tap-major copy of w2 (relayout = 0: wt_scratch holds it already)
+int lhn_bottleneck_fwd_impl(const lhn_view* x, int Cm, const float* w1, const float* b1, const float* t1, const float* w2, const float* t2,
+                            const float* w3, const float* b3, const float* t3, float out_slope, const lhn_view* y, float* wt_scratch,
+                            int relayout, void* stream);
 
 #ifdef __HIPCC__
 // Workgroups of `kernel` (256 threads, `dyn_lds` bytes of dynamic LDS) that are resident on one CU at the same time: the

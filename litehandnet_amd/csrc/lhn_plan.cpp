@@ -23,7 +23,7 @@ static lhn_bnsum mkbns(void* ws, int64_t sums_off, int64_t save_off, int C, int 
 enum {
   OP_STEM = 1, OP_PW = 2, OP_DW = 3, OP_KXK = 4, OP_FINALIZE = 5, OP_EW = 6, OP_MAXPOOL = 7, OP_AVGPOOL = 8,
   OP_CA_MLP = 9, OP_TABLE_FILL = 10, OP_MEMSET = 11, OP_ATT_MLP = 12, OP_SE_MLP = 13, OP_SHUFFLE = 14,
-  OP_PWDW = 15, OP_DWPW = 16, OP_MSRB = 17, OP_CBAM = 18,
+  OP_PWDW = 15, OP_DWPW = 16, OP_MSRB = 17, OP_CBAM = 18, OP_BNECK = 19,
   OP_STEM_BWD = 101, OP_PW_BWD = 102, OP_DW_BWD = 103, OP_KXK_BWD = 104, OP_BN_BWD = 105, OP_EW_BWD = 106,
   OP_MAXPOOL_BWD = 107, OP_AVGPOOL_BWD = 108, OP_GATE_REDUCE = 109, OP_CA_MLP_BWD = 110, OP_ATT_MLP_BWD = 111, OP_SE_MLP_BWD = 112,
   OP_SHUFFLE_BWD = 113, OP_CBAM_BWD = 114,
@@ -390,6 +390,23 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
         lhn_view y = mkview(P, ws, o.out_buf, o.out_coff, o.out_C);
         rc = lhn_conv_dw3_pw_fwd(&x, prm<const float>(params, o.p[0]), o.i[0], reinterpret_cast<const float*>(at(ws, P->bufs[o.in_buf[1]].table_off)),
                                  prm<const float>(params, o.p[1]), prm<const float>(params, o.p[2]), &y, stream);
+        break;
+      }
+      case OP_BNECK: {  // BottleNeck in one launch.  in: x and the outputs of the first 1x1 and of the 3x3 (only their tables exist); ws[0]: table
+        // of the second 1x1's output, ws[1]: tap-major scratch of the 3x3's weights; p: w1, b1 or -1, w2, w3, b3 or -1; f[0] = out_slope.
+        // Inference plans only.  The scratch is a function of the parameters like the tables: LHN_RUN_TABLES_CURRENT keeps it too.
+        if (training) {
+          lhn_set_error("lhn_plan_run: a fused BottleNeck launch has no batch statistics (inference plans only)");
+          rc = 1;
+          break;
+        }
+        lhn_view x = mkview(P, ws, o.in_buf[0], o.in_coff[0], o.in_C[0]);
+        lhn_view y = mkview(P, ws, o.out_buf, o.out_coff, o.out_C);
+        rc = lhn_bottleneck_fwd_impl(&x, o.in_C[1], prm<const float>(params, o.p[0]), prm<const float>(params, o.p[1]),
+                                     reinterpret_cast<const float*>(at(ws, P->bufs[o.in_buf[1]].table_off)), prm<const float>(params, o.p[2]),
+                                     reinterpret_cast<const float*>(at(ws, P->bufs[o.in_buf[2]].table_off)), prm<const float>(params, o.p[3]),
+                                     prm<const float>(params, o.p[4]), reinterpret_cast<const float*>(at(ws, o.ws[0])), o.f[0], &y,
+                                     reinterpret_cast<float*>(at(ws, o.ws[1])), skip_tables ? 0 : 1, stream);
         break;
       }
       case OP_MSRB: {  // one MSRB round.  in[0], in[1]: the x views of the two halves; in[2] and i[1..3] (buffer, first channel, channels):

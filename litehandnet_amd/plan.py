@@ -30,6 +30,8 @@ DWPW = 16              # inference plans only: depthwise 3x3 -> 1x1 in one launc
 MSRB = 17              # inference plans only: both depthwise branches of an MSRB round (+ its attention's pooling) in one pass
                        # (lhn_msrb_round_fwd), see PlanBuilder.fuse_msrb_round
 CBAM = 18              # the CBAM chain between its `pre` convolutions and its final ReLU (lhn_cbam_fwd), see PlanBuilder.cbam_attention
+BNECK = 19             # inference plans only: BottleNeck (1x1 -> 3x3 -> 1x1 + residual + activation) in one launch (lhn_bottleneck_fwd),
+                       # see PlanBuilder.fuse_bottleneck
 STEM_BWD, PW_BWD, DW_BWD, KXK_BWD, BN_BWD, EW_BWD, MAXPOOL_BWD, AVGPOOL_BWD, GATE_REDUCE, CA_MLP_BWD, ATT_MLP_BWD, SE_MLP_BWD, SHUFFLE_BWD = range(101, 114)
 CBAM_BWD = 114
 SLOPE_SILU = 2.0       # LHN_SLOPE_SILU in include/lhn.h: the combine applies SiLU instead of a leaky ReLU
@@ -107,6 +109,22 @@ def infer_fuse_msrb_enabled():
     return _INFER_FUSE_MSRB if _INFER_FUSE_MSRB is not None else os.environ.get("LHN_INFER_FUSE_MSRB", "0") == "1"
 
 
+_INFER_FUSE_BNECK = None     # set_infer_fuse_bneck(): in-process override of LHN_INFER_FUSE_BNECK
+
+
+def set_infer_fuse_bneck(on):
+    """Switch the BottleNeck inference fusion pass (PlanBuilder.fuse_bottleneck) on or off for plans built from now on; None =
+    follow the environment again.  Independent of the other three switches; Engine.plan_for keys its cache on all four."""
+    global _INFER_FUSE_BNECK
+    _INFER_FUSE_BNECK = None if on is None else bool(on)
+
+
+def infer_fuse_bneck_enabled():
+    """LHN_INFER_FUSE_BNECK=1 (default off): plans without a backward run each BottleNeck -- 1x1, dense 3x3, 1x1, residual sum and
+    activation -- as one launch."""
+    return _INFER_FUSE_BNECK if _INFER_FUSE_BNECK is not None else os.environ.get("LHN_INFER_FUSE_BNECK", "0") == "1"
+
+
 def _refs_in(v):
     """Every TRef inside a record value (views, concatenations, lists of views or of (view, coefficient) pairs)."""
     if isinstance(v, TRef):
@@ -173,7 +191,7 @@ class _BufRec:
     coef: bool = False
     dpool: bool = False
     lazy: object = None      # the EW record of a sum that is taken ON LOAD by its consumers (never written in forward)
-    fused: bool = False      # the tensor between the two convolutions of a PWDW / DWPW launch: a table, no data
+    fused: bool = False      # a tensor between the convolutions of a PWDW / DWPW / BNECK launch: a table, no data
     off: dict = field(default_factory=dict)
 
 
@@ -218,7 +236,7 @@ class PlanBuilder:
     _no_grad_buf = -1   # the image never needs a gradient
 
     def __init__(self, N, state_index, image_hw=None, with_backward=True, p_drop=0.0, infer_fuse=None, infer_fuse_dwpw=None,
-                 infer_fuse_msrb=None):
+                 infer_fuse_msrb=None, infer_fuse_bneck=False):
         self.N = N
         # inference fusion (fuse_pw_dw): None = the process-wide switch.  The fused launch has no batch statistics, so the
         # caller passes False for a plan that will run train-mode BatchNorm under no_grad (Engine.plan_for).
@@ -228,6 +246,8 @@ class PlanBuilder:
         self.n_fused_dwpw = 0
         self.infer_fuse_msrb = infer_fuse_msrb_enabled() if infer_fuse_msrb is None else bool(infer_fuse_msrb)   # fuse_msrb_round, likewise
         self.n_fused_msrb = 0
+        self.infer_fuse_bneck = infer_fuse_bneck_enabled() if infer_fuse_bneck is None else bool(infer_fuse_bneck)   # fuse_bottleneck, likewise
+        self.n_fused_bneck = 0
         self.state_index = state_index      # id(tensor) -> index in the params array
         self.bufs = []
         self.recs = []                      # forward records (python dicts)
@@ -955,12 +975,115 @@ class PlanBuilder:
         self.n_fused_msrb += len(at)
         return len(at)
 
+    # Channel pairs (C, Cm) lhn_bottleneck_fwd is built for (csrc/k_bottleneck.hip: bottleneck_supported); any map size.
+    FUSE_BNECK_CHANNELS = ((128, 32), (128, 64))
+
+    def _sole_reader(self, t, writer, uses, kind):
+        """The only record that reads the whole, fresh, ungated, non-lazy buffer behind view t (written by `writer`), if it is of
+        `kind`; else None.  What fills the buffer's table (FINALIZE / TABLE_FILL) is not a reader."""
+        if isinstance(t, TCat) or t.buf < 0:
+            return None
+        tb = self.bufs[t.buf]
+        if t.coff != 0 or tb.C != t.C or tb.gate or tb.lazy is not None or tb.fused:
+            return None
+        if any(v is not None and v.buf == t.buf for v in (self.in_ref, self.out_ref)):
+            return None
+        q = None
+        for u, key in uses.get(t.buf, ()):
+            if (u is writer or u["op"] in (FINALIZE, TABLE_FILL)) and key == "out":
+                continue
+            if u["op"] == kind and key in ("x", "srcs") and q is None:
+                q = u
+                continue
+            return None
+        return q
+
+    def _plain_conv(self, r, kind):
+        """A stride-1 convolution record of `kind` with one plain source and nothing special about its weights or BatchNorm."""
+        if r is None or r["op"] != kind or r["stride"] != 1 or r["nchw"] or r["wrc"] != (0, 0) or r["bn_repeat"] != 1 or self._xs(r)[1] != 1:
+            return False
+        if r["x"].buf < 0 or isinstance(r["x"], TCat):
+            return False
+        return not (r["bn"] is not None and getattr(r["conv"], "bias", None) is not None)     # as _fusable_dw_pw
+
+    def _fusable_bottleneck(self, r1, uses):
+        """(r2, r3, ew) when the 1x1 record r1 starts a BottleNeck pattern, else None: 1x1 C -> Cm, 3x3 Cm -> Cm, 1x1 Cm -> C (slope 1),
+        each into a whole fresh buffer with one reader, and a plain two-source sum of r1's input and the last output."""
+        if not self._plain_conv(r1, PW):
+            return None
+        x, t1 = r1["x"], r1["out"]
+        if (x.C, t1.C) not in self.FUSE_BNECK_CHANNELS:
+            return None
+        r2 = self._sole_reader(t1, r1, uses, KXK)
+        if not self._plain_conv(r2, KXK) or (r2["x"].coff, r2["x"].C) != (0, t1.C) or r2["out"].C != t1.C:
+            return None
+        t2 = r2["out"]
+        r3 = self._sole_reader(t2, r2, uses, PW)
+        if not self._plain_conv(r3, PW) or (r3["x"].coff, r3["x"].C) != (0, t2.C) or r3["out"].C != x.C or r3["slope"] != 1.0:
+            return None
+        t3 = r3["out"]
+        ew = self._sole_reader(t3, r3, uses, EW)
+        if ew is None or ew.get("mode") or ew.get("coefs") is not None or ew.get("lazy") or "flat" in ew or len(ew["srcs"]) != 2:
+            return None
+        if not 0.0 <= ew["slope"] <= 1.0 or len({t1.buf, t2.buf, t3.buf, x.buf}) != 4:
+            return None
+        a, b = ew["srcs"]
+        key = lambda v: None if isinstance(v, TCat) else (v.buf, v.coff, v.C, v.H, v.W)
+        if {key(a), key(b)} != {key(x), key(t3)} or key(x) == key(t3):
+            return None
+        y = ew["out"]
+        if isinstance(y, TCat) or y.buf < 0 or y.buf in (t1.buf, t2.buf, t3.buf) or (y.H, y.W, y.C) != (x.H, x.W, x.C):
+            return None
+        if y.buf == x.buf and x.coff < y.coff + y.C and y.coff < x.coff + x.C:
+            return None
+        return r2, r3, ew
+
+    def fuse_bottleneck(self):
+        """Inference plans with the switch on (infer_fuse_bneck): BottleNeck (liteHandNet.py:23-37) -- RepConv 1x1, RepConv 3x3, RepConv
+        1x1, the residual sum and its activation -- becomes ONE record (lhn_bottleneck_fwd).  The pass matches the record pattern, not
+        the module class.  As in fuse_dw_pw the three intermediate buffers keep their tables and lose their data; what fills those
+        tables in the unfused plan stays ahead of the launch (eval: FINALIZE from the running statistics; deployed: the TABLE_FILL
+        records, which stay where they are; b1 / b3 are the 1x1 biases the unfused kernel adds while storing).  The launch stands
+        where the sum stood.  Plans with a backward are never rewritten."""
+        if self.with_backward or not self.infer_fuse_bneck:
+            return 0
+        uses = {}
+        for r in self.recs:
+            for key, v in r.items():
+                for t in _refs_in(v):
+                    uses.setdefault(t.buf, []).append((r, key))
+        at, drop = {}, set()
+        for r1 in self.recs:
+            m = self._fusable_bottleneck(r1, uses)
+            if m is None:
+                continue
+            r2, r3, ew = m
+            if {id(r1), id(r2), id(r3), id(ew)} & drop:
+                continue
+            tables = [dict(op=FINALIZE, out=q["out"], bn=q["bn"], slope=q["slope"]) for q in (r1, r2, r3) if q["bn"] is not None]
+            fused = dict(op=BNECK, x=r1["x"], mids=[r1["out"], r2["out"], r3["out"]], out=ew["out"], convs=(r1["conv"], r2["conv"], r3["conv"]),
+                         b1=None if r1["bn"] is not None else r1["conv"].bias, b3=None if r3["bn"] is not None else r3["conv"].bias,
+                         slope=ew["slope"], wt=r2["wt"])
+            at[id(ew)] = tables + [fused]
+            drop |= {id(r1), id(r2), id(r3), id(ew)}
+            for q in (r1, r2, r3):
+                self.bufs[q["out"].buf].fused = True
+        if not at:
+            return 0
+        recs = []
+        for r in self.recs:
+            recs += at.get(id(r), [] if id(r) in drop else [r])
+        self.recs = recs
+        self.n_fused_bneck += len(at)
+        return len(at)
+
     # ------------------------------------------------------------------ finalize: the passes in the order they run
     def finalize(self):
         """Lower the records to what lhn_plan_create takes: (Buf array, forward Op array, backward Op array or None, n_fwd, n_bwd)."""
         self.fuse_msrb_round()
         self.fuse_dw_pw()
         self.fuse_pw_dw()
+        self.fuse_bottleneck()
         self._layout()
         self._plan_sum_out()
         fwd = self._lower_forward()
@@ -999,7 +1122,7 @@ class PlanBuilder:
     # ------------------------------------------------------------------ forward lowering: one emitter per record family -> [Op]
     def _lower_forward(self):
         emit = {STEM: self._fwd_conv, PW: self._fwd_conv, DW: self._fwd_conv, KXK: self._fwd_conv, PWDW: self._fwd_pwdw, DWPW: self._fwd_dwpw,
-                MSRB: self._fwd_msrb,
+                MSRB: self._fwd_msrb, BNECK: self._fwd_bneck,
                 FINALIZE: self._fwd_table, TABLE_FILL: self._fwd_table, EW: self._fwd_ew, SHUFFLE: self._fwd_pool,
                 MAXPOOL: self._fwd_pool, AVGPOOL: self._fwd_pool, CA_MLP: self._fwd_ca, SE_MLP: self._fwd_se, ATT_MLP: self._fwd_att,
                 CBAM: self._fwd_cbam}
@@ -1041,6 +1164,14 @@ class PlanBuilder:
     def _fwd_dwpw(self, r):
         return [self._mk(DWPW, ins=(r["x"], r["mid"]), out=r["out"], i=(r["dil"],),
                          p=(self._p(r["conv"].weight), self._p(r["conv2"].weight), self._p(r["bias"])))]
+
+    def _fwd_bneck(self, r):
+        """in: x and the first two intermediates (tables only); ws[0] = the third intermediate's table, ws[1] = the 3x3's tap-major
+        scratch; p = w1, b1, w2, w3, b3 (a bias only where no BatchNorm follows: the unfused 1x1 adds it while storing); f[0] = slope."""
+        t1, t2, t3 = r["mids"]
+        c1, c2, c3 = r["convs"]
+        return [self._mk(BNECK, ins=(r["x"], t1, t2), out=r["out"], ws=(self.bufs[t3.buf].off["table"], self._abs(r["wt"])),
+                         p=(self._p(c1.weight), self._p(r["b1"]), self._p(c2.weight), self._p(c3.weight), self._p(r["b3"])), f=(r["slope"],))]
 
     def _fwd_msrb(self, r):
         """in: the x views of the two halves and the first half's extra source (the second's rides in i[1..3]: an op has three

@@ -1,10 +1,11 @@
 """Inference latency: eval-mode train form vs deployed (re-parameterised) form, each with the inference fusion passes off and on
-(plan.set_infer_fuse, plan.set_infer_fuse_dwpw, plan.set_infer_fuse_msrb; LHN_INFER_FUSE / LHN_INFER_FUSE_DWPW / LHN_INFER_FUSE_MSRB in
-the environment are overridden here).
-python scripts/bench_infer.py [A|B|M] [bs] [every|off|on|dwpw|both|msrb|all]
-  off / on / dwpw / both / msrb / all: only the lines of that setting (no fusion / 1x1 -> depthwise / depthwise -> 1x1 / those two
-  passes / MSRB rounds / all three passes), for alternating runs in fresh processes; every (the default): off and on, dwpw and both
-  where the depthwise -> 1x1 pass finds pairs, msrb and all where the MSRB pass finds rounds.
+(plan.set_infer_fuse, plan.set_infer_fuse_dwpw, plan.set_infer_fuse_msrb, plan.set_infer_fuse_bneck; LHN_INFER_FUSE / LHN_INFER_FUSE_DWPW /
+LHN_INFER_FUSE_MSRB / LHN_INFER_FUSE_BNECK in the environment are overridden here).
+python scripts/bench_infer.py [A|B|M] [bs] [every|off|on|dwpw|both|msrb|all|bneck|full] [reduction]
+  off / on / dwpw / both / msrb / all / bneck / full: only the lines of that setting (no fusion / 1x1 -> depthwise / depthwise -> 1x1 /
+  those two passes / MSRB rounds / those three passes / BottleNecks / all four passes), for alternating runs in fresh processes; every
+  (the default): off and on, dwpw and both where the depthwise -> 1x1 pass finds pairs, msrb and all where the MSRB pass finds rounds,
+  bneck and full where the BottleNeck pass finds blocks.  reduction: the `reduction` of variant A's Residual blocks (config default 4).
 Launches: kernel launches of one steady-state forward (tables current), and the table-only launches a first forward adds."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -12,22 +13,25 @@ import torch
 from litehandnet_amd import get_model, plan
 from litehandnet_amd.config import litehandnet_cfg
 
-# (infer_fuse, infer_fuse_dwpw, infer_fuse_msrb)
-SETTINGS = {"off": (False, False, False), "on": (True, False, False), "dwpw": (False, True, False), "both": (True, True, False),
-            "msrb": (False, False, True), "all": (True, True, True)}
+# (infer_fuse, infer_fuse_dwpw, infer_fuse_msrb, infer_fuse_bneck)
+SETTINGS = {"off": (False, False, False, False), "on": (True, False, False, False), "dwpw": (False, True, False, False),
+            "both": (True, True, False, False), "msrb": (False, False, True, False), "all": (True, True, True, False),
+            "bneck": (False, False, False, True), "full": (True, True, True, True)}
 variant = sys.argv[1] if len(sys.argv) > 1 else "B"
 bs = int(sys.argv[2]) if len(sys.argv) > 2 else 64
 which = sys.argv[3] if len(sys.argv) > 3 else "every"
 assert which == "every" or which in SETTINGS, which
-m = get_model(litehandnet_cfg(variant)).cuda().eval()
+cfg_kw = {"reduction": int(sys.argv[4])} if len(sys.argv) > 4 else {}
+m = get_model(litehandnet_cfg(variant, **cfg_kw)).cuda().eval()
 x = torch.randn(bs, 3, 256, 256, device="cuda")
 
 
 side = torch.cuda.Stream()
 
 
-def launches(fuse, dwpw, msrb):
-    p = next(p for k, p in m.__dict__["_engine"].plans.items() if k[0] == tuple(x.shape) and k[-1] == fuse and k[-2] == dwpw and k[-3] == msrb)
+def launches(fuse, dwpw, msrb, bneck):
+    p = next(p for k, p in m.__dict__["_engine"].plans.items()
+             if k[0] == tuple(x.shape) and k[-1] == fuse and k[-2] == dwpw and k[-3] == msrb and k[-4] == bneck)
     ops = p._keep[1]
     convs = (plan.STEM, plan.PW, plan.DW, plan.KXK)
     tables = sum(o.kind in (plan.TABLE_FILL, plan.FINALIZE) or (o.kind in convs and o.p[2] >= 0) for o in ops)
@@ -35,16 +39,17 @@ def launches(fuse, dwpw, msrb):
     steady += sum(o.kind == plan.MSRB and o.ws[0] >= 0 for o in ops)       # a pooling MSRB round is two launches: the pass and its fold
     # algorithmic bytes per image of THIS plan's graph: 4 B x (input + output elements) of every convolution launch
     mb = sum(4 * (r["x"].H * r["x"].W * r["x"].C + r["out"].H * r["out"].W * r["out"].C)
-             for r in p.pb.recs if r["op"] in convs + (plan.PWDW, plan.DWPW)) / 1e6
+             for r in p.pb.recs if r["op"] in convs + (plan.PWDW, plan.DWPW, plan.BNECK)) / 1e6
     mb += sum(8 * r["out"].H * r["out"].W * r["out"].C for r in p.pb.recs if r["op"] == plan.MSRB) / 1e6
-    return steady, tables, p.pb.n_fused, p.pb.n_fused_dwpw, p.pb.n_fused_msrb, mb
+    return steady, tables, p.pb.n_fused, p.pb.n_fused_dwpw, p.pb.n_fused_msrb, p.pb.n_fused_bneck, mb
 
 
 def timeit(form, setting):
-    fuse, dwpw, msrb = SETTINGS[setting]
+    fuse, dwpw, msrb, bneck = SETTINGS[setting]
     plan.set_infer_fuse(fuse)
     plan.set_infer_fuse_dwpw(dwpw)
     plan.set_infer_fuse_msrb(msrb)
+    plan.set_infer_fuse_bneck(bneck)
     with torch.no_grad(), torch.cuda.stream(side):
         for _ in range(5):
             m(x)
@@ -56,13 +61,13 @@ def timeit(form, setting):
             m(x)
         e1.record()
         torch.cuda.synchronize()
-        steady, tables, fused, fused_dwpw, fused_msrb, mb = launches(fuse, dwpw, msrb)
+        steady, tables, fused, fused_dwpw, fused_msrb, fused_bneck, mb = launches(fuse, dwpw, msrb, bneck)
         ms = e0.elapsed_time(e1) / 20
-        print(f"{variant} bs{bs} {form} [{setting}]: {ms:.3f} ms/fwd (wall {(time.perf_counter() - t0) * 50:.3f}) "
+        print(f"{variant}{'' if not cfg_kw else ' r' + str(cfg_kw['reduction'])} bs{bs} {form} [{setting}]: {ms:.3f} ms/fwd (wall {(time.perf_counter() - t0) * 50:.3f}) "
               f"-> {bs / ms * 1e3:.0f} img/s; {steady} launches (+{tables} table launches on a first run), "
-              f"{fused} 1x1->dw + {fused_dwpw} dw->1x1 fused pairs, {fused_msrb} MSRB rounds; {mb:.2f} MB/image of convolution traffic = {mb * bs / ms / 1e3:.3f} TB/s = "
+              f"{fused} 1x1->dw + {fused_dwpw} dw->1x1 fused pairs, {fused_msrb} MSRB rounds, {fused_bneck} BottleNecks; {mb:.2f} MB/image of convolution traffic = {mb * bs / ms / 1e3:.3f} TB/s = "
               f"{mb * bs / ms / 1e3 / 8:.3f} of 8 TB/s", flush=True)
-    return fused_dwpw, fused_msrb
+    return fused_dwpw, fused_msrb, fused_bneck
 
 
 def form(name):
@@ -75,6 +80,8 @@ def form(name):
         timeit(name, "both")
     if timeit(name, "msrb")[1]:
         timeit(name, "all")
+    if timeit(name, "bneck")[2]:
+        timeit(name, "full")
 
 
 form("eval")
