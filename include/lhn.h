@@ -343,6 +343,22 @@ int lhn_conv_stem_fwd(const float* img /*[N,3,Hi,Wi]*/, const float* w /*[Cout,3
  * (16-byte weight loads per tap instead of 36-byte-strided gathers).  NULL = read the OIHW tensor directly. */
 int lhn_conv_kxk_fwd(const lhn_view* x, const float* w /*[Cout,Cin,3,3]*/, const lhn_view* y, double* stats,
                      int stride, const lhn_bnfin* fin, float* wt_scratch, void* stream);
+/* Inference only: the stride-1 dense 3x3 of lhn_conv_kxk_fwd (liteHandNet.py:31,45: RepConv(.., 3, 1, 1) of BottleNeck / BasicBlock;
+ * hourglassnet.py:33 Residual.conv2; nn.Conv2d(Cin, Cout, 3, 1, 1) on fp32) on the bf16 MFMA with a three-term split ("bf16x3"): every fp32 operand is
+ * hi + lo with hi = bf16(v), lo = bf16(v - hi) (round-to-nearest-even) and  a*b ~ a_lo*b_hi + a_hi*b_lo + a_hi*b_hi  with fp32
+ * accumulation, added in that order per 16 input channels, taps 0..8, channels ascending.  Per element the result stays within
+ * 3.1 * 2^-16 * conv(|value(x)|, |w|) of the exact convolution (about 17 x the error of the fp32 kernel on activations).
+ * value(x) is the view's table, slope and gate applied in fp32 on load, as lhn_conv_kxk_fwd does; the map is padded with zeros of
+ * the VALUE.  y gets the raw sums in channels [y.coff, y.coff + Cout); no statistics, no bias, no atomics: repeated calls give
+ * identical bits, with or without LHN_DETERMINISTIC.
+ * wsplit: caller-owned scratch of 9*Cout*Cin*4 bytes (the size of lhn_conv_kxk_fwd's wt_scratch), REQUIRED.  relay = 1: the call first
+ * writes the split tap-major image of w into it ([2][9][Cout][Cin] bf16: hi, then lo) with one small launch; relay = 0: it already
+ * holds the image of these weights (the plan executor, when the parameters have not changed since the run that wrote it).
+ * Built for Cin, Cout in {32, 64, 128}, any N, H, W, channel-slice views.  A y map that is not x's (stride != 1), any other channel
+ * count, wsplit == NULL or a y view that overlaps x's channels in the same buffer returns the invalid-argument status before any
+ * launch and writes nothing. */
+int lhn_conv_kxk_fwd_bf16x3(const lhn_view* x, const float* w /*[Cout,Cin,3,3]*/, const lhn_view* y,
+                            void* wsplit /* 9*Cout*Cin*4 bytes, required */, int relay /* 1: rebuild wsplit from w */, void* stream);
 /* conv_bias: a biased convolution followed by BatchNorm (models/pose_hg_ms_att.py:27-35,46-56) stores its output
  * WITHOUT the bias -- BatchNorm cancels it -- and the bias only enters the running mean (training) or the shift
  * (eval: beta - (running_mean - bias) * scale).  d(bias) is identically zero in training mode. */

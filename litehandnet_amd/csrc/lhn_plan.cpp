@@ -361,6 +361,18 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
           fin = mkfin(P, ws, o, params);
           fin.count *= cscale;
         }
+        if (o.i[1] == 1) {  // bf16x3 (PlanBuilder.mark_bf16x3): the split-bf16 MFMA kernel; ws[3] holds the split weights.  Inference plans
+          // only.  The scratch is a function of the parameters like the tables: LHN_RUN_TABLES_CURRENT keeps it too.
+          if (training) {
+            lhn_set_error("lhn_plan_run: a bf16x3 3x3 launch has no batch statistics (inference plans only)");
+            rc = 1;
+            break;
+          }
+          if (h0) rc = lhn_conv_kxk_fwd_bf16x3(&x, prm<const float>(params, o.p[0]), &y, o.ws[3] >= 0 ? at(ws, o.ws[3]) : nullptr,
+                                               skip_tables ? 0 : 1, stream);
+          if (!rc && bn && h1 && !skip_tables) rc = sep_finalize(fin, nullptr, 0, stream);
+          break;
+        }
         if (h0) rc = lhn_conv_kxk_fwd(&x, prm<const float>(params, o.p[0]), &y,
                               (training && o.ws[0] >= 0) ? reinterpret_cast<double*>(at(ws, o.ws[0])) : nullptr, o.i[0],
                               (bn && fz) ? &fin : nullptr,

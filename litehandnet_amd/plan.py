@@ -125,6 +125,38 @@ def infer_fuse_bneck_enabled():
     return _INFER_FUSE_BNECK if _INFER_FUSE_BNECK is not None else os.environ.get("LHN_INFER_FUSE_BNECK", "0") == "1"
 
 
+_INFER_BF16X3 = None     # set_infer_bf16x3(): in-process override of LHN_INFER_BF16X3
+
+
+def set_infer_bf16x3(on):
+    """Switch the split-bf16 pass for dense 3x3 convolutions (PlanBuilder.mark_bf16x3) on or off for plans built from now on; None =
+    follow the environment again.  Independent of the four fusion switches; Engine.plan_for keys its cache on all five."""
+    global _INFER_BF16X3
+    _INFER_BF16X3 = None if on is None else bool(on)
+
+
+def infer_bf16x3_enabled():
+    """LHN_INFER_BF16X3=1 (default off): plans without a backward run their stride-1 dense 3x3 convolutions with 32 / 64 / 128
+    channels on the bf16 MFMA with a three-term split (lhn_conv_kxk_fwd_bf16x3) instead of the fp32 MFMA."""
+    return _INFER_BF16X3 if _INFER_BF16X3 is not None else os.environ.get("LHN_INFER_BF16X3", "0") == "1"
+
+
+# What lhn_conv_kxk_fwd_bf16x3 is built for (csrc/k_conv_kxk_bf16.hip: kxk_bf16x3_channels and the checks of the entry point) ...
+BF16X3_CHANNELS = (32, 64, 128)
+# ... and the (Cin, Cout) classes the pass leaves on the fp32 kernel all the same (DESIGN.md 5.2).  32 -> 32: in variant A these are the
+# inner 3x3 of the BottleNecks, whose small split error the following BatchNorm scales up: with them on the bf16 MFMA the heat maps of A
+# at 256 x 256 sit 1.5e-4 of their peak from float64 (bar 1e-4; 1.2e-5 ... 3.3e-5 without them), and they are launch-bound, not
+# MFMA-bound, so nothing is lost.
+BF16X3_LEFT_OUT = ((32, 32),)
+
+
+def bf16x3_eligible(cin, cout, stride, overlap=False):
+    """THE eligibility rule of the bf16x3 pass: a stride-1 dense 3x3 (pad 1) the entry point accepts -- Cin and Cout in
+    BF16X3_CHANNELS, an output view that does not overlap its input's channels in the same buffer -- and whose channel class has not
+    been taken out by measurement (BF16X3_LEFT_OUT).  Any map size."""
+    return stride == 1 and cin in BF16X3_CHANNELS and cout in BF16X3_CHANNELS and not overlap and (cin, cout) not in BF16X3_LEFT_OUT
+
+
 def _refs_in(v):
     """Every TRef inside a record value (views, concatenations, lists of views or of (view, coefficient) pairs)."""
     if isinstance(v, TRef):
@@ -236,7 +268,7 @@ class PlanBuilder:
     _no_grad_buf = -1   # the image never needs a gradient
 
     def __init__(self, N, state_index, image_hw=None, with_backward=True, p_drop=0.0, infer_fuse=None, infer_fuse_dwpw=None,
-                 infer_fuse_msrb=None, infer_fuse_bneck=False):
+                 infer_fuse_msrb=None, infer_fuse_bneck=False, infer_bf16x3=False):
         self.N = N
         # inference fusion (fuse_pw_dw): None = the process-wide switch.  The fused launch has no batch statistics, so the
         # caller passes False for a plan that will run train-mode BatchNorm under no_grad (Engine.plan_for).
@@ -248,6 +280,8 @@ class PlanBuilder:
         self.n_fused_msrb = 0
         self.infer_fuse_bneck = infer_fuse_bneck_enabled() if infer_fuse_bneck is None else bool(infer_fuse_bneck)   # fuse_bottleneck, likewise
         self.n_fused_bneck = 0
+        self.infer_bf16x3 = infer_bf16x3_enabled() if infer_bf16x3 is None else bool(infer_bf16x3)   # mark_bf16x3, likewise
+        self.n_bf16x3 = 0
         self.state_index = state_index      # id(tensor) -> index in the params array
         self.bufs = []
         self.recs = []                      # forward records (python dicts)
@@ -1077,6 +1111,26 @@ class PlanBuilder:
         self.n_fused_bneck += len(at)
         return len(at)
 
+    def mark_bf16x3(self):
+        """Inference plans with the switch on (infer_bf16x3): every dense 3x3 record that bf16x3_eligible accepts runs on the bf16 MFMA
+        with a three-term split (lhn_conv_kxk_fwd_bf16x3).  The record stays a KXK record with the same views, parameters and scratch
+        (the fp32 tap-major copy and the split image are both 9 * Cout * Cin * 4 bytes); it lowers to the same op with i[1] = 1.  Runs
+        after fuse_bottleneck: a BNECK record keeps its fp32 inner 3x3, this pass takes the 3x3 records that are left.  Plans with a
+        backward are never marked."""
+        if self.with_backward or not self.infer_bf16x3:
+            return 0
+        n = 0
+        for r in self.recs:
+            if r["op"] != KXK or isinstance(r["x"], TCat) or isinstance(r["out"], TCat) or r["x"].buf < 0 or r["out"].buf < 0:
+                continue
+            x, y = r["x"], r["out"]
+            overlap = x.buf == y.buf and x.coff < y.coff + y.C and y.coff < x.coff + x.C
+            if r["k"] == 3 and r["pad"] == 1 and r["dil"] == 1 and bf16x3_eligible(x.C, y.C, r["stride"], overlap):
+                r["bf16x3"] = True
+                n += 1
+        self.n_bf16x3 += n
+        return n
+
     # ------------------------------------------------------------------ finalize: the passes in the order they run
     def finalize(self):
         """Lower the records to what lhn_plan_create takes: (Buf array, forward Op array, backward Op array or None, n_fwd, n_bwd)."""
@@ -1084,6 +1138,7 @@ class PlanBuilder:
         self.fuse_dw_pw()
         self.fuse_pw_dw()
         self.fuse_bottleneck()
+        self.mark_bf16x3()
         self._layout()
         self._plan_sum_out()
         fwd = self._lower_forward()
@@ -1149,7 +1204,7 @@ class PlanBuilder:
             return [mk(STEM, out=out, p=(pw, cb) + pbn, ws=wsl, i=(r["k"], r["stride"], r["pad"], x.H, x.W), f=fl)]
         if k == KXK:
             return [mk(KXK, ins=(x,), out=out, p=(pw, cb) + pbn, ws=(tuple(wsl) + (-1, -1, -1))[:3] + (self._abs(r["wt"]),),
-                       i=(r["stride"],), f=fl)]
+                       i=(r["stride"], 1) if r.get("bf16x3") else (r["stride"],), f=fl)]
         xv, nx, cf = self._xs(r)
         ws, f = (tuple(wsl) + (-1,) * 4)[:4] + so, (tuple(fl) + (0.0,) * 4)[:4] + tuple(cf)
         if k == PW:
