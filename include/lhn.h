@@ -317,6 +317,32 @@ int lhn_bottleneck_fwd(const lhn_view* x, int Cm, const float* w1 /*[Cm,C]*/, co
                        const float* w2 /*[Cm,Cm,3,3]*/, const float* t2 /*[3][Cm] or NULL*/,
                        const float* w3 /*[C,Cm]*/, const float* b3 /*[C] or NULL*/, const float* t3 /*[3][C] or NULL*/,
                        float out_slope, const lhn_view* y, float* wt_scratch /*9*Cm*Cm floats or NULL*/, void* stream);
+/* Inference only: the stem after its first convolution (Stem.forward, liteHandNet.py:169-193; my_pelee_stem,
+ * models/pose_hg_ms_att.py:196-228) in one launch -- the depthwise K x K, branch1 (1x1, dense 3x3 stride 2), branch2 (max pool), the
+ * concatenation and the last 1x1; no intermediate tensor reaches memory.  Per image, with m = x.C = 32 and C = y.C = 128:
+ *   t = K ? actT(dwKxK(value(x)) (+ bT)) : value(x)     K in {0, 3, 7}; stride 1, pad K/2; x outside the map is 0, not act(shift_x)
+ *   u = actU(w1 . t (+ b1))                              1x1, m -> m, at H x W
+ *   v = actV(conv3x3(u) (+ b2))                          dense, m -> m, stride 2, pad 1; u padded with ZEROS (not with actU(shift))
+ *   p = maxpool2x2(t), stride 2, ceil_mode               windows clipped to the map; tables are applied BEFORE the max
+ *   y = w3 . cat(v, p) (+ b3)                            1x1, 2m -> C, at ceil(H/2) x ceil(W/2); stored raw into channels
+ *                                                        [y.coff, y.coff + C) of y, as lhn_conv_pw_fwd leaves it
+ * actX(v) = tX ? lrelu_{slope}(scale*v + shift) : v with tT, tU, tV = [3][m] scale | shift | slope tables (NULL = identity); biases may
+ * be NULL; value(x) is the view's own table and gate applied on load.  K = 0: x IS t (the eval-mode RepBlock sum, stored plain by
+ * lhn_ew_fwd) and w_dw, bT, tT are ignored.  All three dense stages run on the fp32 MFMA with fp32 accumulation; no statistics, no
+ * atomics: repeated calls give identical bits, with or without LHN_DETERMINISTIC.
+ * wt_scratch: optional 9*m*m floats of caller-owned scratch; the call re-lays w2 tap-major into it with one small launch of its own, as
+ * lhn_bottleneck_fwd does.  NULL = the kernel reads the OIHW tensor directly (the same products in the same order: the same bits) and
+ * the call is ONE launch.  (The plan executor skips the re-lay when the parameters have not changed since the run that wrote it.)
+ * Built for m == 32, C == 128, K in {0, 3, 7}, any N, H, W >= 1 (H, W may be odd; y is N x ceil(H/2) x ceil(W/2)).  Any other channel
+ * pair, any other K, a table slope outside [0, 1] (LHN_SLOPE_SILU / LHN_SLOPE_RELU_SIGMOID; x's own table included -- this entry point
+ * waits for the stream and reads the slope rows back, so it cannot be called on a capturing stream) or a y view that overlaps x's
+ * channels in the same buffer returns the invalid-argument status ("unsupported shape") before any launch and writes neither y nor
+ * the scratch. */
+int lhn_stem_tail_fwd(const lhn_view* x, int K, const float* w_dw /*[m,1,K,K]; unused when K == 0*/, const float* bT /*[m] or NULL*/,
+                      const float* tT /*[3][m] or NULL*/, const float* w1 /*[m,m]*/, const float* b1 /*[m] or NULL*/,
+                      const float* tU /*[3][m] or NULL*/, const float* w2 /*[m,m,3,3]*/, const float* b2 /*[m] or NULL*/,
+                      const float* tV /*[3][m] or NULL*/, const float* w3 /*[C,2m]*/, const float* b3 /*[C] or NULL*/, const lhn_view* y,
+                      float* wt_scratch /*9*m*m floats or NULL*/, void* stream);
 /* Inference only: one round of an MSRB (litehourglass.py:13-50 over repblocks.py:8-44, common.py:23-66) as one pass over the
  * feature map -- both dilated depthwise 3x3 branches in one launch and, with pooled != NULL, the adaptive-average-pool means the
  * round's ChannelAttension (OH = OW = 3) or SEBlock (OH = OW = 1) reads.  Half k (k = 0: dilation 1, padding 1; k = 1: dilation 2,

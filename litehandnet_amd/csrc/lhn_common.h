@@ -57,6 +57,12 @@ bool lhn_deterministic_mode();   // LHN_DETERMINISTIC=1, see lhn_api.cpp
 int lhn_bottleneck_fwd_impl(const lhn_view* x, int Cm, const float* w1, const float* b1, const float* t1, const float* w2, const float* t2,
                             const float* w3, const float* b3, const float* t3, float out_slope, const lhn_view* y, float* wt_scratch,
                             int relayout, void* stream);
+// k_stem.hip: lhn_stem_tail_fwd with the plan executor's choices -- tV is rows of a [3][tv_stride] table (the first m channels of the
+// concatenation buffer's), relayout as above, check_slopes = 0 skips the blocking read-back of the tables' slope rows (the plan pass
+// has looked at the slopes already, and a captured stream cannot be waited for)
+int lhn_stem_tail_fwd_impl(const lhn_view* x, int K, const float* w_dw, const float* bT, const float* tT, const float* w1, const float* b1,
+                           const float* tU, const float* w2, const float* b2, const float* tV, int tv_stride, const float* w3, const float* b3,
+                           const lhn_view* y, float* wt_scratch, int relayout, int check_slopes, void* stream);
 
 #ifdef __HIPCC__
 // Workgroups of `kernel` (256 threads, `dyn_lds` bytes of dynamic LDS) that are resident on one CU at the same time: the

@@ -23,7 +23,7 @@ static lhn_bnsum mkbns(void* ws, int64_t sums_off, int64_t save_off, int C, int 
 enum {
   OP_STEM = 1, OP_PW = 2, OP_DW = 3, OP_KXK = 4, OP_FINALIZE = 5, OP_EW = 6, OP_MAXPOOL = 7, OP_AVGPOOL = 8,
   OP_CA_MLP = 9, OP_TABLE_FILL = 10, OP_MEMSET = 11, OP_ATT_MLP = 12, OP_SE_MLP = 13, OP_SHUFFLE = 14,
-  OP_PWDW = 15, OP_DWPW = 16, OP_MSRB = 17, OP_CBAM = 18, OP_BNECK = 19,
+  OP_PWDW = 15, OP_DWPW = 16, OP_MSRB = 17, OP_CBAM = 18, OP_BNECK = 19, OP_STEMTAIL = 20,
   OP_STEM_BWD = 101, OP_PW_BWD = 102, OP_DW_BWD = 103, OP_KXK_BWD = 104, OP_BN_BWD = 105, OP_EW_BWD = 106,
   OP_MAXPOOL_BWD = 107, OP_AVGPOOL_BWD = 108, OP_GATE_REDUCE = 109, OP_CA_MLP_BWD = 110, OP_ATT_MLP_BWD = 111, OP_SE_MLP_BWD = 112,
   OP_SHUFFLE_BWD = 113, OP_CBAM_BWD = 114,
@@ -419,6 +419,26 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
                                      reinterpret_cast<const float*>(at(ws, P->bufs[o.in_buf[2]].table_off)), prm<const float>(params, o.p[3]),
                                      prm<const float>(params, o.p[4]), reinterpret_cast<const float*>(at(ws, o.ws[0])), o.f[0], &y,
                                      reinterpret_cast<float*>(at(ws, o.ws[1])), skip_tables ? 0 : 1, stream);
+        break;
+      }
+      case OP_STEMTAIL: {  // the stem after its first convolution in one launch.  in[0]: x (i[0] = K > 0: the depthwise convolution's input;
+        // K == 0: t itself), in[1]: t, in[2]: u (of both only the tables exist; K == 0: t's is x's own); ws[0]: table of the concatenation
+        // buffer, whose first in_C[2] channels are v's, i[1]: its channel count; ws[1]: tap-major scratch of the 3x3's weights; p: w_dw, bT,
+        // w1, b1, w2, b2, w3, b3 (-1 = none).  Inference plans only; the scratch follows LHN_RUN_TABLES_CURRENT like OP_BNECK's.
+        if (training) {
+          lhn_set_error("lhn_plan_run: a fused stem launch has no batch statistics (inference plans only)");
+          rc = 1;
+          break;
+        }
+        lhn_view x = mkview(P, ws, o.in_buf[0], o.in_coff[0], o.in_C[0]);
+        lhn_view y = mkview(P, ws, o.out_buf, o.out_coff, o.out_C);
+        rc = lhn_stem_tail_fwd_impl(&x, o.i[0], prm<const float>(params, o.p[0]), prm<const float>(params, o.p[1]),
+                                    o.i[0] ? reinterpret_cast<const float*>(at(ws, P->bufs[o.in_buf[1]].table_off)) : nullptr,
+                                    prm<const float>(params, o.p[2]), prm<const float>(params, o.p[3]),
+                                    reinterpret_cast<const float*>(at(ws, P->bufs[o.in_buf[2]].table_off)), prm<const float>(params, o.p[4]),
+                                    prm<const float>(params, o.p[5]), reinterpret_cast<const float*>(at(ws, o.ws[0])), o.i[1],
+                                    prm<const float>(params, o.p[6]), prm<const float>(params, o.p[7]), &y,
+                                    reinterpret_cast<float*>(at(ws, o.ws[1])), skip_tables ? 0 : 1, 0, stream);
         break;
       }
       case OP_MSRB: {  // one MSRB round.  in[0], in[1]: the x views of the two halves; in[2] and i[1..3] (buffer, first channel, channels):

@@ -10,7 +10,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .plan import CompiledPlan, PlanBuilder, infer_bf16x3_enabled, infer_fuse_bneck_enabled, infer_fuse_dwpw_enabled, infer_fuse_enabled, infer_fuse_msrb_enabled
+from .plan import CompiledPlan, PlanBuilder, infer_bf16x3_enabled, infer_fuse_bneck_enabled, infer_fuse_stem_enabled, infer_fuse_dwpw_enabled, infer_fuse_enabled, infer_fuse_msrb_enabled
 
 
 class PlanModule(nn.Module):
@@ -205,7 +205,7 @@ class Engine:
         if any(getattr(m, "deploy", False) for m in self.module.modules()):
             with_backward = False           # re-parameterised (deploy) form is inference-only
         # inference fusion (plan.set_infer_fuse / LHN_INFER_FUSE, plan.set_infer_fuse_dwpw / LHN_INFER_FUSE_DWPW, plan.set_infer_fuse_msrb /
-        # LHN_INFER_FUSE_MSRB, plan.set_infer_fuse_bneck / LHN_INFER_FUSE_BNECK): never with a backward, and not for train-mode BatchNorm under
+        # LHN_INFER_FUSE_MSRB, plan.set_infer_fuse_bneck / LHN_INFER_FUSE_BNECK, plan.set_infer_fuse_stem / LHN_INFER_FUSE_STEM): never with a backward, and not for train-mode BatchNorm under
         # no_grad -- the fused launch takes its transform from running statistics or deployed biases
         deployed = any(getattr(m, "deploy", False) for m in self.module.modules())
         fuse = bool(infer_fuse_enabled() and not with_backward and (deployed or not self.module.training))
@@ -213,8 +213,9 @@ class Engine:
         fuse_msrb = bool(infer_fuse_msrb_enabled() and not with_backward and (deployed or not self.module.training))
         fuse_bneck = bool(infer_fuse_bneck_enabled() and not with_backward and (deployed or not self.module.training))
         bf16x3 = bool(infer_bf16x3_enabled() and not with_backward and (deployed or not self.module.training))   # plan.set_infer_bf16x3
-        # (fuse stays last, fuse_dwpw before it, fuse_msrb before that: callers index the key from its end)
-        key = (tuple(x.shape), bool(with_backward), float(p_drop), x.device.index, bf16x3, fuse_bneck, fuse_msrb, fuse_dwpw, fuse)
+        fuse_stem = bool(infer_fuse_stem_enabled() and not with_backward and (deployed or not self.module.training))
+        # (fuse stays last, fuse_dwpw before it, fuse_msrb before that: callers index the key from its end; fuse_stem stands ahead of bf16x3)
+        key = (tuple(x.shape), bool(with_backward), float(p_drop), x.device.index, fuse_stem, bf16x3, fuse_bneck, fuse_msrb, fuse_dwpw, fuse)
         plan = self.plans.get(key)
         tensors = self._state(x.device)
         if plan is not None and len(plan.state_tensors) == len(tensors) and all(
@@ -224,7 +225,7 @@ class Engine:
         self._ensure_grads(tensors, x.device)
         index = {id(t): j for j, t in enumerate(tensors)}
         pb = PlanBuilder(N, index, image_hw=(H, W), with_backward=with_backward, p_drop=p_drop, infer_fuse=fuse, infer_fuse_dwpw=fuse_dwpw,
-                         infer_fuse_msrb=fuse_msrb, infer_fuse_bneck=fuse_bneck, infer_bf16x3=bf16x3)
+                         infer_fuse_msrb=fuse_msrb, infer_fuse_bneck=fuse_bneck, infer_bf16x3=bf16x3, infer_fuse_stem=fuse_stem)
         if self.full:
             if Cc != 3:
                 raise _lib.LhnError("the backbone consumes a 3-channel image")

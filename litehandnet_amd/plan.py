@@ -32,6 +32,8 @@ MSRB = 17              # inference plans only: both depthwise branches of an MSR
 CBAM = 18              # the CBAM chain between its `pre` convolutions and its final ReLU (lhn_cbam_fwd), see PlanBuilder.cbam_attention
 BNECK = 19             # inference plans only: BottleNeck (1x1 -> 3x3 -> 1x1 + residual + activation) in one launch (lhn_bottleneck_fwd),
                        # see PlanBuilder.fuse_bottleneck
+STEMTAIL = 20          # inference plans only: the stem after its first convolution (depthwise K x K, 1x1, 3x3 stride 2, max pool, 1x1) in one
+                       # launch (lhn_stem_tail_fwd), see PlanBuilder.fuse_stem
 STEM_BWD, PW_BWD, DW_BWD, KXK_BWD, BN_BWD, EW_BWD, MAXPOOL_BWD, AVGPOOL_BWD, GATE_REDUCE, CA_MLP_BWD, ATT_MLP_BWD, SE_MLP_BWD, SHUFFLE_BWD = range(101, 114)
 CBAM_BWD = 114
 SLOPE_SILU = 2.0       # LHN_SLOPE_SILU in include/lhn.h: the combine applies SiLU instead of a leaky ReLU
@@ -123,6 +125,22 @@ def infer_fuse_bneck_enabled():
     """LHN_INFER_FUSE_BNECK=1 (default off): plans without a backward run each BottleNeck -- 1x1, dense 3x3, 1x1, residual sum and
     activation -- as one launch."""
     return _INFER_FUSE_BNECK if _INFER_FUSE_BNECK is not None else os.environ.get("LHN_INFER_FUSE_BNECK", "0") == "1"
+
+
+_INFER_FUSE_STEM = None     # set_infer_fuse_stem(): in-process override of LHN_INFER_FUSE_STEM
+
+
+def set_infer_fuse_stem(on):
+    """Switch the stem inference fusion pass (PlanBuilder.fuse_stem) on or off for plans built from now on; None = follow the
+    environment again.  Independent of the other switches; Engine.plan_for keys its cache on all of them."""
+    global _INFER_FUSE_STEM
+    _INFER_FUSE_STEM = None if on is None else bool(on)
+
+
+def infer_fuse_stem_enabled():
+    """LHN_INFER_FUSE_STEM=1 (default off): plans without a backward run the stem after its first convolution -- depthwise K x K, 1x1,
+    dense 3x3 stride 2, max pool, concatenation and 1x1 -- as one launch."""
+    return _INFER_FUSE_STEM if _INFER_FUSE_STEM is not None else os.environ.get("LHN_INFER_FUSE_STEM", "0") == "1"
 
 
 _INFER_BF16X3 = None     # set_infer_bf16x3(): in-process override of LHN_INFER_BF16X3
@@ -223,7 +241,7 @@ class _BufRec:
     coef: bool = False
     dpool: bool = False
     lazy: object = None      # the EW record of a sum that is taken ON LOAD by its consumers (never written in forward)
-    fused: bool = False      # a tensor between the convolutions of a PWDW / DWPW / BNECK launch: a table, no data
+    fused: bool = False      # a tensor between the convolutions of a PWDW / DWPW / BNECK / STEMTAIL launch: a table, no data
     off: dict = field(default_factory=dict)
 
 
@@ -268,7 +286,7 @@ class PlanBuilder:
     _no_grad_buf = -1   # the image never needs a gradient
 
     def __init__(self, N, state_index, image_hw=None, with_backward=True, p_drop=0.0, infer_fuse=None, infer_fuse_dwpw=None,
-                 infer_fuse_msrb=None, infer_fuse_bneck=False, infer_bf16x3=False):
+                 infer_fuse_msrb=None, infer_fuse_bneck=False, infer_bf16x3=False, infer_fuse_stem=False):
         self.N = N
         # inference fusion (fuse_pw_dw): None = the process-wide switch.  The fused launch has no batch statistics, so the
         # caller passes False for a plan that will run train-mode BatchNorm under no_grad (Engine.plan_for).
@@ -282,6 +300,8 @@ class PlanBuilder:
         self.n_fused_bneck = 0
         self.infer_bf16x3 = infer_bf16x3_enabled() if infer_bf16x3 is None else bool(infer_bf16x3)   # mark_bf16x3, likewise
         self.n_bf16x3 = 0
+        self.infer_fuse_stem = infer_fuse_stem_enabled() if infer_fuse_stem is None else bool(infer_fuse_stem)   # fuse_stem, likewise
+        self.n_fused_stem = 0
         self.state_index = state_index      # id(tensor) -> index in the params array
         self.bufs = []
         self.recs = []                      # forward records (python dicts)
@@ -1032,13 +1052,14 @@ class PlanBuilder:
             return None
         return q
 
-    def _plain_conv(self, r, kind):
-        """A stride-1 convolution record of `kind` with one plain source and nothing special about its weights or BatchNorm."""
+    def _plain_conv(self, r, kind, biased_bn=False):
+        """A stride-1 convolution record of `kind` with one plain source and nothing special about its weights or BatchNorm (biased_bn:
+        a bias in front of a BatchNorm is fine -- the caller's kernel adds it ahead of the table)."""
         if r is None or r["op"] != kind or r["stride"] != 1 or r["nchw"] or r["wrc"] != (0, 0) or r["bn_repeat"] != 1 or self._xs(r)[1] != 1:
             return False
         if r["x"].buf < 0 or isinstance(r["x"], TCat):
             return False
-        return not (r["bn"] is not None and getattr(r["conv"], "bias", None) is not None)     # as _fusable_dw_pw
+        return biased_bn or not (r["bn"] is not None and getattr(r["conv"], "bias", None) is not None)     # as _fusable_dw_pw
 
     def _fusable_bottleneck(self, r1, uses):
         """(r2, r3, ew) when the 1x1 record r1 starts a BottleNeck pattern, else None: 1x1 C -> Cm, 3x3 Cm -> Cm, 1x1 Cm -> C (slope 1),
@@ -1111,6 +1132,132 @@ class PlanBuilder:
         self.n_fused_bneck += len(at)
         return len(at)
 
+    # What lhn_stem_tail_fwd is built for (csrc/k_stem.hip: stem_tail_supported): (m, C) and the depthwise kernel sizes it absorbs; any map.
+    FUSE_STEM_CHANNELS = (32, 128)
+    FUSE_STEM_K = (3, 7)
+
+    def _whole_fresh(self, t, C):
+        """True when view t is the whole of a C-channel buffer that is ungated, not lazy, not fused and neither the plan's input nor its output."""
+        if isinstance(t, TCat) or t.buf < 0:
+            return False
+        tb = self.bufs[t.buf]
+        if t.coff != 0 or t.C != C or tb.C != C or tb.gate or tb.lazy is not None or tb.fused:
+            return False
+        return not any(v is not None and v.buf == t.buf for v in (self.in_ref, self.out_ref))
+
+    def _fusable_stem(self, mp, uses):
+        """(dw or None, r1, r2, r3) when the MAXPOOL record mp is branch2 of a stem (liteHandNet.py:169-193), else None: mp pools a whole
+        fresh m-channel buffer t into channels [m, 2m) of a 2m-channel buffer cat; t's only other reader is a plain 1x1 (m -> m) whose
+        sole reader is a 3x3 (stride 2, pad 1) into channels [0, m) of cat; cat's sole reader is a plain 1x1 (2m -> C).  dw: t's writer
+        when that is a plain depthwise K x K (K in FUSE_STEM_K, stride 1, pad K / 2) the launch can absorb."""
+        m, Cout = self.FUSE_STEM_CHANNELS
+        t, po = mp["x"], mp["out"]
+        if not self._whole_fresh(t, m) or isinstance(po, TCat) or po.buf < 0 or (po.coff, po.C) != (m, m):
+            return None
+        cat = TRef(po.buf, 0, 2 * m, po.H, po.W)
+        if not self._whole_fresh(cat, 2 * m) or cat.buf == t.buf:
+            return None
+        ok_slope = lambda q: 0.0 <= q.get("slope", 1.0) <= 1.0
+        r1, writers = None, []
+        for u, key in uses.get(t.buf, ()):
+            if key == "out":
+                writers.append(u)
+            elif u is mp and key == "x":
+                continue
+            elif u["op"] == PW and key == "x" and r1 is None:
+                r1 = u
+            else:
+                return None
+        if not self._plain_conv(r1, PW, True) or (r1["x"].coff, r1["x"].C) != (0, m) or not ok_slope(r1) or not self._whole_fresh(r1["out"], m):
+            return None
+        u_ = r1["out"]
+        r2 = self._sole_reader(u_, r1, uses, KXK)
+        if r2 is None or (r2["k"], r2["stride"], r2["pad"], r2["dil"]) != (3, 2, 1, 1) or r2["nchw"] or r2["wrc"] != (0, 0) or \
+                r2["bn_repeat"] != 1 or self._xs(r2)[1] != 1:
+            return None
+        v = r2["out"]
+        if (r2["x"].coff, r2["x"].C) != (0, m) or isinstance(v, TCat) or (v.buf, v.coff, v.C) != (cat.buf, 0, m) or not ok_slope(r2):
+            return None
+        r3 = None
+        for u, key in uses.get(cat.buf, ()):
+            if (u is r2 or u is mp) and key == "out":
+                continue
+            if u["op"] in (FINALIZE, TABLE_FILL) and key == "out" and (u["out"].coff, u["out"].C) == (0, m) and ok_slope(u):
+                continue
+            if u["op"] == PW and key == "x" and r3 is None:
+                r3 = u
+                continue
+            return None
+        if not self._plain_conv(r3, PW) or (r3["x"].coff, r3["x"].C) != (0, 2 * m):
+            return None
+        y = r3["out"]
+        if isinstance(y, TCat) or y.buf < 0 or y.C != Cout or len({t.buf, u_.buf, cat.buf, y.buf}) != 4:
+            return None
+        dw = None
+        convs = [q for q in writers if q["op"] in (STEM, PW, DW, KXK)]
+        if len(convs) == 1 and len(convs) + sum(q["op"] in (FINALIZE, TABLE_FILL) for q in writers) == len(writers):
+            q = convs[0]
+            if q["op"] == DW and q["k"] in self.FUSE_STEM_K and (q["stride"], q["dil"], q["pad"]) == (1, 1, q["k"] // 2) and \
+                    q["conv"].weight is not None and q.get("bn_repeat", 1) == 1 and self._xs(q)[1] == 1 and not isinstance(q["x"], TCat) and \
+                    q["x"].buf >= 0 and q["x"].C == m and q["x"].buf not in (t.buf, u_.buf, cat.buf):
+                dw = q
+        x = dw["x"] if dw is not None else t
+        # every table the launch applies holds a leaky slope: SiLU / relu-sigmoid leave the plan as it is
+        for b in {x.buf, t.buf}:
+            if any(key == "out" and q["op"] in (STEM, PW, DW, KXK, FINALIZE, TABLE_FILL) and not ok_slope(q) for q, key in uses.get(b, ())):
+                return None
+        if y.buf == x.buf and x.coff < y.coff + y.C and y.coff < x.coff + x.C:
+            return None
+        return dw, r1, r2, r3
+
+    def fuse_stem(self):
+        """Inference plans with the switch on (infer_fuse_stem): everything after the stem's first convolution (Stem, liteHandNet.py:169-193;
+        my_pelee_stem, models/pose_hg_ms_att.py:196-228) becomes ONE record (lhn_stem_tail_fwd).  The pass matches the record pattern of
+        _fusable_stem, not the module class.  K = the absorbed depthwise convolution's kernel size (t keeps its table and loses its data),
+        or 0 when t is written by something else (the eval-mode RepBlock sum) and stays.  u and the concatenation buffer become
+        table-only; what fills the tables in the unfused plan stays ahead of the launch (eval: FINALIZE from the running statistics;
+        deployed: the TABLE_FILL records, which stay where they are).  Biases: a 1x1 without a BatchNorm adds its bias while storing,
+        so b1 / b3 ride in the launch; a bias in FRONT of a BatchNorm (mynet's branch1) is folded into the table's shift by the unfused
+        convolution's own finalize, which a FINALIZE record does not do, so it rides in the launch too (bT, b1, b2).
+        The launch stands where the last 1x1 stood.  Runs first in finalize().  Plans with a backward are never rewritten."""
+        if self.with_backward or not self.infer_fuse_stem:
+            return 0
+        uses = {}
+        for r in self.recs:
+            for key, v in r.items():
+                for t in _refs_in(v):
+                    uses.setdefault(t.buf, []).append((r, key))
+        at, drop = {}, set()
+        for mp in self.recs:
+            if mp["op"] != MAXPOOL:
+                continue
+            found = self._fusable_stem(mp, uses)
+            if found is None:
+                continue
+            dw, r1, r2, r3 = found
+            absorbed = [q for q in (dw, r1, r2) if q is not None]
+            if {id(q) for q in absorbed + [mp, r3]} & drop:
+                continue
+            tables = [dict(op=FINALIZE, out=q["out"], bn=q["bn"], slope=q["slope"]) for q in absorbed if q["bn"] is not None]
+            fused = dict(op=STEMTAIL, x=dw["x"] if dw is not None else mp["x"], t=mp["x"], u=r1["out"],
+                         cat=TRef(r2["out"].buf, 0, 2 * r2["out"].C, r2["out"].H, r2["out"].W), out=r3["out"], K=dw["k"] if dw is not None else 0,
+                         dw=dw["conv"] if dw is not None else None, convs=(r1["conv"], r2["conv"], r3["conv"]),
+                         bT=dw["conv"].bias if dw is not None and dw["bn"] is not None else None, b1=r1["conv"].bias,
+                         b2=r2["conv"].bias if r2["bn"] is not None else None, b3=None if r3["bn"] is not None else r3["conv"].bias, wt=r2["wt"])
+            tail = [dict(op=FINALIZE, out=r3["out"], bn=r3["bn"], slope=r3["slope"])] if r3["bn"] is not None else []
+            at[id(r3)] = tables + [fused] + tail
+            drop |= {id(q) for q in absorbed + [mp, r3]}
+            for q in absorbed:
+                self.bufs[q["out"].buf].fused = True       # t (when absorbed), u and -- through v -- the whole concatenation buffer
+        if not at:
+            return 0
+        recs = []
+        for r in self.recs:
+            recs += at.get(id(r), [] if id(r) in drop else [r])
+        self.recs = recs
+        self.n_fused_stem += len(at)
+        return len(at)
+
     def mark_bf16x3(self):
         """Inference plans with the switch on (infer_bf16x3): every dense 3x3 record that bf16x3_eligible accepts runs on the bf16 MFMA
         with a three-term split (lhn_conv_kxk_fwd_bf16x3).  The record stays a KXK record with the same views, parameters and scratch
@@ -1134,6 +1281,7 @@ class PlanBuilder:
     # ------------------------------------------------------------------ finalize: the passes in the order they run
     def finalize(self):
         """Lower the records to what lhn_plan_create takes: (Buf array, forward Op array, backward Op array or None, n_fwd, n_bwd)."""
+        self.fuse_stem()
         self.fuse_msrb_round()
         self.fuse_dw_pw()
         self.fuse_pw_dw()
@@ -1177,7 +1325,7 @@ class PlanBuilder:
     # ------------------------------------------------------------------ forward lowering: one emitter per record family -> [Op]
     def _lower_forward(self):
         emit = {STEM: self._fwd_conv, PW: self._fwd_conv, DW: self._fwd_conv, KXK: self._fwd_conv, PWDW: self._fwd_pwdw, DWPW: self._fwd_dwpw,
-                MSRB: self._fwd_msrb, BNECK: self._fwd_bneck,
+                MSRB: self._fwd_msrb, BNECK: self._fwd_bneck, STEMTAIL: self._fwd_stemtail,
                 FINALIZE: self._fwd_table, TABLE_FILL: self._fwd_table, EW: self._fwd_ew, SHUFFLE: self._fwd_pool,
                 MAXPOOL: self._fwd_pool, AVGPOOL: self._fwd_pool, CA_MLP: self._fwd_ca, SE_MLP: self._fwd_se, ATT_MLP: self._fwd_att,
                 CBAM: self._fwd_cbam}
@@ -1227,6 +1375,16 @@ class PlanBuilder:
         c1, c2, c3 = r["convs"]
         return [self._mk(BNECK, ins=(r["x"], t1, t2), out=r["out"], ws=(self.bufs[t3.buf].off["table"], self._abs(r["wt"])),
                          p=(self._p(c1.weight), self._p(r["b1"]), self._p(c2.weight), self._p(c3.weight), self._p(r["b3"])), f=(r["slope"],))]
+
+    def _fwd_stemtail(self, r):
+        """in: x (K > 0: the depthwise convolution's input; K == 0: t), t and u (tables only); ws[0] = the concatenation buffer's table
+        (its first m channels are v's), ws[1] = the 3x3's tap-major scratch; p = w_dw, bT, w1, b1, w2, b2, w3, b3 (-1 = none: see
+        fuse_stem); i = K, the table's channel count."""
+        c1, c2, c3 = r["convs"]
+        cb = self.bufs[r["cat"].buf]
+        return [self._mk(STEMTAIL, ins=(r["x"], r["t"], r["u"]), out=r["out"], ws=(cb.off["table"], self._abs(r["wt"])),
+                         p=(self._p(r["dw"].weight) if r["dw"] is not None else -1, self._p(r["bT"]), self._p(c1.weight), self._p(r["b1"]),
+                            self._p(c2.weight), self._p(r["b2"]), self._p(c3.weight), self._p(r["b3"])), i=(r["K"], cb.C))]
 
     def _fwd_msrb(self, r):
         """in: the x views of the two halves and the first half's extra source (the second's rides in i[1..3]: an op has three

@@ -1,17 +1,19 @@
-"""Print the forward records of a model's plan (CPU only; no library call).  python scripts/dump_plan.py [A|B] [bs]"""
+"""Print the forward records of a model's plan (CPU only; no library call).  python scripts/dump_plan.py [A|B|M] [bs] [stem]
+(stem: with the stem inference fusion pass, PlanBuilder.fuse_stem, applied)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import collections
 from litehandnet_amd import get_model
 from litehandnet_amd.config import litehandnet_cfg
-from litehandnet_amd.plan import PlanBuilder, STEM, PW, DW, KXK, EW, MAXPOOL, AVGPOOL, CA_MLP, TABLE_FILL, ATT_MLP
+from litehandnet_amd.plan import PlanBuilder, STEM, PW, DW, KXK, EW, MAXPOOL, AVGPOOL, CA_MLP, TABLE_FILL, ATT_MLP, FINALIZE, STEMTAIL
 variant = sys.argv[1] if len(sys.argv) > 1 else "B"
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 64
 m = get_model(litehandnet_cfg(variant))
 tensors = list(m.state_dict(keep_vars=True).values())
-pb = PlanBuilder(N, {id(t): j for j, t in enumerate(tensors)}, image_hw=(256, 256), with_backward=False, p_drop=0.0)
+pb = PlanBuilder(N, {id(t): j for j, t in enumerate(tensors)}, image_hw=(256, 256), with_backward=False, p_drop=0.0, infer_fuse_stem="stem" in sys.argv[3:])
 y = m.emit(pb, pb.image())
-names = {STEM: "stem", PW: "pw", DW: "dw", KXK: "kxk", EW: "ew", MAXPOOL: "maxpool", AVGPOOL: "avgpool", CA_MLP: "ca", TABLE_FILL: "table", ATT_MLP: "ca"}
+pb.fuse_stem()
+names = {STEM: "stem", PW: "pw", DW: "dw", KXK: "kxk", EW: "ew", MAXPOOL: "maxpool", AVGPOOL: "avgpool", CA_MLP: "ca", TABLE_FILL: "table", ATT_MLP: "ca", FINALIZE: "table", STEMTAIL: "stemtail"}
 tot = collections.Counter()
 for r in pb.recs:
     k = r["op"]
@@ -27,6 +29,12 @@ for r in pb.recs:
         o = r["out"]
         mb = N * 4 * o.H * o.W * o.C * (1 + len(r["srcs"])) / 1e6
         print(f"{'ew':8s} " + " + ".join(f"b{s.buf}[{s.coff}:{s.coff + s.C}]{s.H}x{s.W}" for s in r["srcs"]) + f" -> b{o.buf}[{o.coff}:{o.coff + o.C}] {o.H}x{o.W} slope={r['slope']} {mb:.1f}MB")
+    elif k in (TABLE_FILL, FINALIZE):
+        continue
+    elif k == STEMTAIL:
+        x, o = r["x"], r["out"]
+        mb = N * 4 * (x.H * x.W * x.C + o.H * o.W * o.C) / 1e6
+        print(f"{names[k]:8s} in b{x.buf}[{x.coff}:{x.coff + x.C}] {x.H}x{x.W} -> b{o.buf}[{o.coff}:{o.coff + o.C}] {o.H}x{o.W} K{r['K']} (t b{r['t'].buf}, u b{r['u'].buf}, cat b{r['cat'].buf}: tables only) {mb:.1f}MB")
     elif k in (CA_MLP, ATT_MLP):
         yv = r["y"]
         mb = N * 4 * yv.H * yv.W * yv.C / 1e6
