@@ -1059,6 +1059,563 @@ __global__ void __launch_bounds__(1024) k_ca_bwd1(const float* __restrict__ pool
   }
 }
 
+// ---- the same four kernels with every phase paying one memory latency (C <= 128; LHN_CA_MLP_V1=1 keeps the four above).
+// Arithmetic and the order of every sum are those of k_ca1 / k_ca2 / k_ca_bwd2 / k_ca_bwd1, so the bits are too: only when a
+// load is issued and which thread adds a fold change.  The multiply-adds the compiler fuses in those kernels are spelled fmaf / fma
+// here: whether it fuses one depends on the basic block the product lands in, and these kernels cut the blocks differently.
+// Everything whose address is known at entry is loaded at entry (16 bytes wide where the tensors allow) into registers or LDS;
+// the sample-lane count is the constant 32 of the launch.
+#define LHN_CA_NL 32
+__device__ __forceinline__ bool lhn_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+__global__ void __launch_bounds__(1024) k_ca1s(const float* __restrict__ pooled, const float* __restrict__ w3,
+                                              const float* __restrict__ gamma, const float* __restrict__ beta,
+                                              float* __restrict__ rmean, float* __restrict__ rvar, int64_t* __restrict__ nbt,
+                                              const float* __restrict__ mask, float* __restrict__ save, int N, int C,
+                                              float eps, float momentum, int training, int stage, double* __restrict__ gsum,
+                                              double count_scale) {
+  constexpr int NL = LHN_CA_NL;
+  __shared__ double rs[NL][32], rq[NL][32];
+  __shared__ float s_sc[32], s_sh[32];
+  float* a = save;
+  float* ahat = save + (int64_t)N * C;
+  float* smean = save + (int64_t)N * C * 3 + (int64_t)N * (C / 2);
+  float* sinv = smean + C;
+  const int cl = threadIdx.x & 31, nl = threadIdx.x >> 5, c = blockIdx.x * 32 + cl;
+  const bool ok = c < C;
+  // samples nl and nl + NL stay in registers across both barriers; a larger batch walks the rest as k_ca1 does
+  // (the entry loads are unconditional, from indices clamped into the tensors: a value selected against a constant invites the
+  // compiler to move the selection behind the multiply, and the multiply-add would no longer be the fused one of k_ca1)
+  const bool has0 = ok && nl < N, has1 = ok && nl + NL < N;
+  const int cc = min(c, C - 1), n0 = min(nl, N - 1), n1 = min(nl + NL, N - 1);
+  const int64_t i0 = (int64_t)n0 * C + cc, i1 = (int64_t)n1 * C + cc;
+  float wt[9], p0[9], p1[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t) {
+    wt[t] = w3[cc * 9 + t];
+    p0[t] = pooled[((int64_t)n0 * 9 + t) * C + cc];
+    p1[t] = pooled[((int64_t)n1 * 9 + t) * C + cc];
+  }
+  float v0 = 0.f, v1 = 0.f, m0 = 1.f, m1 = 1.f;
+  if (stage == 2) {
+    v0 = a[i0];
+    v1 = a[i1];
+  }
+  if (mask) {
+    m0 = mask[i0];
+    m1 = mask[i1];
+  }
+  float ga = 0.f, be = 0.f, rm = 0.f, rv = 0.f;
+  if (nl == 0 && ok && stage != 1) {
+    if (beta) be = beta[c];
+    if (gamma) {
+      ga = gamma[c];
+      rm = rmean[c];
+      rv = rvar[c];
+    }
+  }
+  double s = 0, q = 0;
+  if (ok && stage != 2) {
+    if (has0) {
+      float v = 0.f;
+#pragma unroll
+      for (int t = 0; t < 9; ++t) v = fmaf(p0[t], wt[t], v);
+      a[i0] = v;
+      s += v;
+      q = fma((double)v, (double)v, q);
+      v0 = v;
+    }
+    if (has1) {
+      float v = 0.f;
+#pragma unroll
+      for (int t = 0; t < 9; ++t) v = fmaf(p1[t], wt[t], v);
+      a[i1] = v;
+      s += v;
+      q = fma((double)v, (double)v, q);
+      v1 = v;
+    }
+    for (int n = nl + 2 * NL; n < N; n += NL) {
+      float v = 0.f;
+#pragma unroll
+      for (int t = 0; t < 9; ++t) v = fmaf(pooled[((int64_t)n * 9 + t) * C + c], wt[t], v);
+      a[(int64_t)n * C + c] = v;
+      s += v;
+      q = fma((double)v, (double)v, q);
+    }
+  }
+  rs[nl][cl] = s;
+  rq[nl][cl] = q;
+  __syncthreads();
+  if (nl == 0 && ok) {
+#pragma unroll
+    for (int j = 1; j < NL; ++j) {
+      s += rs[j][cl];
+      q += rq[j][cl];
+    }
+    if (stage == 1) {
+      gsum[c] = s;
+      gsum[C + c] = q;
+    } else if (stage == 2) {
+      s = gsum[c];
+      q = gsum[C + c];
+    }
+  }
+  if (stage == 1) return;
+  const double NT = (double)N * count_scale;
+  if (nl == 0 && ok) {
+    double mean, var;
+    if (!gamma) {          // deployed attention: the BatchNorm is folded, `beta` is the conv bias
+      smean[c] = 0.f;
+      sinv[c] = 1.f;
+      s_sc[cl] = 1.f;
+      s_sh[cl] = beta ? be : 0.f;
+    } else {
+    if (training) {
+      mean = s / NT;
+      var = q / NT - mean * mean;
+      if (var < 0) var = 0;
+      rmean[c] = (float)((1.0 - (double)momentum) * rm + (double)momentum * mean);
+      rvar[c] = (float)((1.0 - (double)momentum) * rv + (double)momentum * (NT > 1 ? var * NT / (NT - 1.0) : var));
+    } else {
+      mean = rm;
+      var = rv;
+    }
+    const float invstd = (float)(1.0 / sqrt(var + (double)eps));
+    smean[c] = (float)mean;
+    sinv[c] = invstd;
+    s_sc[cl] = ga * invstd;
+    s_sh[cl] = be - (float)mean * (ga * invstd);
+    }
+  }
+  __syncthreads();
+  if (ok) {
+    const float sc = s_sc[cl], sh = s_sh[cl];
+    if (has0) {
+      float v = fmaf(v0, sc, sh);
+      if (mask) v *= m0;
+      ahat[i0] = v;
+    }
+    if (has1) {
+      float v = fmaf(v1, sc, sh);
+      if (mask) v *= m1;
+      ahat[i1] = v;
+    }
+    for (int n = nl + 2 * NL; n < N; n += NL) {
+      float v = fmaf(a[(int64_t)n * C + c], sc, sh);
+      if (mask) v *= mask[(int64_t)n * C + c];
+      ahat[(int64_t)n * C + c] = v;
+    }
+  }
+  if (training && nbt && blockIdx.x == 0 && threadIdx.x == 0) nbt[0] += 1;
+}
+
+// One workgroup of 256 per sample.  Both weight matrices (C <= 128: 2 x 32 KB) are in flight at entry as 16-byte loads by all
+// threads and land in LDS with odd row strides, where the output threads walk their rows without bank conflicts.
+#define LHN_CA_CMAX 128
+__global__ void __launch_bounds__(256) k_ca2s(const float* __restrict__ w1, const float* __restrict__ b1,
+                                              const float* __restrict__ w2, const float* __restrict__ b2,
+                                              float* __restrict__ save, float* __restrict__ gate, int gs, int gcoff, int N,
+                                              int C) {
+  constexpr int CM = LHN_CA_CMAX, HM = CM / 2, PER = CM * HM / 4 / 256;      // 16-byte loads per thread and matrix
+  __shared__ float sw1[HM * (CM + 1)], sw2[CM * (HM + 1)], sa[CM], shh[HM];
+  const int n = blockIdx.x, Ch = C / 2, nw = C * Ch, tid = threadIdx.x;
+  const float* ahat = save + (int64_t)N * C + (int64_t)n * C;
+  float* h = save + (int64_t)N * C * 2 + (int64_t)n * Ch;
+  float* g = save + (int64_t)N * C * 2 + (int64_t)N * Ch + (int64_t)n * C;
+  const float av = tid < C ? ahat[tid] : 0.f;
+  const float bias1 = tid < Ch ? b1[tid] : 0.f, bias2 = tid < C ? b2[tid] : 0.f;
+  if ((C & 7) == 0 && lhn_al16(w1) && lhn_al16(w2)) {       // rows of both matrices are whole 16-byte groups
+    f4 r1[PER], r2[PER];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      const int i = tid + k * 256;
+      r1[k] = 4 * i < nw ? reinterpret_cast<const f4*>(w1)[i] : (f4){0.f, 0.f, 0.f, 0.f};
+      r2[k] = 4 * i < nw ? reinterpret_cast<const f4*>(w2)[i] : (f4){0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      const int i = 4 * (tid + k * 256);
+      if (i < nw) {
+        const int ra = i / C, rb = i / Ch;
+        float* d1 = sw1 + ra * (C + 1) + (i - ra * C);
+        float* d2 = sw2 + rb * (Ch + 1) + (i - rb * Ch);
+        d1[0] = r1[k].x; d1[1] = r1[k].y; d1[2] = r1[k].z; d1[3] = r1[k].w;
+        d2[0] = r2[k].x; d2[1] = r2[k].y; d2[2] = r2[k].z; d2[3] = r2[k].w;
+      }
+    }
+  } else {
+    for (int i = tid; i < nw; i += 256) {
+      const int ra = i / C, rb = i / Ch;
+      sw1[ra * (C + 1) + (i - ra * C)] = w1[i];
+      sw2[rb * (Ch + 1) + (i - rb * Ch)] = w2[i];
+    }
+  }
+  if (tid < C) sa[tid] = av;
+  __syncthreads();
+  if (tid < Ch) {
+    const float* row = sw1 + tid * (C + 1);
+    float v = bias1;
+    for (int c = 0; c < C; ++c) v = fmaf(row[c], sa[c], v);
+    v = lhn_lrelu(v, 0.01f);
+    h[tid] = v;
+    shh[tid] = v;
+  }
+  __syncthreads();
+  if (tid < C) {
+    const float* row = sw2 + tid * (Ch + 1);
+    float v = bias2;
+    for (int j = 0; j < Ch; ++j) v = fmaf(row[j], shh[j], v);
+    const float sg = 1.f / (1.f + expf(-v));
+    g[tid] = sg;
+    gate[(int64_t)n * gs + gcoff + tid] = sg;
+  }
+}
+
+// One workgroup of 256 per sample: both matrices, the gate, its gradient and h in flight at entry; the mat-vec threads read LDS.
+__global__ void __launch_bounds__(256) k_ca_bwd2s(const float* __restrict__ w1, const float* __restrict__ w2,
+                                                  const float* __restrict__ save, const float* __restrict__ dgate,
+                                                  float* __restrict__ dahat /*[N][C]*/, float* __restrict__ dvbuf /*[N][C]*/,
+                                                  float* __restrict__ dhbuf /*[N][C/2]*/, int N, int C) {
+  constexpr int CM = LHN_CA_CMAX, HM = CM / 2, PER = CM * HM / 4 / 256;
+  __shared__ __align__(16) float sw1[HM * CM], sw2[CM * HM];
+  __shared__ float sdv[CM], sdh[HM], shh[HM];
+  const int Ch = C / 2, n = blockIdx.x, nw = C * Ch, tid = threadIdx.x;
+  const float* h = save + (int64_t)N * C * 2 + (int64_t)n * Ch;
+  const float* g = save + (int64_t)N * C * 2 + (int64_t)N * Ch + (int64_t)n * C;
+  const float gg = tid < C ? g[tid] : 0.f, dg = tid < C ? dgate[(int64_t)n * C + tid] : 0.f;
+  const float hv = tid < Ch ? h[tid] : 0.f;
+  if ((nw & 3) == 0 && lhn_al16(w1) && lhn_al16(w2)) {
+    f4 r1[PER], r2[PER];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      const int i = tid + k * 256;
+      r2[k] = 4 * i < nw ? reinterpret_cast<const f4*>(w2)[i] : (f4){0.f, 0.f, 0.f, 0.f};
+      r1[k] = 4 * i < nw ? reinterpret_cast<const f4*>(w1)[i] : (f4){0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      const int i = tid + k * 256;
+      if (4 * i < nw) {
+        reinterpret_cast<f4*>(sw2)[i] = r2[k];
+        reinterpret_cast<f4*>(sw1)[i] = r1[k];
+      }
+    }
+  } else {
+    for (int i = tid; i < nw; i += 256) {
+      sw2[i] = w2[i];
+      sw1[i] = w1[i];
+    }
+  }
+  if (tid < C) {
+    const float dv = dg * gg * (1.f - gg);
+    sdv[tid] = dv;
+    dvbuf[(int64_t)n * C + tid] = dv;
+  }
+  if (tid < Ch) shh[tid] = hv;
+  __syncthreads();
+  if (tid < Ch) {
+    float d = 0.f;
+    for (int c = 0; c < C; ++c) d = fmaf(sw2[c * Ch + tid], sdv[c], d);
+    d *= shh[tid] > 0.f ? 1.f : 0.01f;
+    sdh[tid] = d;
+    dhbuf[(int64_t)n * Ch + tid] = d;
+  }
+  __syncthreads();
+  if (tid < C) {
+    float d = 0.f;
+    for (int j = 0; j < Ch; ++j) d = fmaf(sw1[j * C + tid], sdh[j], d);
+    dahat[(int64_t)n * C + tid] = d;
+  }
+}
+
+// one (sample, channel) of k_ca_bwd1's second loop: dw3 partials, the 25 pooled-gradient segments, the slice sums' addends
+struct CaBwdRow {
+  float d, xh, pl[9], g, t0, t1, ps[18];
+};
+// Workgroups of 512: 16 channel lanes x 32 sample lanes, so that a thread may hold every operand of its two samples (149
+// registers; a 1024-thread workgroup has 128 per thread, and k_ca_bwd1 spills 17 of them into scratch memory as it is).
+#define LHN_CA_CL 16
+#define LHN_CA_TB (LHN_CA_CL * LHN_CA_NL)
+__global__ void __launch_bounds__(LHN_CA_TB) k_ca_bwd1s(const float* __restrict__ pooled, const float* __restrict__ w3,
+                                                  const float* __restrict__ gamma, const float* __restrict__ mask,
+                                                  const float* __restrict__ save, const float* __restrict__ dahat,
+                                                  float* __restrict__ dpool, int cs, int coff, int H, int W,
+                                                  float* __restrict__ dw3, float* __restrict__ dgamma,
+                                                  float* __restrict__ dbeta, int N, int C, int training, int stage,
+                                                  double* __restrict__ gsum, double count_scale, float pgrad_scale,
+                                                  const float* __restrict__ tsum, const float* __restrict__ pstat, BnSlices sl,
+                                                  const float* __restrict__ dvbuf, const float* __restrict__ dhbuf,
+                                                  float* __restrict__ dw1, float* __restrict__ db1, float* __restrict__ dw2,
+                                                  float* __restrict__ db2) {
+  constexpr int NL = LHN_CA_NL, CL = LHN_CA_CL, TB = LHN_CA_TB, CM = LHN_CA_CMAX, HM = CM / 2, NS = 64;      // NS: samples per staging round of the extra workgroups
+  __shared__ __align__(16) float smem[NS * 3 * CM];                             // dv | h | dh | ahat rows, or the main workgroups' folds
+  const int nmain = (C + CL - 1) / CL, tid = threadIdx.x;
+  if ((int)blockIdx.x >= nmain) {
+    // ---- extra workgroups: parameter gradients of the two 1x1 layers.  One thread per weight as in k_ca_bwd1; the dv / h rows
+    // (dW2, db2) and the dh / ahat rows (dW1, db1) of up to NS samples arrive in LDS with one round of 16-byte loads, then each
+    // thread adds the samples in ascending order.
+    if (stage == 1) return;
+    const int Ch = C / 2, nw = C * Ch, o0 = ((int)blockIdx.x - nmain) * TB, o = o0 + tid;
+    const int oend = 2 * nw + C + Ch, o1 = min(o0 + TB, oend);
+    const bool needA = o0 < nw || (o1 > 2 * nw && o0 < 2 * nw + C), needB = (o1 > nw && o0 < 2 * nw) || o1 > 2 * nw + C;
+    float* sdv = smem;
+    float* sh = smem + NS * CM;
+    float* sdh = sh + NS * HM;
+    float* sah = sdh + NS * HM;
+    const float* ahat = save + (int64_t)N * C;
+    const float* hh = save + (int64_t)N * C * 2;
+    int kind = -1, ia = 0, ib = 0;
+    float* dst = nullptr;
+    if (o < nw) {                                                         // dW2[c][j] = sum_n dv[n][c] * h[n][j]
+      kind = 0; ia = o / Ch; ib = o - ia * Ch; dst = dw2 + o;
+    } else if (o < 2 * nw) {                                              // dW1[j][c] = sum_n dh[n][j] * ahat[n][c]
+      const int q = o - nw;
+      kind = 1; ia = q / C; ib = q - ia * C; dst = dw1 + q;
+    } else if (o < 2 * nw + C) {                                          // db2[c] = sum_n dv[n][c]
+      kind = 2; ia = o - 2 * nw; dst = db2 + ia;
+    } else if (o < oend) {                                                // db1[j] = sum_n dh[n][j]
+      kind = 3; ia = o - 2 * nw - C; dst = db1 + ia;
+    }
+    float acc = dst ? *dst : 0.f;
+    const bool vec = (C & 7) == 0 && lhn_al16(dvbuf) && lhn_al16(dhbuf) && lhn_al16(ahat) && lhn_al16(hh);
+    float v = 0.f;
+    for (int n0 = 0; n0 < N; n0 += NS) {
+      const int cnt = min(NS, N - n0);
+      if (n0) __syncthreads();
+      if (vec) {
+        const int nc4 = cnt * C / 4, nh4 = cnt * Ch / 4;
+        const f4 z = (f4){0.f, 0.f, 0.f, 0.f};
+        const f4* gdv = reinterpret_cast<const f4*>(dvbuf + (int64_t)n0 * C);
+        const f4* gah = reinterpret_cast<const f4*>(ahat + (int64_t)n0 * C);
+        const f4* gh = reinterpret_cast<const f4*>(hh + (int64_t)n0 * Ch);
+        const f4* gdh = reinterpret_cast<const f4*>(dhbuf + (int64_t)n0 * Ch);
+        f4 xa[4], xb[4], xh[2], xd[2];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          xa[u] = needA && tid + u * TB < nc4 ? gdv[tid + u * TB] : z;
+          xb[u] = needB && tid + u * TB < nc4 ? gah[tid + u * TB] : z;
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          xh[u] = needA && tid + u * TB < nh4 ? gh[tid + u * TB] : z;
+          xd[u] = needB && tid + u * TB < nh4 ? gdh[tid + u * TB] : z;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          if (needA && tid + u * TB < nc4) reinterpret_cast<f4*>(sdv)[tid + u * TB] = xa[u];
+          if (needB && tid + u * TB < nc4) reinterpret_cast<f4*>(sah)[tid + u * TB] = xb[u];
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          if (needA && tid + u * TB < nh4) reinterpret_cast<f4*>(sh)[tid + u * TB] = xh[u];
+          if (needB && tid + u * TB < nh4) reinterpret_cast<f4*>(sdh)[tid + u * TB] = xd[u];
+        }
+      } else {
+        for (int i = tid; i < cnt * C; i += TB) {
+          if (needA) sdv[i] = dvbuf[(int64_t)n0 * C + i];
+          if (needB) sah[i] = ahat[(int64_t)n0 * C + i];
+        }
+        for (int i = tid; i < cnt * Ch; i += TB) {
+          if (needA) sh[i] = hh[(int64_t)n0 * Ch + i];
+          if (needB) sdh[i] = dhbuf[(int64_t)n0 * Ch + i];
+        }
+      }
+      __syncthreads();
+      if (kind == 0) {
+#pragma unroll 8
+        for (int n = 0; n < cnt; ++n) v = fmaf(sdv[n * C + ia], sh[n * Ch + ib], v);
+      } else if (kind == 1) {
+#pragma unroll 8
+        for (int n = 0; n < cnt; ++n) v = fmaf(sdh[n * Ch + ia], sah[n * C + ib], v);
+      } else if (kind == 2) {
+#pragma unroll 8
+        for (int n = 0; n < cnt; ++n) v += sdv[n * C + ia];
+      } else if (kind == 3) {
+#pragma unroll 8
+        for (int n = 0; n < cnt; ++n) v += sdh[n * Ch + ia];
+      }
+    }
+    if (dst) {
+      acc += v;
+      *dst = acc;
+    }
+    return;
+  }
+  double(*rs)[CL] = reinterpret_cast<double(*)[CL]>(smem);                    // [NL][CL] each
+  double(*rq)[CL] = rs + NL;
+  float(*rw)[CL][9] = reinterpret_cast<float(*)[CL][9]>(rq + NL);            // [NL][CL][9]
+  const float* a = save;
+  const float* smean = save + (int64_t)N * C * 3 + (int64_t)N * (C / 2);
+  const float* sinv = smean + C;
+  const float* gsave = save + (int64_t)N * C * 2 + (int64_t)N * (C / 2);      // sigmoid gate g[n][c] of the forward
+  const int cl = tid % CL, nl = tid / CL, c = blockIdx.x * CL + cl;
+  const bool ok = c < C;
+  // ---- entry: every operand of both loops for samples nl and nl + NL
+  // (unconditional, from indices clamped into the tensors: see k_ca1s)
+  const int cc = min(c, C - 1);
+  const float mean = smean[cc], invstd = sinv[cc], gm = gamma[cc];
+  float wt[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t) wt[t] = w3[cc * 9 + t];
+  CaBwdRow r[2];
+  bool has[2];
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    has[k] = ok && nl + k * NL < N;
+    const int n = min(nl + k * NL, N - 1);
+    const int64_t i = (int64_t)n * C + cc;
+    r[k].d = dahat[i];
+    const float av = a[i];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) r[k].pl[t] = pooled[((int64_t)n * 9 + t) * C + cc];
+    if (tsum) {
+      r[k].g = gsave[i];
+      r[k].t0 = tsum[((int64_t)n * 2 + 0) * C + cc];
+      r[k].t1 = tsum[((int64_t)n * 2 + 1) * C + cc];
+#pragma unroll
+      for (int t = 0; t < 18; ++t) r[k].ps[t] = pstat[((int64_t)n * 18 + t) * C + cc];
+    }
+    if (mask) r[k].d *= mask[i];
+    r[k].xh = (av - mean) * invstd;
+  }
+  float dg0 = 0.f, db0 = 0.f;
+  if (nl == 0 && ok && stage != 1) {
+    dg0 = dgamma[c];
+    db0 = dbeta[c];
+  }
+  double sd = 0, sdx = 0;
+  if (ok && stage != 2) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+      if (has[k]) {
+        sd += r[k].d;
+        sdx = fma((double)r[k].d, (double)r[k].xh, sdx);
+      }
+    for (int n = nl + 2 * NL; n < N; n += NL) {
+      float d = dahat[(int64_t)n * C + c];
+      if (mask) d *= mask[(int64_t)n * C + c];
+      const float xh = (a[(int64_t)n * C + c] - mean) * invstd;
+      sd += d;
+      sdx = fma((double)d, (double)xh, sdx);
+    }
+  }
+  rs[nl][cl] = sd;
+  rq[nl][cl] = sdx;
+  __syncthreads();
+  sd = 0;
+  sdx = 0;
+#pragma unroll
+  for (int j = 0; j < NL; ++j) {
+    sd += rs[j][cl];
+    sdx += rq[j][cl];
+  }
+  if (stage == 1) {
+    if (nl == 0 && ok) {
+      gsum[c] = sd;
+      gsum[C + c] = sdx;
+    }
+    return;
+  }
+  if (stage == 2 && ok) {
+    sd = gsum[c];
+    sdx = gsum[C + c];
+  }
+  const double NT = (double)N * count_scale;
+  if (nl == 0 && ok) {
+    dg0 = fmaf((float)sdx, pgrad_scale, dg0);
+    db0 = fmaf((float)sd, pgrad_scale, db0);
+    dgamma[c] = dg0;
+    dbeta[c] = db0;
+  }
+  double bs0 = 0, bs1 = 0;
+  float dwt[9], binv[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t) {
+    dwt[t] = 0.f;
+    const int bi = t / 3, bj = t % 3;
+    binv[t] = 1.f / (float)((lhn_bin_hi(bi, H) - lhn_bin_lo(bi, H)) * (lhn_bin_hi(bj, W) - lhn_bin_lo(bj, W)));
+  }
+  auto row = [&](int n, const CaBwdRow& x) {
+    float da = gm * invstd * x.d;
+    if (training) da = gm * invstd * fmaf(-x.xh, (float)(sdx / NT), x.d - (float)(sd / NT));
+    float dseg[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      dwt[t] = fmaf(da, x.pl[t], dwt[t]);
+      dseg[t] = da * wt[t] * binv[t];
+    }
+    lhn_dpool_store(dpool, n, cs, coff + c, dseg);
+    if (tsum) {
+      // (k_ca_bwd1's `g * T + dseg[0] * M[0]` compiles to the left product fused onto the right one)
+      float a0 = fmaf(x.g, x.t0, dseg[0] * x.ps[0]), a1 = fmaf(x.g, x.t1, dseg[0] * x.ps[1]);
+#pragma unroll
+      for (int t = 1; t < 9; ++t) {
+        a0 = fmaf(dseg[t], x.ps[2 * t], a0);
+        a1 = fmaf(dseg[t], x.ps[2 * t + 1], a1);
+      }
+      bs0 += a0;
+      bs1 += a1;
+    }
+  };
+  if (ok) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+      if (has[k]) row(nl + k * NL, r[k]);
+    for (int n = nl + 2 * NL; n < N; n += NL) {
+      CaBwdRow x;
+      const int64_t i = (int64_t)n * C + c;
+      x.d = dahat[i];
+      if (mask) x.d *= mask[i];
+      x.xh = (a[i] - mean) * invstd;
+#pragma unroll
+      for (int t = 0; t < 9; ++t) x.pl[t] = pooled[((int64_t)n * 9 + t) * C + c];
+      if (tsum) {
+        x.g = gsave[i];
+        x.t0 = tsum[((int64_t)n * 2 + 0) * C + c];
+        x.t1 = tsum[((int64_t)n * 2 + 1) * C + c];
+#pragma unroll
+        for (int t = 0; t < 18; ++t) x.ps[t] = pstat[((int64_t)n * 18 + t) * C + c];
+      }
+      row(n, x);
+    }
+  }
+  if (tsum) {
+    __syncthreads();          // rs / rq are free again
+    rs[nl][cl] = bs0;
+    rq[nl][cl] = bs1;
+  }
+#pragma unroll
+  for (int t = 0; t < 9; ++t) rw[nl][cl][t] = dwt[t];
+  __syncthreads();
+  if (tsum && nl == 0 && ok) {
+    double t0 = 0, t1 = 0;
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+      t0 += rs[j][cl];
+      t1 += rq[j][cl];
+    }
+    const int cb = coff + c;                    // channel of the gated buffer
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+      if (k < sl.n && sl.sums[k] && cb >= sl.lo[k] && cb < sl.lo[k] + sl.C[k]) {   // this block is the channel's only writer
+        sl.sums[k][cb - sl.lo[k]] = t0;
+        sl.sums[k][sl.C[k] + cb - sl.lo[k]] = t1;
+      }
+  }
+  // the 9 x CL dw3 sums, one thread each (waves 1..3, beside the slice sums of wave 0), 32 partials in lane order
+  const int ft = tid - 64;
+  if (ft >= 0 && ft < 9 * CL) {
+    const int t = ft / CL, fc = ft % CL, c2 = blockIdx.x * CL + fc;
+    if (c2 < C) {
+      const float old = dw3[c2 * 9 + t];
+      float v = 0.f;
+#pragma unroll
+      for (int j = 0; j < NL; ++j) v += rw[j][fc][t];
+      dw3[c2 * 9 + t] = old + v;
+    }
+  }
+}
+
 // ------------------------------------------------------------------ BatchNorm backward reductions
 // sums[0][c] = sum du, sums[1][c] = sum du * xhat   over all pixels (du: gradient at the BN output)
 __global__ void __launch_bounds__(256) k_bn_bwd_reduce(lhn_view y, lhn_gradview g, const float* __restrict__ save,
@@ -1449,6 +2006,18 @@ int lhn_avgpool_bwd3(const lhn_view* x, const float* dout, int OH, int OW, int o
   return 0;
 }
 
+// LHN_CA_MLP_V1=1 (read once): the attention MLP runs k_ca1 / k_ca2 / k_ca_bwd2 / k_ca_bwd1 instead of the staged kernels
+// k_ca1s / k_ca2s / k_ca_bwd2s / k_ca_bwd1s.  The staged kernels hold both weight matrices in LDS, which C <= 128 allows;
+// a wider attention takes the first four whatever the switch says.  Both sets give the same bits.
+static bool lhn_ca_mlp_staged(int C) {
+  static int v = -1;
+  if (v < 0) {
+    const char* e = getenv("LHN_CA_MLP_V1");
+    v = (e && e[0] == '1') ? 1 : 0;
+  }
+  return v == 0 && C <= LHN_CA_CMAX;
+}
+
 int lhn_ca_mlp_fwd(const float* pooled, const float* w3, const float* gamma, const float* beta, float* rmean, float* rvar,
                    int64_t* nbt, const float* w1, const float* b1, const float* w2, const float* b2, const float* dropmask,
                    float* gate, int gate_stride, int gate_coff, float* save, int N, int C, float eps, float momentum,
@@ -1460,8 +2029,13 @@ int lhn_ca_mlp_fwd(const float* pooled, const float* w3, const float* gamma, con
   LHN_CHECK_ARG(stage == 0 || (gsum && stage >= 1 && stage <= 2 && count_scale >= 1), "lhn_ca_mlp_fwd: stage %d needs gsum", stage);
   // (one launch for both kernels -- every workgroup recomputing the batch statistics from the pooled tensor -- was measured
   // slower than the two launches: forward of the MSRB hourglass 2.770 vs 2.714 ms, round 3)
-  hipLaunchKernelGGL(k_ca1, dim3((C + 31) / 32), dim3(1024), 0, s, pooled, w3, gamma, beta, rmean, rvar, nbt, dropmask, save, N, C, eps, momentum, training, stage, gsum, stage ? count_scale : 1.0);
-  if (stage != 1) hipLaunchKernelGGL(k_ca2, dim3(N), dim3(128), 0, s, w1, b1, w2, b2, save, gate, gate_stride, gate_coff, N, C);
+  if (lhn_ca_mlp_staged(C)) {
+    hipLaunchKernelGGL(k_ca1s, dim3((C + 31) / 32), dim3(1024), 0, s, pooled, w3, gamma, beta, rmean, rvar, nbt, dropmask, save, N, C, eps, momentum, training, stage, gsum, stage ? count_scale : 1.0);
+    if (stage != 1) hipLaunchKernelGGL(k_ca2s, dim3(N), dim3(256), 0, s, w1, b1, w2, b2, save, gate, gate_stride, gate_coff, N, C);
+  } else {
+    hipLaunchKernelGGL(k_ca1, dim3((C + 31) / 32), dim3(1024), 0, s, pooled, w3, gamma, beta, rmean, rvar, nbt, dropmask, save, N, C, eps, momentum, training, stage, gsum, stage ? count_scale : 1.0);
+    if (stage != 1) hipLaunchKernelGGL(k_ca2, dim3(N), dim3(128), 0, s, w1, b1, w2, b2, save, gate, gate_stride, gate_coff, N, C);
+  }
   LHN_CHECK_LAUNCH("lhn_ca_mlp_fwd");
   return 0;
 }
@@ -1521,6 +2095,14 @@ int lhn_ca_mlp_bwd2(const float* pooled, const float* w3, const float* gamma, co
   float* dvbuf = dahat + (int64_t)N * C;
   float* dhbuf = dvbuf + (int64_t)N * C;
   LHN_CHECK_ARG(stage == 0 || (gsum && stage >= 1 && stage <= 2 && count_scale >= 1), "lhn_ca_mlp_bwd: stage %d needs gsum", stage);
+  const bool staged = lhn_ca_mlp_staged(C) && N > 0;
+  if (staged) {
+    const dim3 grids((C + LHN_CA_CL - 1) / LHN_CA_CL + (C * C + C + C / 2 + LHN_CA_TB - 1) / LHN_CA_TB);
+    if (stage != 2) hipLaunchKernelGGL(k_ca_bwd2s, dim3(N), dim3(256), 0, s, w1, w2, save, dgate, dahat, dvbuf, dhbuf, N, C);
+    hipLaunchKernelGGL(k_ca_bwd1s, grids, dim3(LHN_CA_TB), 0, s, pooled, w3, gamma, dropmask, save, dahat, dpool, cstride, coff, H, W, dw3, dgamma, dbeta, N, C, 1, stage, gsum, stage ? count_scale : 1.0, stage ? pgrad_scale : 1.f, tsum, pstat, sl, dvbuf, dhbuf, dw1, db1, dw2, db2);
+    LHN_CHECK_LAUNCH("lhn_ca_mlp_bwd");
+    return 0;
+  }
   if (stage != 2) hipLaunchKernelGGL(k_ca_bwd2, dim3(N), dim3(256), 0, s, w1, w2, save, dgate, dahat, dvbuf, dhbuf, N, C);
   hipLaunchKernelGGL(k_ca_bwd1, dim3((C + 31) / 32 + (C * C + C + C / 2 + 1023) / 1024), dim3(1024), 0, s, pooled, w3, gamma, dropmask, save, dahat, dpool, cstride, coff, H, W, dw3, dgamma, dbeta, N, C, 1, stage, gsum, stage ? count_scale : 1.0, stage ? pgrad_scale : 1.f, tsum, pstat, sl, dvbuf, dhbuf, dw1, db1, dw2, db2);
   LHN_CHECK_LAUNCH("lhn_ca_mlp_bwd");
