@@ -65,98 +65,98 @@ def _switch(name):
     return os.environ.get(name, "1") != "0"
 
 
-_INFER_FUSE = None     # set_infer_fuse(): in-process override of LHN_INFER_FUSE
+# Inference switches: opt-in rewrites of plans without a backward.  One row per switch, in the order finalize() runs the passes:
+# (PlanBuilder attribute and keyword, environment variable, pass method, counter attribute, what the pass does).  Every one is off
+# unless NAME=1 is in the environment or its set_* function below switched it on in the process.  PlanBuilder's keywords differ in
+# their defaults, and tests rely on it: infer_fuse, infer_fuse_dwpw and infer_fuse_msrb default to None = follow the process switch,
+# infer_fuse_bneck, infer_bf16x3 and infer_fuse_stem to False (Engine.plan_for passes all six).
+INFER_SWITCHES = (
+    ("infer_fuse_stem", "LHN_INFER_FUSE_STEM", "fuse_stem", "n_fused_stem", "the stem after its first convolution is one launch"),
+    ("infer_fuse_msrb", "LHN_INFER_FUSE_MSRB", "fuse_msrb_round", "n_fused_msrb", "an MSRB round and its attention's pooling are one pass"),
+    ("infer_fuse_dwpw", "LHN_INFER_FUSE_DWPW", "fuse_dw_pw", "n_fused_dwpw", "DWConv's depthwise 3x3 -> 1x1 is one launch"),
+    ("infer_fuse", "LHN_INFER_FUSE", "fuse_pw_dw", "n_fused", "RepBasicUnit's 1x1 -> depthwise 3x3 is one launch"),
+    ("infer_fuse_bneck", "LHN_INFER_FUSE_BNECK", "fuse_bottleneck", "n_fused_bneck", "a BottleNeck is one launch"),
+    ("infer_bf16x3", "LHN_INFER_BF16X3", "mark_bf16x3", "n_bf16x3", "dense 3x3 convolutions run on the split-bf16 MFMA"),
+)
+_INFER_ENV = {row[0]: row[1] for row in INFER_SWITCHES}
+_INFER_OVERRIDE = {}       # switch name -> bool: what _set_infer_switch put in front of the environment
+
+
+def _infer_switch(name):
+    """State of an inference switch now: the in-process override if there is one, else NAME=1 in the environment (default off)."""
+    on = _INFER_OVERRIDE.get(name)
+    return on if on is not None else os.environ.get(_INFER_ENV[name], "0") == "1"
+
+
+def _set_infer_switch(name, on):
+    """Switch an inference pass on or off for plans built from now on; None = follow the environment again.  The switches are
+    independent of each other, and Engine.plan_for keys its cache on all of them, so the next forward builds the matching plan."""
+    assert name in _INFER_ENV, name
+    _INFER_OVERRIDE[name] = None if on is None else bool(on)
 
 
 def set_infer_fuse(on):
-    """Switch the inference fusion pass (PlanBuilder.fuse_pw_dw) on or off for plans built from now on; None = follow the
-    environment again.  Engine.plan_for keys its cache on the switch, so the next forward builds the matching plan."""
-    global _INFER_FUSE
-    _INFER_FUSE = None if on is None else bool(on)
+    """_set_infer_switch for the 1x1 -> depthwise 3x3 inference fusion pass (PlanBuilder.fuse_pw_dw)."""
+    _set_infer_switch("infer_fuse", on)
 
 
 def infer_fuse_enabled():
     """LHN_INFER_FUSE=1 (default off): plans without a backward run RepBasicUnit's 1x1 -> depthwise 3x3 pairs as one launch."""
-    return _INFER_FUSE if _INFER_FUSE is not None else os.environ.get("LHN_INFER_FUSE", "0") == "1"
-
-
-_INFER_FUSE_DWPW = None     # set_infer_fuse_dwpw(): in-process override of LHN_INFER_FUSE_DWPW
+    return _infer_switch("infer_fuse")
 
 
 def set_infer_fuse_dwpw(on):
-    """Switch the depthwise -> 1x1 inference fusion pass (PlanBuilder.fuse_dw_pw) on or off for plans built from now on; None =
-    follow the environment again.  Independent of set_infer_fuse; Engine.plan_for keys its cache on both."""
-    global _INFER_FUSE_DWPW
-    _INFER_FUSE_DWPW = None if on is None else bool(on)
+    """_set_infer_switch for the depthwise -> 1x1 inference fusion pass (PlanBuilder.fuse_dw_pw)."""
+    _set_infer_switch("infer_fuse_dwpw", on)
 
 
 def infer_fuse_dwpw_enabled():
     """LHN_INFER_FUSE_DWPW=1 (default off): plans without a backward run DWConv's depthwise 3x3 -> 1x1 pairs as one launch."""
-    return _INFER_FUSE_DWPW if _INFER_FUSE_DWPW is not None else os.environ.get("LHN_INFER_FUSE_DWPW", "0") == "1"
-
-
-_INFER_FUSE_MSRB = None     # set_infer_fuse_msrb(): in-process override of LHN_INFER_FUSE_MSRB
+    return _infer_switch("infer_fuse_dwpw")
 
 
 def set_infer_fuse_msrb(on):
-    """Switch the MSRB-round inference fusion pass (PlanBuilder.fuse_msrb_round) on or off for plans built from now on; None =
-    follow the environment again.  Independent of the other two switches; Engine.plan_for keys its cache on all three."""
-    global _INFER_FUSE_MSRB
-    _INFER_FUSE_MSRB = None if on is None else bool(on)
+    """_set_infer_switch for the MSRB-round inference fusion pass (PlanBuilder.fuse_msrb_round)."""
+    _set_infer_switch("infer_fuse_msrb", on)
 
 
 def infer_fuse_msrb_enabled():
     """LHN_INFER_FUSE_MSRB=1 (default off): plans without a backward run each MSRB round -- its two dilated depthwise 3x3
     convolutions and the pooling of its attention -- as one pass over the feature map."""
-    return _INFER_FUSE_MSRB if _INFER_FUSE_MSRB is not None else os.environ.get("LHN_INFER_FUSE_MSRB", "0") == "1"
-
-
-_INFER_FUSE_BNECK = None     # set_infer_fuse_bneck(): in-process override of LHN_INFER_FUSE_BNECK
+    return _infer_switch("infer_fuse_msrb")
 
 
 def set_infer_fuse_bneck(on):
-    """Switch the BottleNeck inference fusion pass (PlanBuilder.fuse_bottleneck) on or off for plans built from now on; None =
-    follow the environment again.  Independent of the other three switches; Engine.plan_for keys its cache on all four."""
-    global _INFER_FUSE_BNECK
-    _INFER_FUSE_BNECK = None if on is None else bool(on)
+    """_set_infer_switch for the BottleNeck inference fusion pass (PlanBuilder.fuse_bottleneck)."""
+    _set_infer_switch("infer_fuse_bneck", on)
 
 
 def infer_fuse_bneck_enabled():
     """LHN_INFER_FUSE_BNECK=1 (default off): plans without a backward run each BottleNeck -- 1x1, dense 3x3, 1x1, residual sum and
     activation -- as one launch."""
-    return _INFER_FUSE_BNECK if _INFER_FUSE_BNECK is not None else os.environ.get("LHN_INFER_FUSE_BNECK", "0") == "1"
-
-
-_INFER_FUSE_STEM = None     # set_infer_fuse_stem(): in-process override of LHN_INFER_FUSE_STEM
+    return _infer_switch("infer_fuse_bneck")
 
 
 def set_infer_fuse_stem(on):
-    """Switch the stem inference fusion pass (PlanBuilder.fuse_stem) on or off for plans built from now on; None = follow the
-    environment again.  Independent of the other switches; Engine.plan_for keys its cache on all of them."""
-    global _INFER_FUSE_STEM
-    _INFER_FUSE_STEM = None if on is None else bool(on)
+    """_set_infer_switch for the stem inference fusion pass (PlanBuilder.fuse_stem)."""
+    _set_infer_switch("infer_fuse_stem", on)
 
 
 def infer_fuse_stem_enabled():
     """LHN_INFER_FUSE_STEM=1 (default off): plans without a backward run the stem after its first convolution -- depthwise K x K, 1x1,
     dense 3x3 stride 2, max pool, concatenation and 1x1 -- as one launch."""
-    return _INFER_FUSE_STEM if _INFER_FUSE_STEM is not None else os.environ.get("LHN_INFER_FUSE_STEM", "0") == "1"
-
-
-_INFER_BF16X3 = None     # set_infer_bf16x3(): in-process override of LHN_INFER_BF16X3
+    return _infer_switch("infer_fuse_stem")
 
 
 def set_infer_bf16x3(on):
-    """Switch the split-bf16 pass for dense 3x3 convolutions (PlanBuilder.mark_bf16x3) on or off for plans built from now on; None =
-    follow the environment again.  Independent of the four fusion switches; Engine.plan_for keys its cache on all five."""
-    global _INFER_BF16X3
-    _INFER_BF16X3 = None if on is None else bool(on)
+    """_set_infer_switch for the split-bf16 pass for dense 3x3 convolutions (PlanBuilder.mark_bf16x3)."""
+    _set_infer_switch("infer_bf16x3", on)
 
 
 def infer_bf16x3_enabled():
     """LHN_INFER_BF16X3=1 (default off): plans without a backward run their stride-1 dense 3x3 convolutions with 32 / 64 / 128
     channels on the bf16 MFMA with a three-term split (lhn_conv_kxk_fwd_bf16x3) instead of the fp32 MFMA."""
-    return _INFER_BF16X3 if _INFER_BF16X3 is not None else os.environ.get("LHN_INFER_BF16X3", "0") == "1"
+    return _infer_switch("infer_bf16x3")
 
 
 # What lhn_conv_kxk_fwd_bf16x3 is built for (csrc/k_conv_kxk_bf16.hip: kxk_bf16x3_channels and the checks of the entry point) ...
@@ -184,6 +184,17 @@ def _refs_in(v):
     elif isinstance(v, (list, tuple)):
         for u in v:
             yield from _refs_in(u)
+
+
+def _overlaps(x, y):
+    """True when the views x and y share channels of one buffer."""
+    return y.buf == x.buf and x.coff < y.coff + y.C and y.coff < x.coff + x.C
+
+
+def _biased_bn(r):
+    """True when the convolution record r has a bias in front of a BatchNorm: the unfused convolution's own finalize folds it into the
+    table's shift, a FINALIZE record does not."""
+    return r["bn"] is not None and getattr(r["conv"], "bias", None) is not None
 
 
 def _reads(rec):
@@ -288,20 +299,12 @@ class PlanBuilder:
     def __init__(self, N, state_index, image_hw=None, with_backward=True, p_drop=0.0, infer_fuse=None, infer_fuse_dwpw=None,
                  infer_fuse_msrb=None, infer_fuse_bneck=False, infer_bf16x3=False, infer_fuse_stem=False):
         self.N = N
-        # inference fusion (fuse_pw_dw): None = the process-wide switch.  The fused launch has no batch statistics, so the
-        # caller passes False for a plan that will run train-mode BatchNorm under no_grad (Engine.plan_for).
-        self.infer_fuse = infer_fuse_enabled() if infer_fuse is None else bool(infer_fuse)
-        self.n_fused = 0
-        self.infer_fuse_dwpw = infer_fuse_dwpw_enabled() if infer_fuse_dwpw is None else bool(infer_fuse_dwpw)   # fuse_dw_pw, likewise
-        self.n_fused_dwpw = 0
-        self.infer_fuse_msrb = infer_fuse_msrb_enabled() if infer_fuse_msrb is None else bool(infer_fuse_msrb)   # fuse_msrb_round, likewise
-        self.n_fused_msrb = 0
-        self.infer_fuse_bneck = infer_fuse_bneck_enabled() if infer_fuse_bneck is None else bool(infer_fuse_bneck)   # fuse_bottleneck, likewise
-        self.n_fused_bneck = 0
-        self.infer_bf16x3 = infer_bf16x3_enabled() if infer_bf16x3 is None else bool(infer_bf16x3)   # mark_bf16x3, likewise
-        self.n_bf16x3 = 0
-        self.infer_fuse_stem = infer_fuse_stem_enabled() if infer_fuse_stem is None else bool(infer_fuse_stem)   # fuse_stem, likewise
-        self.n_fused_stem = 0
+        # The inference switches (INFER_SWITCHES): None = the process-wide switch.  The rewritten launches have no batch statistics,
+        # so the caller passes False for a plan that will run train-mode BatchNorm under no_grad (Engine.plan_for).
+        given = locals()
+        for name, _, _, counter, _ in INFER_SWITCHES:
+            setattr(self, name, _infer_switch(name) if given[name] is None else bool(given[name]))
+            setattr(self, counter, 0)
         self.state_index = state_index      # id(tensor) -> index in the params array
         self.bufs = []
         self.recs = []                      # forward records (python dicts)
@@ -790,22 +793,90 @@ class PlanBuilder:
             self._needs_zero_grad.add(t.buf)
             written.setdefault(t.buf, []).append((t.coff, hi))
 
+    # ------------------------------------------------------------------ inference rewrites: what the matchers and passes share
+    def _uses(self):
+        """buffer -> [(record, key)] for every view in every record, in record order (the matchers take the first candidate).  Every
+        pass calls it on entry and nothing caches it: a pass sees the records the previous one left."""
+        uses = {}
+        for r in self.recs:
+            for key, v in r.items():
+                for t in _refs_in(v):
+                    uses.setdefault(t.buf, []).append((r, key))
+        return uses
+
+    def _whole_fresh(self, t, C):
+        """True when view t is the whole of a C-channel buffer that is ungated, not lazy, not fused and neither the plan's input nor its output."""
+        if isinstance(t, TCat) or t.buf < 0:
+            return False
+        tb = self.bufs[t.buf]
+        if t.coff != 0 or t.C != C or tb.C != C or tb.gate or tb.lazy is not None or tb.fused:
+            return False
+        return not any(v is not None and v.buf == t.buf for v in (self.in_ref, self.out_ref))
+
+    def _sole_reader(self, t, writer, uses, kind):
+        """The only record that reads the whole fresh buffer behind view t (written by `writer`), if it is of `kind`; else None.  What
+        fills the buffer's table (FINALIZE / TABLE_FILL) is not a reader."""
+        if not self._whole_fresh(t, t.C):
+            return None
+        q = None
+        for u, key in uses.get(t.buf, ()):
+            if (u is writer or u["op"] in (FINALIZE, TABLE_FILL)) and key == "out":
+                continue
+            if u["op"] == kind and key in ("x", "srcs") and q is None:
+                q = u
+                continue
+            return None
+        return q
+
+    def _plain_conv(self, r, kind, biased_bn=False):
+        """A stride-1 convolution record of `kind` with one plain source and nothing special about its weights or BatchNorm (biased_bn:
+        a bias in front of a BatchNorm is fine -- the caller's kernel adds it ahead of the table)."""
+        if r is None or r["op"] != kind or r["stride"] != 1 or r["nchw"] or r["wrc"] != (0, 0) or r["bn_repeat"] != 1 or self._xs(r)[1] != 1:
+            return False
+        if r["x"].buf < 0 or isinstance(r["x"], TCat):
+            return False
+        return biased_bn or not _biased_bn(r)
+
+    def _plain_dw3(self, q, dils, max_srcs=1):
+        """A 3x3 depthwise convolution record with weights: stride 1, padding == dilation in `dils`, at most max_srcs summed sources and
+        no bias in front of a BatchNorm."""
+        if q is None or q["op"] != DW or (q["k"], q["stride"]) != (3, 1) or q["pad"] != q["dil"] or q["dil"] not in dils:
+            return False
+        if q["conv"].weight is None or q.get("bn_repeat", 1) != 1 or self._xs(q)[1] > max_srcs or q["x"].buf < 0:
+            return False
+        return not _biased_bn(q)
+
+    @staticmethod
+    def _tables(q, fill=False):
+        """The records that fill the table of convolution record q's output without q: FINALIZE when q has a BatchNorm; else, with `fill`,
+        a TABLE_FILL for its pending bias / activation.  fuse_pw_dw and fuse_msrb_round drop the original TABLE_FILL and emit this one
+        ahead of their launch; the other passes leave the original where it stands and ask for none."""
+        if q["bn"] is not None:
+            return [dict(op=FINALIZE, out=q["out"], bn=q["bn"], slope=q["slope"])]
+        if fill and (q["conv"].bias is not None or q["slope"] != 1.0):
+            return [dict(op=TABLE_FILL, out=q["out"], bias=q["conv"].bias, slope=q["slope"])]
+        return []
+
+    def _splice(self, at, drop):
+        """Rebuild the record list: a record whose id is in `at` is replaced by the list there, one whose id is in `drop` disappears,
+        the rest stay.  Returns the number of replacements."""
+        recs = []
+        for r in self.recs:
+            recs += at.get(id(r), [] if id(r) in drop else [r])
+        self.recs = recs
+        return len(at)
+
     # Channel counts lhn_conv_pw_dw3_fwd is built for (csrc/k_conv_pwdw.hip: pw_dw3_supported); any map size.
     FUSE_PW_DW_CHANNELS = (64,)
 
     def _fusable_pw_dw(self, r, uses):
         """The depthwise record that can share a launch with the 1x1 record r, or None.  The pair: a stride-1 1x1 of one plain
-        source into a whole, ungated buffer whose ONLY reader is a 3x3 depthwise convolution (stride 1, dilation 1, padding 1,
+        source into a whole fresh buffer whose ONLY reader is a 3x3 depthwise convolution (stride 1, dilation 1, padding 1,
         one source) over all of it, with channel counts the entry point accepts."""
-        if r["op"] != PW or r["stride"] != 1 or r["nchw"] or r["wrc"] != (0, 0) or r["bn_repeat"] != 1 or self._xs(r)[1] != 1:
+        if not self._plain_conv(r, PW):
             return None
         x, t = r["x"], r["out"]
-        tb = self.bufs[t.buf]
-        if x.buf < 0 or x.C not in self.FUSE_PW_DW_CHANNELS or t.C != x.C or t.coff != 0 or tb.C != t.C or tb.gate or tb.lazy is not None:
-            return None
-        if any(v is not None and v.buf == t.buf for v in (self.in_ref, self.out_ref)):
-            return None
-        if r["bn"] is not None and getattr(r["conv"], "bias", None) is not None:
+        if x.C not in self.FUSE_PW_DW_CHANNELS or not self._whole_fresh(t, x.C):
             return None
         q = None
         for u, key in uses.get(t.buf, ()):
@@ -817,15 +888,10 @@ class PlanBuilder:
                 q = u
                 continue
             return None
-        if q is None or (q["k"], q["stride"], q["pad"], q["dil"]) != (3, 1, 1, 1) or q["conv"].weight is None or \
-                q.get("bn_repeat", 1) != 1 or self._xs(q)[1] != 1:
+        if not self._plain_dw3(q, (1,)):
             return None
         qx, y = q["x"], q["out"]
-        if (qx.coff, qx.C) != (0, t.C) or y.C != t.C or y.buf == t.buf:
-            return None
-        if q["bn"] is not None and getattr(q["conv"], "bias", None) is not None:
-            return None
-        if y.buf == x.buf and x.coff < y.coff + y.C and y.coff < x.coff + x.C:
+        if (qx.coff, qx.C) != (0, t.C) or y.C != t.C or y.buf == t.buf or _overlaps(x, y):
             return None
         return q
 
@@ -835,41 +901,24 @@ class PlanBuilder:
         is known before the launch: it is written into the intermediate buffer's table by what fills it in the unfused plan
         (eval: FINALIZE from the running statistics; deployed: TABLE_FILL with the 1x1's bias, which the unfused 1x1 adds while
         storing), the fused kernel reads it as t_table, and the intermediate buffer gets no data.  Both table launches sit
-        under LHN_RUN_TABLES_CURRENT like every other.  Plans with a backward are never rewritten."""
+        under LHN_RUN_TABLES_CURRENT like every other.  The launch stands where the depthwise convolution stood.  Plans with a
+        backward are never rewritten."""
         if self.with_backward or not self.infer_fuse:
             return 0
-        uses = {}
-        for r in self.recs:
-            for key, v in r.items():
-                for t in _refs_in(v):
-                    uses.setdefault(t.buf, []).append((r, key))
-        pairs = {}
+        uses = self._uses()
+        at, drop = {}, set()
         for r in self.recs:
             q = self._fusable_pw_dw(r, uses)
-            if q is not None:
-                pairs[id(q)] = r
-        drop = {id(r) for r in pairs.values()}
-        drop |= {id(u) for r in pairs.values() for u, key in uses[r["out"].buf] if u["op"] == TABLE_FILL and key == "out"}
-        recs = []
-        for q in self.recs:
-            if id(q) in drop:
-                continue
-            r = pairs.get(id(q))
-            if r is None:
-                recs.append(q)
+            if q is None:
                 continue
             t = r["out"]
-            if r["bn"] is not None:
-                recs.append(dict(op=FINALIZE, out=t, bn=r["bn"], slope=r["slope"]))
-            elif r["conv"].bias is not None or r["slope"] != 1.0:
-                recs.append(dict(op=TABLE_FILL, out=t, bias=r["conv"].bias, slope=r["slope"]))
-            recs.append(dict(op=PWDW, x=r["x"], mid=t, out=q["out"], conv=r["conv"], conv2=q["conv"]))
-            if q["bn"] is not None:
-                recs.append(dict(op=FINALIZE, out=q["out"], bn=q["bn"], slope=q["slope"]))
+            at[id(q)] = self._tables(r, fill=True) + [dict(op=PWDW, x=r["x"], mid=t, out=q["out"], conv=r["conv"], conv2=q["conv"])] + \
+                self._tables(q)
+            drop |= {id(r)} | {id(u) for u, key in uses[t.buf] if u["op"] == TABLE_FILL and key == "out"}
             self.bufs[t.buf].fused = True
-        self.recs = recs
-        self.n_fused += len(pairs)
-        return len(pairs)
+        n = self._splice(at, drop)
+        self.n_fused += n
+        return n
 
     # Channel counts and dilations lhn_conv_dw3_pw_fwd is built for (csrc/k_conv_dwpw.hip: dw3_pw_supported); any map size.
     FUSE_DW_PW_CHANNELS = (32, 64)
@@ -877,18 +926,12 @@ class PlanBuilder:
 
     def _fusable_dw_pw(self, q, uses):
         """The 1x1 record that can share a launch with the depthwise record q, or None.  The pair: a 3x3 depthwise convolution
-        (stride 1, padding == dilation, one plain source) into a whole, ungated buffer whose ONLY reader is a stride-1 1x1 of one
+        (stride 1, padding == dilation, one plain source) into a whole fresh buffer whose ONLY reader is a stride-1 1x1 of one
         source over all of it, with channel counts the entry point accepts."""
-        if q["op"] != DW or (q["k"], q["stride"]) != (3, 1) or q["pad"] != q["dil"] or q["dil"] not in self.FUSE_DW_PW_DILATIONS or \
-                q["conv"].weight is None or q.get("bn_repeat", 1) != 1 or self._xs(q)[1] != 1:
+        if not self._plain_dw3(q, self.FUSE_DW_PW_DILATIONS):
             return None
         x, t = q["x"], q["out"]
-        tb = self.bufs[t.buf]
-        if x.buf < 0 or x.C not in self.FUSE_DW_PW_CHANNELS or t.C != x.C or t.coff != 0 or tb.C != t.C or tb.gate or tb.lazy is not None:
-            return None
-        if any(v is not None and v.buf == t.buf for v in (self.in_ref, self.out_ref)):
-            return None
-        if q["bn"] is not None and getattr(q["conv"], "bias", None) is not None:
+        if x.C not in self.FUSE_DW_PW_CHANNELS or not self._whole_fresh(t, x.C):
             return None
         r = None
         for u, key in uses.get(t.buf, ()):
@@ -900,14 +943,10 @@ class PlanBuilder:
                 r = u
                 continue
             return None
-        if r is None or r["stride"] != 1 or r["nchw"] or r["wrc"] != (0, 0) or r["bn_repeat"] != 1 or self._xs(r)[1] != 1:
+        if not self._plain_conv(r, PW):
             return None
         rx, y = r["x"], r["out"]
-        if (rx.coff, rx.C) != (0, t.C) or y.C not in self.FUSE_DW_PW_CHANNELS or y.buf == t.buf:
-            return None
-        if r["bn"] is not None and getattr(r["conv"], "bias", None) is not None:
-            return None
-        if y.buf == x.buf and x.coff < y.coff + y.C and y.coff < x.coff + x.C:
+        if (rx.coff, rx.C) != (0, t.C) or y.C not in self.FUSE_DW_PW_CHANNELS or y.buf == t.buf or _overlaps(x, y):
             return None
         return r
 
@@ -919,36 +958,21 @@ class PlanBuilder:
         intermediate buffer gets no data.  The launch stands where the 1x1 stood.  Plans with a backward are never rewritten."""
         if self.with_backward or not self.infer_fuse_dwpw:
             return 0
-        uses = {}
-        for r in self.recs:
-            for key, v in r.items():
-                for t in _refs_in(v):
-                    uses.setdefault(t.buf, []).append((r, key))
-        pairs = {}
+        uses = self._uses()
+        at, drop = {}, set()
         for q in self.recs:
             r = self._fusable_dw_pw(q, uses)
-            if r is not None:
-                pairs[id(r)] = q
-        drop = {id(q) for q in pairs.values()}
-        recs = []
-        for r in self.recs:
-            if id(r) in drop:
-                continue
-            q = pairs.get(id(r))
-            if q is None:
-                recs.append(r)
+            if r is None:
                 continue
             t = q["out"]
-            if q["bn"] is not None:
-                recs.append(dict(op=FINALIZE, out=t, bn=q["bn"], slope=q["slope"]))
-            recs.append(dict(op=DWPW, x=q["x"], mid=t, out=r["out"], conv=q["conv"], conv2=r["conv"], dil=q["dil"],
-                             bias=None if r["bn"] is not None else r["conv"].bias))
-            if r["bn"] is not None:
-                recs.append(dict(op=FINALIZE, out=r["out"], bn=r["bn"], slope=r["slope"]))
+            fused = dict(op=DWPW, x=q["x"], mid=t, out=r["out"], conv=q["conv"], conv2=r["conv"], dil=q["dil"],
+                         bias=None if r["bn"] is not None else r["conv"].bias)
+            at[id(r)] = self._tables(q) + [fused] + self._tables(r)
+            drop.add(id(q))
             self.bufs[t.buf].fused = True
-        self.recs = recs
-        self.n_fused_dwpw += len(pairs)
-        return len(pairs)
+        n = self._splice(at, drop)
+        self.n_fused_dwpw += n
+        return n
 
     # Channels per half lhn_msrb_round_fwd is built for (csrc/k_msrb.hip: msrb_half_ok); any map size.
     FUSE_MSRB_HALF = (32, 64, 128)
@@ -956,13 +980,10 @@ class PlanBuilder:
     def _msrb_branch(self, q, dil):
         """True when the record q can be one branch of a fused MSRB round: a 3x3 depthwise convolution, stride 1, dilation ==
         padding == dil, of at most two summed sources, over a channel count the entry point accepts."""
-        if q["op"] != DW or (q["k"], q["stride"], q["pad"], q["dil"]) != (3, 1, dil, dil) or q["conv"].weight is None or \
-                q.get("bn_repeat", 1) != 1 or self._xs(q)[1] > 2:
+        if not self._plain_dw3(q, (dil,), max_srcs=2):
             return False
         x, y = q["x"], q["out"]
-        if x.buf < 0 or y.buf < 0 or x.C != y.C or y.C not in self.FUSE_MSRB_HALF:
-            return False
-        return not (q["bn"] is not None and getattr(q["conv"], "bias", None) is not None)
+        return y.buf >= 0 and x.C == y.C and y.C in self.FUSE_MSRB_HALF
 
     def fuse_msrb_round(self):
         """Inference plans with the switch on (infer_fuse_msrb): one round of an MSRB (litehourglass.py:43-50) -- the depthwise 3x3
@@ -974,11 +995,7 @@ class PlanBuilder:
         backward are never rewritten."""
         if self.with_backward or not self.infer_fuse_msrb:
             return 0
-        uses = {}
-        for r in self.recs:
-            for key, v in r.items():
-                for t in _refs_in(v):
-                    uses.setdefault(t.buf, []).append((r, key))
+        uses = self._uses()
         order = {id(r): j for j, r in enumerate(self.recs)}
         at, drop = {}, set()
         for b, rec in enumerate(self.bufs):
@@ -1012,54 +1029,14 @@ class PlanBuilder:
                     continue
                 att["pool_fused"] = True        # _fwd_ca / _fwd_se: no AVGPOOL launch, the fused record fills `pooled`
                 fused.update(pooled=att["pooled"], scratch=self._ws("misc", nbytes), OH=3 if att["op"] == CA_MLP else 1)
-            tables = []
-            for q in (q1, q2):
-                if q["bn"] is not None:
-                    tables.append(dict(op=FINALIZE, out=q["out"], bn=q["bn"], slope=q["slope"]))
-                elif q["conv"].bias is not None or q["slope"] != 1.0:
-                    tables.append(dict(op=TABLE_FILL, out=q["out"], bias=q["conv"].bias, slope=q["slope"]))
-            at[id(self.recs[hi])] = tables + [fused]
+            at[id(self.recs[hi])] = self._tables(q1, fill=True) + self._tables(q2, fill=True) + [fused]
             drop |= {id(q1), id(q2)} | {id(u) for u in fills}
-        if not at:
-            return 0
-        recs = []
-        for r in self.recs:
-            recs += at.get(id(r), [] if id(r) in drop else [r])
-        self.recs = recs
-        self.n_fused_msrb += len(at)
-        return len(at)
+        n = self._splice(at, drop)
+        self.n_fused_msrb += n
+        return n
 
     # Channel pairs (C, Cm) lhn_bottleneck_fwd is built for (csrc/k_bottleneck.hip: bottleneck_supported); any map size.
     FUSE_BNECK_CHANNELS = ((128, 32), (128, 64))
-
-    def _sole_reader(self, t, writer, uses, kind):
-        """The only record that reads the whole, fresh, ungated, non-lazy buffer behind view t (written by `writer`), if it is of
-        `kind`; else None.  What fills the buffer's table (FINALIZE / TABLE_FILL) is not a reader."""
-        if isinstance(t, TCat) or t.buf < 0:
-            return None
-        tb = self.bufs[t.buf]
-        if t.coff != 0 or tb.C != t.C or tb.gate or tb.lazy is not None or tb.fused:
-            return None
-        if any(v is not None and v.buf == t.buf for v in (self.in_ref, self.out_ref)):
-            return None
-        q = None
-        for u, key in uses.get(t.buf, ()):
-            if (u is writer or u["op"] in (FINALIZE, TABLE_FILL)) and key == "out":
-                continue
-            if u["op"] == kind and key in ("x", "srcs") and q is None:
-                q = u
-                continue
-            return None
-        return q
-
-    def _plain_conv(self, r, kind, biased_bn=False):
-        """A stride-1 convolution record of `kind` with one plain source and nothing special about its weights or BatchNorm (biased_bn:
-        a bias in front of a BatchNorm is fine -- the caller's kernel adds it ahead of the table)."""
-        if r is None or r["op"] != kind or r["stride"] != 1 or r["nchw"] or r["wrc"] != (0, 0) or r["bn_repeat"] != 1 or self._xs(r)[1] != 1:
-            return False
-        if r["x"].buf < 0 or isinstance(r["x"], TCat):
-            return False
-        return biased_bn or not (r["bn"] is not None and getattr(r["conv"], "bias", None) is not None)     # as _fusable_dw_pw
 
     def _fusable_bottleneck(self, r1, uses):
         """(r2, r3, ew) when the 1x1 record r1 starts a BottleNeck pattern, else None: 1x1 C -> Cm, 3x3 Cm -> Cm, 1x1 Cm -> C (slope 1),
@@ -1087,9 +1064,7 @@ class PlanBuilder:
         if {key(a), key(b)} != {key(x), key(t3)} or key(x) == key(t3):
             return None
         y = ew["out"]
-        if isinstance(y, TCat) or y.buf < 0 or y.buf in (t1.buf, t2.buf, t3.buf) or (y.H, y.W, y.C) != (x.H, x.W, x.C):
-            return None
-        if y.buf == x.buf and x.coff < y.coff + y.C and y.coff < x.coff + x.C:
+        if isinstance(y, TCat) or y.buf < 0 or y.buf in (t1.buf, t2.buf, t3.buf) or (y.H, y.W, y.C) != (x.H, x.W, x.C) or _overlaps(x, y):
             return None
         return r2, r3, ew
 
@@ -1102,11 +1077,7 @@ class PlanBuilder:
         where the sum stood.  Plans with a backward are never rewritten."""
         if self.with_backward or not self.infer_fuse_bneck:
             return 0
-        uses = {}
-        for r in self.recs:
-            for key, v in r.items():
-                for t in _refs_in(v):
-                    uses.setdefault(t.buf, []).append((r, key))
+        uses = self._uses()
         at, drop = {}, set()
         for r1 in self.recs:
             m = self._fusable_bottleneck(r1, uses)
@@ -1115,35 +1086,20 @@ class PlanBuilder:
             r2, r3, ew = m
             if {id(r1), id(r2), id(r3), id(ew)} & drop:
                 continue
-            tables = [dict(op=FINALIZE, out=q["out"], bn=q["bn"], slope=q["slope"]) for q in (r1, r2, r3) if q["bn"] is not None]
             fused = dict(op=BNECK, x=r1["x"], mids=[r1["out"], r2["out"], r3["out"]], out=ew["out"], convs=(r1["conv"], r2["conv"], r3["conv"]),
                          b1=None if r1["bn"] is not None else r1["conv"].bias, b3=None if r3["bn"] is not None else r3["conv"].bias,
                          slope=ew["slope"], wt=r2["wt"])
-            at[id(ew)] = tables + [fused]
+            at[id(ew)] = [t for q in (r1, r2, r3) for t in self._tables(q)] + [fused]
             drop |= {id(r1), id(r2), id(r3), id(ew)}
             for q in (r1, r2, r3):
                 self.bufs[q["out"].buf].fused = True
-        if not at:
-            return 0
-        recs = []
-        for r in self.recs:
-            recs += at.get(id(r), [] if id(r) in drop else [r])
-        self.recs = recs
-        self.n_fused_bneck += len(at)
-        return len(at)
+        n = self._splice(at, drop)
+        self.n_fused_bneck += n
+        return n
 
     # What lhn_stem_tail_fwd is built for (csrc/k_stem.hip: stem_tail_supported): (m, C) and the depthwise kernel sizes it absorbs; any map.
     FUSE_STEM_CHANNELS = (32, 128)
     FUSE_STEM_K = (3, 7)
-
-    def _whole_fresh(self, t, C):
-        """True when view t is the whole of a C-channel buffer that is ungated, not lazy, not fused and neither the plan's input nor its output."""
-        if isinstance(t, TCat) or t.buf < 0:
-            return False
-        tb = self.bufs[t.buf]
-        if t.coff != 0 or t.C != C or tb.C != C or tb.gate or tb.lazy is not None or tb.fused:
-            return False
-        return not any(v is not None and v.buf == t.buf for v in (self.in_ref, self.out_ref))
 
     def _fusable_stem(self, mp, uses):
         """(dw or None, r1, r2, r3) when the MAXPOOL record mp is branch2 of a stem (liteHandNet.py:169-193), else None: mp pools a whole
@@ -1206,7 +1162,7 @@ class PlanBuilder:
         for b in {x.buf, t.buf}:
             if any(key == "out" and q["op"] in (STEM, PW, DW, KXK, FINALIZE, TABLE_FILL) and not ok_slope(q) for q, key in uses.get(b, ())):
                 return None
-        if y.buf == x.buf and x.coff < y.coff + y.C and y.coff < x.coff + x.C:
+        if _overlaps(x, y):
             return None
         return dw, r1, r2, r3
 
@@ -1222,11 +1178,7 @@ class PlanBuilder:
         The launch stands where the last 1x1 stood.  Runs first in finalize().  Plans with a backward are never rewritten."""
         if self.with_backward or not self.infer_fuse_stem:
             return 0
-        uses = {}
-        for r in self.recs:
-            for key, v in r.items():
-                for t in _refs_in(v):
-                    uses.setdefault(t.buf, []).append((r, key))
+        uses = self._uses()
         at, drop = {}, set()
         for mp in self.recs:
             if mp["op"] != MAXPOOL:
@@ -1238,25 +1190,18 @@ class PlanBuilder:
             absorbed = [q for q in (dw, r1, r2) if q is not None]
             if {id(q) for q in absorbed + [mp, r3]} & drop:
                 continue
-            tables = [dict(op=FINALIZE, out=q["out"], bn=q["bn"], slope=q["slope"]) for q in absorbed if q["bn"] is not None]
             fused = dict(op=STEMTAIL, x=dw["x"] if dw is not None else mp["x"], t=mp["x"], u=r1["out"],
                          cat=TRef(r2["out"].buf, 0, 2 * r2["out"].C, r2["out"].H, r2["out"].W), out=r3["out"], K=dw["k"] if dw is not None else 0,
                          dw=dw["conv"] if dw is not None else None, convs=(r1["conv"], r2["conv"], r3["conv"]),
                          bT=dw["conv"].bias if dw is not None and dw["bn"] is not None else None, b1=r1["conv"].bias,
                          b2=r2["conv"].bias if r2["bn"] is not None else None, b3=None if r3["bn"] is not None else r3["conv"].bias, wt=r2["wt"])
-            tail = [dict(op=FINALIZE, out=r3["out"], bn=r3["bn"], slope=r3["slope"])] if r3["bn"] is not None else []
-            at[id(r3)] = tables + [fused] + tail
+            at[id(r3)] = [t for q in absorbed for t in self._tables(q)] + [fused] + self._tables(r3)
             drop |= {id(q) for q in absorbed + [mp, r3]}
             for q in absorbed:
                 self.bufs[q["out"].buf].fused = True       # t (when absorbed), u and -- through v -- the whole concatenation buffer
-        if not at:
-            return 0
-        recs = []
-        for r in self.recs:
-            recs += at.get(id(r), [] if id(r) in drop else [r])
-        self.recs = recs
-        self.n_fused_stem += len(at)
-        return len(at)
+        n = self._splice(at, drop)
+        self.n_fused_stem += n
+        return n
 
     def mark_bf16x3(self):
         """Inference plans with the switch on (infer_bf16x3): every dense 3x3 record that bf16x3_eligible accepts runs on the bf16 MFMA
@@ -1271,8 +1216,7 @@ class PlanBuilder:
             if r["op"] != KXK or isinstance(r["x"], TCat) or isinstance(r["out"], TCat) or r["x"].buf < 0 or r["out"].buf < 0:
                 continue
             x, y = r["x"], r["out"]
-            overlap = x.buf == y.buf and x.coff < y.coff + y.C and y.coff < x.coff + x.C
-            if r["k"] == 3 and r["pad"] == 1 and r["dil"] == 1 and bf16x3_eligible(x.C, y.C, r["stride"], overlap):
+            if r["k"] == 3 and r["pad"] == 1 and r["dil"] == 1 and bf16x3_eligible(x.C, y.C, r["stride"], _overlaps(x, y)):
                 r["bf16x3"] = True
                 n += 1
         self.n_bf16x3 += n
@@ -1281,12 +1225,8 @@ class PlanBuilder:
     # ------------------------------------------------------------------ finalize: the passes in the order they run
     def finalize(self):
         """Lower the records to what lhn_plan_create takes: (Buf array, forward Op array, backward Op array or None, n_fwd, n_bwd)."""
-        self.fuse_stem()
-        self.fuse_msrb_round()
-        self.fuse_dw_pw()
-        self.fuse_pw_dw()
-        self.fuse_bottleneck()
-        self.mark_bf16x3()
+        for _, _, method, _, _ in INFER_SWITCHES:
+            getattr(self, method)()
         self._layout()
         self._plan_sum_out()
         fwd = self._lower_forward()

@@ -15,6 +15,7 @@ import bottleneck_cases as bc
 from litehandnet_amd import _lib, get_model, plan
 from litehandnet_amd.config import litehandnet_cfg
 from litehandnet_amd.plan import BNECK, CBAM, DWPW, EW, FINALIZE, KXK, MSRB, PW, PWDW, TABLE_FILL, PlanBuilder
+from plan_digest import _deploy_without_gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SWITCHES = ("LHN_INFER_FUSE_BNECK", "LHN_INFER_FUSE_MSRB", "LHN_INFER_FUSE_DWPW", "LHN_INFER_FUSE")
@@ -27,22 +28,6 @@ def _switches_back(monkeypatch):
     yield
     for f in (plan.set_infer_fuse, plan.set_infer_fuse_dwpw, plan.set_infer_fuse_msrb, plan.set_infer_fuse_bneck):
         f(None)
-
-
-def _deploy_without_gpu(m):
-    """The deployed module tree, built without the GPU fold (weights are whatever nn.Conv2d draws: the pass looks at shapes)."""
-    for u in m.modules():
-        if hasattr(u, "conv") and hasattr(u, "slope") and not hasattr(u, "rep_conv"):
-            c = u.conv.conv
-            u.rep_conv = nn.Conv2d(c.in_channels, c.out_channels, c.kernel_size, c.stride, c.padding, c.dilation, c.groups, bias=True)
-            del u.conv
-        if hasattr(u, "rbr_dense"):
-            c = u.rbr_dense.conv
-            u.rbr_reparam = nn.Conv2d(c.in_channels, c.out_channels, c.kernel_size, c.stride, c.padding, c.dilation, c.groups, bias=True)
-            del u.rbr_dense, u.rbr_1x1
-            if hasattr(u, "rbr_identity"):
-                del u.rbr_identity
-    return m
 
 
 def _a_model(size=256, deployed=False, **kw):

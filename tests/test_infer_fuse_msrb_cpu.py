@@ -16,6 +16,7 @@ from litehandnet_amd import _lib, get_model, plan
 from litehandnet_amd.config import litehandnet_cfg
 from litehandnet_amd.litehourglass import MSRB as MSRBModule
 from litehandnet_amd.plan import AVGPOOL, CA_MLP, DW, DWPW, FINALIZE, MSRB, PW, PWDW, SE_MLP, TABLE_FILL, PlanBuilder, TCat, TRef
+from plan_digest import _deploy_without_gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -36,20 +37,6 @@ def _builder(m, n, size, backward, image=True, cin=None, cls=PlanBuilder, **kw):
     if getattr(y, "buf", None) != -2:
         pb.set_output(y)
     return pb
-
-
-def _deploy_without_gpu(m):
-    """The deployed module tree, built without the GPU fold (the weights do not matter to the plan compiler)."""
-    for u in m.modules():
-        if hasattr(u, "conv") and hasattr(u, "slope") and not hasattr(u, "rep_conv"):
-            c = u.conv.conv
-            u.rep_conv = nn.Conv2d(c.in_channels, c.out_channels, c.kernel_size, c.stride, c.padding, c.dilation, c.groups, bias=True)
-            del u.conv
-        if hasattr(u, "conv3x3") and not hasattr(u, "rbr_reparam"):
-            c = u.conv3x3.conv
-            u.rbr_reparam = nn.Conv2d(c.in_channels, c.out_channels, 3, 1, 0, groups=c.groups)
-            del u.conv3x3
-    return m
 
 
 def _b_model(size=256, deployed=False, **model_kw):
