@@ -561,7 +561,8 @@ int lhn_conv_pw_bwd3(const lhn_view* x, const float* w, const lhn_view* y, const
 /* The two backward calls above with the BatchNorm-backward finalize of y taken in the kernel's prologue (lhn_bnbwdsrc; fin NULL =
  * the calls above).  gy->coef must point at the coefficient table: it is written.  lhn_conv_dw_bwd4 joins lhn_conv_dw_bwd2 (bns: the
  * producer's sums, x's first channel at bns->coff) and lhn_conv_dw_bwd3 (addends); bns and addends exclude each other as they do there.
- * In-prologue fold: k_dw3_bwd_rows (3x3, stride 1, "same" padding, W >= 8) and k_pw_bwd_wr (the shapes listed at lhn_conv_pw_bwd3's
+ * In-prologue fold: k_dw3_bwd_rows (3x3, stride 1, "same" padding, W >= 8; dilation 1 on maps of at most 256 pixels: the tile kernel
+ * k_dwk_bwd_lds, same fold, LHN_DW_BWD_SMALL=0 keeps the row kernel) and k_pw_bwd_wr (the shapes listed at lhn_conv_pw_bwd3's
  * register-W dispatch); every other kernel gets a lhn_bn_bwd_finalize2 launch in front, from this call. */
 int lhn_conv_dw_bwd4(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate,
                      float* dw, int k, int stride, int pad, int dil, int nrep, int64_t rep_stride, const lhn_bnsum* bns,
@@ -611,6 +612,20 @@ typedef struct lhn_gatesum {
 int lhn_conv_pw_bwd5(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate,
                      float* dw, float* dbias, int stride, const float* dy_nchw, int nrep, int64_t rep_stride,
                      const lhn_pw_opts* opts, const lhn_bnsum* bns, const lhn_bnbwdsrc* fin, const lhn_gatesum* gs, void* stream);
+/* lhn_conv_pw_bwd6 = lhn_conv_pw_bwd5 + flags (0 = lhn_conv_pw_bwd5).
+ * LHN_PW_BWD_DZ_DEAD: the caller reads gy->dz (y's channels of the gradient buffer) no more after this call and does not expect
+ * dy = d loss / d (convolution output) there either.  The wide register-W kernel (128 -> 128, 64 -> 128, 128 -> 64; stride 1, NHWC)
+ * then keeps dy in LDS and only READS dz: one write pass over the output's gradient less.  Without the flag those shapes leave dy in
+ * place of dz, as the three-launch split path always did.  The flag is a permission, not a request: kernels that need dy in memory
+ * (the split path under LHN_PW_BWD_SPLIT=1 or LHN_PW_LDSW=1) still form it in place, and kernels that never stored it (k_pw_bwd, the
+ * narrow register-W instances, strided and NCHW shapes) ignore it.  So with the flag the contents of gy->dz after the call are
+ * unspecified (dz or dy); dx, dW, dbias, the coefficients and every sum are the same bits either way in deterministic mode: the
+ * result never depends on the flag or on the kernel chosen. */
+#define LHN_PW_BWD_DZ_DEAD 1
+int lhn_conv_pw_bwd6(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate,
+                     float* dw, float* dbias, int stride, const float* dy_nchw, int nrep, int64_t rep_stride,
+                     const lhn_pw_opts* opts, const lhn_bnsum* bns, const lhn_bnbwdsrc* fin, const lhn_gatesum* gs, int flags,
+                     void* stream);
 int lhn_avgpool_fwd3(const lhn_view* x, float* out /*[N,OH,OW,C]*/, int OH, int OW, float* pstat /*[N*OH*OW][2][C] or NULL*/,
                      const lhn_bn_slices* slices, void* stream);
 int lhn_ca_mlp_bwd2(const float* pooled, const float* w3, const float* gamma, const float* w1, const float* w2,
@@ -678,6 +693,11 @@ void  lhn_plan_destroy(void* plan);
  * same sums (lhn_gatesum: the op before it is the backward of an NCHW 1x1 that stores the gradient of the whole gated buffer), or -1:
  * no such pair, LHN_HEAD_STREAM=0, or deterministic mode.  The op lists themselves are the same either way. */
 int   lhn_plan_head_gate_fold(void* plan);
+/* 1 when backward op bwd_index is the backward of an NHWC 1x1 whose output gradient no later op of the list touches (as a buffer's
+ * gradient with overlapping channels, aliased buffers included, or through a byte offset): a whole-plan run then passes
+ * LHN_PW_BWD_DZ_DEAD to lhn_conv_pw_bwd6 unless LHN_PW_BWD_DY_STORE=1; 0 otherwise; -1: index out of range.  The answer does not
+ * depend on the switch, and the op lists are the same either way. */
+int   lhn_plan_pw_dz_dead(void* plan, int bwd_index);
 /* io: phase 0 {image NCHW, heatmap NCHW out}; phase 1 {image NCHW, d(heatmap) NCHW}.
  * training: a bit set -- bit 0 = train-mode BatchNorm (batch statistics, running statistics updated); bit 1 (LHN_RUN_TABLES_CURRENT,
  * eval only) = the workspace's per-buffer BatchNorm tables were built by an earlier eval run of THIS plan and no parameter

@@ -999,7 +999,8 @@ extern "C" int lhn_conv_dw_bwd(const lhn_view* x, const float* w, const lhn_view
 static int dw_bwd_fin(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc, float* dw, int k,
                       int dil, int nrep, int64_t rep_stride, const lhn_bnsum* bns, const float* a0, const float* a1, const lhn_bnbwdsrc* fin,
                       hipStream_t s);
-// the shapes lhn_conv_dw_bwd / _bwd2 / _bwd3 hand to k_dw3_bwd_rows (has_ext: sums or addends, which ignore LHN_DW_GATHER)
+// the shapes lhn_conv_dw_bwd / _bwd2 / _bwd3 hand to k_dw3_bwd_rows or, on small maps, to the FOLD instances of k_dwk_bwd_lds: both
+// fold the finalize in their prologue (lhn_dwk_bwd_lds decides between them)  (has_ext: sums or addends, which ignore LHN_DW_GATHER)
 static bool dw_bwd_folds(const lhn_view* x, const float* w, const float* dw, int k, int stride, int pad, int dil, bool has_ext) {
   return w && dw && k == 3 && stride == 1 && (dil == 1 || dil == 2) && pad == dil && x->C % 4 == 0 && x->W >= 8 && !lhn_dw_bwd_v1() &&
          (has_ext || !lhn_dw_force_gather());
@@ -1289,10 +1290,15 @@ struct DwBnSum {
                          // read x, so that no separate elementwise pass copies / accumulates them (NULL: none)
 };
 
-template <int K, int DIL, bool BNS = false>
+// FOLD: the instances of the small-map route (lhn_dwk_bwd_lds) take the BatchNorm-backward finalize of y in their prologue
+// (lhn_bnbwdsrc, fs.sums != NULL) as k_dw3_bwd_rows does: same helpers, replica order and double arithmetic, the replicas as loaded
+// in the dy tile (16 KB of its 23 KB, first written after the tile loop's opening barrier), A | B | C of the block's channel group in
+// 24 float4 of LDS behind the other regions; blocks 0 .. cgroups-1 (bid = cg) also write memory.
+template <int K, int DIL, bool BNS = false, bool FOLD = false>
 __global__ void __launch_bounds__(256) k_dwk_bwd_lds(lhn_view x, const float* __restrict__ w, lhn_view y, lhn_gradview gy,
                                                      float* __restrict__ dx, int dx_acc, float* __restrict__ dw, int tiles_h,
-                                                     int tiles_w, int cgroups, int nrep, int64_t rep_stride, int ps, DwBnSum bs, int xchunk) {
+                                                     int tiles_w, int cgroups, int nrep, int64_t rep_stride, int ps, DwBnSum bs, int xchunk,
+                                                     lhn_bnbwdsrc fs) {
   constexpr int TH = 8, TW = 16, KK = K * K;
   const int bid = xchunk ? (int)(blockIdx.x & 7) * xchunk + (int)(blockIdx.x >> 3) : (int)blockIdx.x;     // see k_dwk_fwd_lds
   constexpr bool REGACC = (K == 3);
@@ -1305,6 +1311,7 @@ __global__ void __launch_bounds__(256) k_dwk_bwd_lds(lhn_view x, const float* __
   f4* dws = wl + KK * 8;                        // [KK][8]  (K = 7 only) block-level dW partials
   f4* traw = dws + KK * 8;                      // [TH*TW][8] raw x of the tile interior (BNS only)
   f4* tmi = traw + TH * TW * 8;                 // [2][8] mean | invstd of this block's channel group (BNS only)
+  float* cfA = reinterpret_cast<float*>(BNS ? tmi + 16 : traw);      // [3][32] A | B | C of this block's channel group (FOLD only)
   const int tid = threadIdx.x, c4 = tid & 7, pl = tid >> 3;
   const int colw = pl & 15, rpar = pl >> 4;
   const int ntile = y.N * ps * ps * tiles_h * tiles_w * cgroups;      // ps: see k_dwk_fwd_lds
@@ -1314,7 +1321,24 @@ __global__ void __launch_bounds__(256) k_dwk_bwd_lds(lhn_view x, const float* __
   const int c4e = cok ? c4 : 0;
   const int cx = x.coff + cg * 32 + 4 * c4e, cy = y.coff + cg * 32 + 4 * c4e;
   const Xf4 xxf = lhn_load_xf(x, cx), yxf = lhn_load_xf(y, cy);
-  const Gr4 ygr = lhn_load_coef(gy, y.cstride, cy);
+  Gr4 ygr;
+  if (FOLD && fs.sums) {
+    static_assert(!FOLD || T::PIX * 8 * sizeof(f4) >= 2 * LHN_FIN_THREADS * sizeof(double), "dy tile holds the replica fold's partials");
+    double* raw = reinterpret_cast<double*>(tdy);
+    const int nc = 4 * cvalid;
+    const LhnBwdPre pre = lhn_bn_bwd_pre(fs, cg * 32, nc);
+    lhn_bn_bwd_fold_raw(fs.sums, fs.stat_channels, cg * 32, nc, raw);
+    __syncthreads();
+    if (tid < nc)
+      lhn_bn_bwd_coef_put(lhn_bn_bwd_coef_raw(raw, nc, lhn_fin_groups(y.C), tid, pre, fs.count), fs, const_cast<float*>(gy.coef), y.cstride,
+                          y.coff, cg * 32 + tid, cfA, 32, tid, bid < cgroups);
+    __syncthreads();      // (publishes cfA; the tile loop's opening barrier frees the fold's scratch)
+    ygr.A = *reinterpret_cast<const f4*>(cfA + 4 * c4e);
+    ygr.B = *reinterpret_cast<const f4*>(cfA + 32 + 4 * c4e);
+    ygr.Cc = *reinterpret_cast<const f4*>(cfA + 64 + 4 * c4e);
+  } else {
+    ygr = lhn_load_coef(gy, y.cstride, cy);
+  }
   for (int i = tid; i < KK * 8; i += 256) {
     const int k = i >> 3, cc = cg * 32 + 4 * min(i & 7, cvalid - 1);
     wl[i] = (f4){w[(cc + 0) * KK + k], w[(cc + 1) * KK + k], w[(cc + 2) * KK + k], w[(cc + 3) * KK + k]};
@@ -1774,21 +1798,24 @@ static void launch_dwk_fwd(const lhn_view* x, const float* w, const lhn_view* y,
   const int grid = dw3_grid(ntile, cg, per_cu * 2);      // (2 / 3 / 4 / 8 / 16 blocks per CU measured in round 3: forward 2.65 / 2.68 / 2.66 / 2.71 / 2.71 ms)
   hipLaunchKernelGGL((k_dwk_fwd_lds<K, DIL, NS>), dim3(grid), dim3(256), lds, s, *x, w, *y, stats, th, tw, cg, fin, ps, ex, dw3_xchunk(grid, cg));
 }
-template <int K, int DIL, bool BNS = false>
+template <int K, int DIL, bool BNS = false, bool FOLD = false>
 static void launch_dwk_bwd(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc,
-                           float* dw, int nrep, int64_t rep_stride, hipStream_t s, int ps = 1, const DwBnSum* bsp = nullptr) {
+                           float* dw, int nrep, int64_t rep_stride, hipStream_t s, int ps = 1, const DwBnSum* bsp = nullptr,
+                           const lhn_bnbwdsrc* fsp = nullptr) {
   constexpr int TH = 8, TW = 16, P = DIL * (K - 1) / 2;
   DwBnSum bs;
   if (bsp) bs = *bsp; else { bs.sums = nullptr; bs.save = nullptr; bs.C = bs.coff = 0; bs.add[0] = bs.add[1] = nullptr; }
+  lhn_bnbwdsrc fs;
+  if (FOLD && fsp) fs = *fsp; else memset(&fs, 0, sizeof(fs));
   const int cg = (x->C + 31) / 32;
   const int sh = (x->H + ps - 1) / ps, sw = (x->W + ps - 1) / ps;
   const int th = (sh + TH - 1) / TH, tw = (sw + TW - 1) / TW, ntile = x->N * ps * ps * th * tw * cg;
-  const size_t lds = (size_t)((TH + 2 * P) * (TW + 2 * P) * 16 + 256 + 2 * K * K * 8 + (BNS ? TH * TW * 8 + 16 : 0)) * 16;
+  const size_t lds = (size_t)((TH + 2 * P) * (TW + 2 * P) * 16 + 256 + 2 * K * K * 8 + (BNS ? TH * TW * 8 + 16 : 0) + (FOLD ? 24 : 0)) * 16;
   static LhnKernelCfg cfg;
-  (void)lhn_kernel_cfg(cfg, &k_dwk_bwd_lds<K, DIL, BNS>, lds, 4, nullptr);
+  (void)lhn_kernel_cfg(cfg, &k_dwk_bwd_lds<K, DIL, BNS, FOLD>, lds, 4, nullptr);
   const int grid = dw3_grid(ntile, cg, 4);
-  hipLaunchKernelGGL((k_dwk_bwd_lds<K, DIL, BNS>), dim3(grid), dim3(256), lds, s, *x, w, *y, *gy, dx, dx_acc, dw, th, tw,
-                     cg, nrep, rep_stride, ps, bs, dw3_xchunk(grid, cg));
+  hipLaunchKernelGGL((k_dwk_bwd_lds<K, DIL, BNS, FOLD>), dim3(grid), dim3(256), lds, s, *x, w, *y, *gy, dx, dx_acc, dw, th, tw,
+                     cg, nrep, rep_stride, ps, bs, dw3_xchunk(grid, cg), fs);
 }
 template <int DIL, bool BNS = false>
 static void launch_dw3_bwd_rows(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc,
@@ -1826,6 +1853,18 @@ static bool lhn_dw_bwd_v1() {
     v = (e && e[0] == '1') ? 1 : 0;
   }
   return v == 1;
+}
+// The size rule of the small-map route (3x3, dilation 1): H * W <= 256.  Train step of variant B at batch 64, per launch, rows kernel
+// against the tile kernel with its separate finalize launch (profiles/dwsmall_launches.md): 8^2 21.8 us against 10.9 + 4.7, 16^2 24.2
+// against 14.0 + 4.8, 32^2 30.3 against 31.7 + 4.9 -- so 32^2 and everything between 16^2 and 32^2, which was not measured, stay on
+// k_dw3_bwd_rows, where 64^2 and 128^2 were tuned.  LHN_DW_BWD_SMALL=0 (read once): every size on k_dw3_bwd_rows, for A/B runs.
+static bool dw_bwd_small(const lhn_view* x) {
+  static int v = -1;
+  if (v < 0) {
+    const char* e = getenv("LHN_DW_BWD_SMALL");
+    v = (e && e[0] == '0') ? 0 : 1;
+  }
+  return v == 1 && (int64_t)x->H * x->W <= 256;
 }
 
 
@@ -2108,17 +2147,23 @@ int lhn_dwk_fwd_lds(const lhn_view* x, const float* w, const lhn_view* y, double
 int lhn_dwk_bwd_lds(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc,
                     float* dw, int k, int dil, int nrep, int64_t rep_stride, hipStream_t s, const DwBnSum* bs,
                     const lhn_bnbwdsrc* fs) {
-  // fs (the BatchNorm-backward finalize of y in the prologue): k_dw3_bwd_rows only -- dw_bwd_folds() is the callers' test
+  // fs (the BatchNorm-backward finalize of y in the prologue): k_dw3_bwd_rows and the small-map instances of k_dwk_bwd_lds (every
+  // 3x3 shape that is not under LHN_DW_BWD_V1=1 reaches one of the two) -- dw_bwd_folds() is the callers' test
   if (fs && (lhn_dw_bwd_v1() || k != 3)) return 0;
+  // 3x3, dilation 1 on a map of at most 256 pixels: the 8 x 16 tile kernel, whose whole halo tile is ONE batch of loads, where
+  // a row strip pays CH + 2 = 10 dependent memory latencies and a barrier per row whatever the map size (dw_bwd_small)
+  const bool small = k == 3 && dil == 1 && dw_bwd_small(x);
   if (bs && bs->sums) {        // fused BatchNorm-backward sums of the producer: the 3x3 / dilation 1 instance only
     if (!(k == 3 && dil == 1 && dx && !dx_acc)) return 0;
     if (lhn_dw_bwd_v1()) launch_dwk_bwd<3, 1, true>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs);
+    else if (small) launch_dwk_bwd<3, 1, true, true>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs, fs);
     else launch_dw3_bwd_rows<1, true>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs, fs);
     return 1;
   }
   const bool v1 = lhn_dw_bwd_v1();
   if (k == 3 && dil == 1) {
     if (v1) launch_dwk_bwd<3, 1>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs);
+    else if (small) launch_dwk_bwd<3, 1, false, true>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs, fs);
     else launch_dw3_bwd_rows<1>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs, fs);
   } else if (k == 3 && dil == 2 && x->W >= 16) {       // parity sub-lattices
     if (v1) launch_dwk_bwd<3, 1>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 2, bs);

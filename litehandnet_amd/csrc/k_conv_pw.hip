@@ -1041,7 +1041,9 @@ static int launch_pw_bwd(const lhn_view* x, const float* w, const lhn_view* y, c
 //       BatchNorm-backward coefficients: 36 registers per thread in k_pw_bwd, re-read here from LDS at each commit), 38..55 KB:
 //       two workgroups per CU (the register file decides, not LDS), so one's loads, commit and stores run under the other's MFMAs.
 // dy is ALSO stored over dz, as k_dy_inplace does on the split path: the callers of lhn_conv_pw_bwd3 see the same buffers whichever
-// path ran (tests/test_pw_gpu.py pins dz = dy for these shapes).  PX: pixels per tile (64, or 32 where 64 does not fit the registers).
+// path ran (tests/test_pw_gpu.py pins dz = dy for these shapes) -- unless the caller declares dz dead (lhn_conv_pw_bwd6,
+// LHN_PW_BWD_DZ_DEAD): the DYST = false instances of the same shapes keep dy in LDS and save the write pass (the plan executor's
+// calls: 134 MB per launch on variant B's 64^2 maps at batch 64).  PX: pixels per tile (64, or 32 where 64 does not fit the registers).
 // PF: what rides in the register prefetch one tile ahead, 0 = x, 1 = x and y, 2 = x, y and dz; the rest is fetched inside commit()
 // four rows at a time, so that its registers are not live across the MFMA phase.
 //
@@ -1423,20 +1425,28 @@ extern "C" int lhn_conv_pw_bwd4(const lhn_view* x, const float* w, const lhn_vie
 }
 static int pw_bwd_run(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate, float* dw,
                       float* dbias, int stride, const float* dy_nchw, int nrep, int64_t rep_stride, const lhn_pw_opts* opts,
-                      const lhn_bnsum* bns, const lhn_bnbwdsrc* fin, const lhn_gatesum* gs, bool* gs_done, void* stream);
+                      const lhn_bnsum* bns, const lhn_bnbwdsrc* fin, const lhn_gatesum* gs, bool* gs_done, int flags, void* stream);
 // gs: gate-gradient sums of x's buffer (lhn_gatesum).  The streaming head kernel adds them in its launch; any other kernel is
 // followed by the lhn_gate_bwd_reduce3 launch over (x, dx) from here, so the caller finds the same sums whichever kernel ran.
 extern "C" int lhn_conv_pw_bwd5(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
                                 int dx_accumulate, float* dw, float* dbias, int stride, const float* dy_nchw, int nrep,
                                 int64_t rep_stride, const lhn_pw_opts* opts, const lhn_bnsum* bns, const lhn_bnbwdsrc* fin,
                                 const lhn_gatesum* gs, void* stream) {
+  return lhn_conv_pw_bwd6(x, w, y, gy, dx, dx_accumulate, dw, dbias, stride, dy_nchw, nrep, rep_stride, opts, bns, fin, gs, 0, stream);
+}
+// flags: LHN_PW_BWD_DZ_DEAD -- the wide register-W instances then run without their dy store (every other path forms dy where it
+// always did: the split path and k_dy_inplace need it in memory, k_pw_bwd and the narrow instances never stored it)
+extern "C" int lhn_conv_pw_bwd6(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
+                                int dx_accumulate, float* dw, float* dbias, int stride, const float* dy_nchw, int nrep,
+                                int64_t rep_stride, const lhn_pw_opts* opts, const lhn_bnsum* bns, const lhn_bnbwdsrc* fin,
+                                const lhn_gatesum* gs, int flags, void* stream) {
   if (gs && !gs->dgate) gs = nullptr;
   // (dx accumulated: the head kernel would sum this call's part of dx, the reduce launch the whole buffer -- refused, so the
   // result cannot depend on the route; the executor only ever passes the stored mode)
   if (gs) LHN_CHECK_ARG(lhn_view_ok(x) && dx && !dx_accumulate && stride == 1 && (!gs->slices || (gs->slices->n >= 0 && gs->slices->n <= 2)),
                         "lhn_conv_pw_bwd5: gate sums need a stored dx (no accumulate), stride 1 and 0..2 BatchNorm slices");
   bool gs_done = false;
-  const int rc = pw_bwd_run(x, w, y, gy, dx, dx_accumulate, dw, dbias, stride, dy_nchw, nrep, rep_stride, opts, bns, fin, gs, &gs_done, stream);
+  const int rc = pw_bwd_run(x, w, y, gy, dx, dx_accumulate, dw, dbias, stride, dy_nchw, nrep, rep_stride, opts, bns, fin, gs, &gs_done, flags, stream);
   if (rc || !gs || gs_done) return rc;
   lhn_view xv = *x;
   xv.gate = nullptr;
@@ -1444,7 +1454,7 @@ extern "C" int lhn_conv_pw_bwd5(const lhn_view* x, const float* w, const lhn_vie
 }
 static int pw_bwd_run(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate, float* dw,
                       float* dbias, int stride, const float* dy_nchw, int nrep, int64_t rep_stride, const lhn_pw_opts* opts,
-                      const lhn_bnsum* bns, const lhn_bnbwdsrc* fin, const lhn_gatesum* gs, bool* gs_done, void* stream) {
+                      const lhn_bnsum* bns, const lhn_bnbwdsrc* fin, const lhn_gatesum* gs, bool* gs_done, int flags, void* stream) {
   if (nrep < 1) nrep = 1;
   if (fin && !fin->sums) fin = nullptr;
   lhn_bnsum bs;
@@ -1495,9 +1505,13 @@ static int pw_bwd_run(const lhn_view* x, const float* w, const lhn_view* y, cons
   // LHN_PW_LDSW=1, which means "no register-W kernel", keep the split path)
   if (wr_wide) {
     int rc = -1;
-    if (Cin == 128 && Cout == 128) rc = launch_pw_bwd_wr<128, 128, 32, 1>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs, fin);
-    else if (Cin == 64 && Cout == 128) rc = launch_pw_bwd_wr<64, 128, 64, 1>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs, fin);
-    else if (Cin == 128 && Cout == 64) rc = launch_pw_bwd_wr<128, 64, 64, 2>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs, fin);
+#define PWB_WIDE(CI, CO, PXV, PFV) \
+  if (Cin == CI && Cout == CO)     \
+    rc = dz_dead ? launch_pw_bwd_wr<CI, CO, PXV, PFV, false>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs, fin) \
+                 : launch_pw_bwd_wr<CI, CO, PXV, PFV, true>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs, fin);
+    const bool dz_dead = (flags & LHN_PW_BWD_DZ_DEAD) != 0;      // dy stays in LDS: dz is only read
+    PWB_WIDE(128, 128, 32, 1) PWB_WIDE(64, 128, 64, 1) PWB_WIDE(128, 64, 64, 2)
+#undef PWB_WIDE
     if (rc == 0) {
       LHN_CHECK_LAUNCH("lhn_conv_pw_bwd");
       return 0;

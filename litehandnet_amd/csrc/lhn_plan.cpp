@@ -42,7 +42,8 @@ struct GraphEntry {
 struct Plan {
   std::vector<lhn_buf> bufs;
   std::vector<lhn_op> fwd, bwd;
-  std::vector<GraphEntry> graphs;      // LHN_GRAPH=1: replayed instead of ~150-400 individual launches
+  std::vector<uint8_t> pw_dz_dead;     // per backward op: an NHWC PW_BWD whose dz no later op touches (pw_dz_dead_at)
+  std::vector<GraphEntry> graphs;     // LHN_GRAPH=1: replayed instead of ~150-400 individual launches
   uint64_t tick = 0;
   int graph_misses = 0;
 };
@@ -151,6 +152,58 @@ static bool head_gate_fold_at(const Plan* P, const std::vector<lhn_op>& ops, siz
   return o.in_coff[0] == 0 && o.in_C[0] == b.C && b.gate_off >= 0 && nx.kind == OP_GATE_REDUCE && nx.out_buf == o.in_buf[0] &&
          nx.out_coff == 0 && nx.out_C == b.C && nx.ws[3] >= 0 && nx.ws[4] >= 0;
 }
+// No dy store from the wide 1x1 backward (LHN_PW_BWD_DZ_DEAD of lhn_conv_pw_bwd6; LHN_PW_BWD_DY_STORE=1, read once, keeps the store
+// for A/B runs).  dy = d loss / d (convolution output, in front of its BatchNorm) has two consumers, dX and dW of that convolution,
+// both inside the PW_BWD launch; every other backward op reads a gradient buffer as d (the buffer's values as its readers see
+// them), which is dz.  The backward list walks the forward records in reverse, so all writers of a view's gradient (its readers'
+// backward ops) and the BN_BWD / GATE_REDUCE ops over it stand in FRONT of its producer's PW_BWD.  What can stand behind it and
+// touch the same memory is another view of a shared gradient buffer (_alias_gradients: the hourglass Residual's conv3 and skip 1x1
+// both take d(sum) from one buffer) -- and that op wants dz, which an in-place dy only equals because neither convolution has a
+// BatchNorm.  So the flag would be right everywhere; it is still given only where the op list shows that nothing behind the PW_BWD
+// touches the view's gradient at all (as a buffer's gradient, channels overlapping, or through a byte offset in ws[]): then the
+// stored tensor has provably no reader and the bytes nobody looks at are the only difference.  Decided here, once per plan, and
+// not in the plan compiler: the op lists do not change.  Whole-plan runs only.  Variant B: all 3 wide PW_BWD ops (2 MSRB closing
+// 1x1 + the stem's 64 -> 128); A 8 of 8, M 6 of 6, H 4 of 5 (the Residual pair above keeps its store).
+static bool pw_bwd_dy_store() {
+  static int v = -1;
+  if (v < 0) {
+    const char* e = getenv("LHN_PW_BWD_DY_STORE");
+    v = (e && e[0] == '1') ? 1 : 0;
+  }
+  return v == 1;
+}
+static bool pw_dz_dead_at(const Plan* P, const std::vector<lhn_op>& ops, size_t oi) {
+  const lhn_op& o = ops[oi];
+  if (o.kind != OP_PW_BWD || o.i[1] || o.out_buf < 0 || P->bufs[o.out_buf].grad_off < 0) return false;
+  auto grad_bytes = [&](int buf, int64_t* lo, int64_t* hi) {
+    const lhn_buf& b = P->bufs[buf];
+    *lo = b.grad_off;
+    *hi = b.grad_off + (int64_t)sizeof(float) * b.N * b.H * b.W * b.C;
+    return b.grad_off >= 0;
+  };
+  int64_t lo, hi;
+  grad_bytes(o.out_buf, &lo, &hi);
+  const int oC = P->bufs[o.out_buf].C;
+  auto touches = [&](int buf, int coff, int C) {
+    int64_t a, b;
+    if (buf < 0 || !grad_bytes(buf, &a, &b) || a >= hi || lo >= b) return false;
+    // the same pixel stride: channel ranges decide; another layout over the same bytes: any overlap counts
+    return a != lo || P->bufs[buf].C != oC || (coff < o.out_coff + o.out_C && o.out_coff < coff + C);
+  };
+  for (size_t k = oi + 1; k < ops.size(); ++k) {
+    const lhn_op& q = ops[k];
+    if (q.kind == OP_MEMSET) {
+      if (q.ws[0] < hi && lo < q.ws[0] + q.ws[1]) return false;
+      continue;
+    }
+    if (touches(q.out_buf, q.out_coff, q.out_C)) return false;
+    for (int s = 0; s < 3; ++s)
+      if (touches(q.in_buf[s], q.in_coff[s], q.in_C[s])) return false;
+    for (int s = 0; s < 12; ++s)
+      if (q.ws[s] >= lo && q.ws[s] < hi) return false;
+  }
+  return true;
+}
 
 // creal: channels the BatchNorm really has when the convolution's output view is padded to a multiple of 4 (f.C then is the
 // layout of the statistics); repeat: the reference evaluates some units twice per forward (lite_hrnet.py:192-197), which
@@ -185,6 +238,8 @@ void* lhn_plan_create(const lhn_buf* bufs, int nbufs, const lhn_op* fwd, int nfw
         return nullptr;
       }
     }
+  p->pw_dz_dead.resize(p->bwd.size());
+  for (size_t oi = 0; oi < p->bwd.size(); ++oi) p->pw_dz_dead[oi] = pw_dz_dead_at(p, p->bwd, oi) ? 1 : 0;
   return p;
 }
 
@@ -194,6 +249,12 @@ int lhn_plan_head_gate_fold(void* plan) {
   for (size_t oi = 0; oi + 1 < p->bwd.size(); ++oi)
     if (head_gate_fold_at(p, p->bwd, oi)) return (int)oi + 1;
   return -1;
+}
+
+int lhn_plan_pw_dz_dead(void* plan, int bwd_index) {
+  const Plan* p = static_cast<const Plan*>(plan);
+  if (!p || bwd_index < 0 || (size_t)bwd_index >= p->pw_dz_dead.size()) return -1;
+  return p->pw_dz_dead[bwd_index];
 }
 
 void lhn_plan_destroy(void* plan) {
@@ -596,9 +657,10 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
           gsum.slices = &gsl;
           gfold_at = oi + 1;
         }
-        rc = lhn_conv_pw_bwd5(&x, prm<const float>(params, o.p[0]), &y, &g, dx, o.i[2] == 2, prm<float>(grads, o.p[1]),
+        const int flags = (phase == 1 && whole && P->pw_dz_dead[oi] && !pw_bwd_dy_store()) ? LHN_PW_BWD_DZ_DEAD : 0;
+        rc = lhn_conv_pw_bwd6(&x, prm<const float>(params, o.p[0]), &y, &g, dx, o.i[2] == 2, prm<float>(grads, o.p[1]),
                               prm<float>(grads, o.p[2]), o.i[0], nchw, nrep, rstr, &po, bs.sums ? &bs : nullptr,
-                              cfin_for == oi ? &cfin : nullptr, gsum.dgate ? &gsum : nullptr, stream);
+                              cfin_for == oi ? &cfin : nullptr, gsum.dgate ? &gsum : nullptr, flags, stream);
         break;
       }
       case OP_DW_BWD: {
