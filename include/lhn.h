@@ -59,7 +59,10 @@ typedef struct lhn_bnfin {
   float        eps, momentum, slope;
   const float* conv_bias;   /* bias of the convolution in front of the BatchNorm, or NULL (see lhn_bn_finalize) */
 } lhn_bnfin;
-/* same idea for lhn_bn_bwd_reduce -> lhn_bn_bwd_finalize */
+/* same idea for lhn_bn_bwd_reduce -> lhn_bn_bwd_finalize.  The slice must be y's: cstride, coff and C equal to those of the view
+ * the reduction runs over (the kernel strides sums and save by y->C), anything else returns the invalid-argument status before
+ * the launch.  The fused form has no pgrad_scale (dgamma / dbeta get the plain sums): SyncBatchNorm runs, which scale them by
+ * 1 / world, take the separate lhn_bn_bwd_finalize launch. */
 typedef struct lhn_bnbwdfin {
   uint32_t*    counter;
   const float* gamma;
@@ -363,6 +366,10 @@ int64_t lhn_msrb_round_scratch_bytes(int N, int H, int W, int C);   /* host-only
 int lhn_msrb_round_fwd(const lhn_view x[2], const lhn_view* extra /*[2] or NULL*/, const float* coef2 /*host, 2 floats, or NULL*/,
                        const float* w_d1 /*[C/2,1,3,3]*/, const float* w_d2 /*[C/2,1,3,3]*/, const lhn_view* y /*C channels*/,
                        float* pooled /*[N,OH,OW,C] or NULL*/, int OH, int OW, void* scratch, void* stream);
+/* Cout = 8, 16, .. 256 (a power of two times 8), k = 1, 3, 5 or 7.  3x3 -> 32 and 7x7 -> 64 run on MFMA kernels; every other shape
+ * on the direct kernel, which keeps the weights and its reduction scratch in 3*k*k*Cout*4 + 16384 bytes of LDS: a shape that
+ * needs more than 65536 bytes (k = 7 with Cout >= 128, k = 5 with Cout = 256) returns the invalid-argument status before any
+ * launch, with the byte count in the text, and writes nothing. */
 int lhn_conv_stem_fwd(const float* img /*[N,3,Hi,Wi]*/, const float* w /*[Cout,3,k,k]*/, const lhn_view* y,
                       double* stats, int Hi, int Wi, int k, int stride, int pad, const lhn_bnfin* fin, void* stream);
 /* wt_scratch: optional 9*Cout*Cin floats of caller-owned scratch; the call re-lays the OIHW weights tap-major into it
@@ -387,7 +394,9 @@ int lhn_conv_kxk_fwd_bf16x3(const lhn_view* x, const float* w /*[Cout,Cin,3,3]*/
                             void* wsplit /* 9*Cout*Cin*4 bytes, required */, int relay /* 1: rebuild wsplit from w */, void* stream);
 /* conv_bias: a biased convolution followed by BatchNorm (models/pose_hg_ms_att.py:27-35,46-56) stores its output
  * WITHOUT the bias -- BatchNorm cancels it -- and the bias only enters the running mean (training) or the shift
- * (eval: beta - (running_mean - bias) * scale).  d(bias) is identically zero in training mode. */
+ * (eval: beta - (running_mean - bias) * scale).  d(bias) is identically zero in training mode.
+ * training = 0: the table comes from the running statistics; running_mean, running_var, num_batches_tracked and
+ * save_mean_invstd are not written (there are no batch statistics to save). */
 int lhn_bn_finalize(const double* stats, const float* gamma, const float* beta, float* running_mean,
                     float* running_var, int64_t* num_batches_tracked, float* table, int cstride, int coff,
                     int C, float* save_mean_invstd /*[2][C]*/, double count, float eps, float momentum,

@@ -499,6 +499,9 @@ extern "C" int lhn_conv_stem_fwd(const float* img, const float* w, const lhn_vie
   LHN_CHECK_ARG(y->H == Ho && y->W == Wo, "lhn_conv_stem_fwd: output %dx%d, expected %dx%d", y->H, y->W, Ho, Wo);
   const int PL = 256 / (y->C / 8);
   const size_t lds = (size_t)(3 * k * k * y->C) * 4 + 256 * 16 * 4;
+  const bool mfma = !lhn_dw_force_gather() && ((k == 7 && y->C == 64) || (k == 3 && y->C == 32));
+  // the direct kernel is launched without a dynamic-LDS opt-in: 64 KiB is what a launch may ask for unprepared
+  LHN_CHECK_ARG(mfma || lds <= 65536, "lhn_conv_stem_fwd: k=%d Cout=%d needs %zu B of LDS (limit 65536 B)", k, y->C, lds);
   if (k == 7 && y->C == 64 && !lhn_dw_force_gather()) {
     const size_t lds7 = (size_t)64 * 164 * 4 + 2 * 2 * 64 * 8;
     static LhnKernelCfg cfg7;

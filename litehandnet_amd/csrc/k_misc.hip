@@ -69,7 +69,7 @@ __global__ void __launch_bounds__(LHN_FIN_THREADS) k_bn_finalize(const double* _
     table[coff + c] = sc;
     table[cs + coff + c] = b - (float)mean * sc;
     table[2 * cs + coff + c] = slope;
-    if (save) {
+    if (save && training) {      // eval: no batch statistics to save (torch's batch_norm returns none either); save keeps its bytes
       save[c] = (float)mean;
       save[SC + c] = invstd;
     }
@@ -2114,6 +2114,10 @@ int lhn_bn_bwd_reduce(const lhn_view* y, const lhn_gradview* g, const float* sav
   lhn_bnbwdfin fin;
   if (finp) fin = *finp; else fin.counter = nullptr;
   LHN_CHECK_ARG(lhn_view_ok(y) && g && g->dz && save && sums && y->C % 4 == 0 && y->C <= 1024 && lhn_no_pend(y), "lhn_bn_bwd_reduce: bad args");
+  // the kernel strides sums / save by y->C; the fused finalize indexes the same arrays by fin->C and writes coef at fin's slice
+  LHN_CHECK_ARG(!fin.counter || (fin.C == y->C && fin.coff == y->coff && fin.cstride == y->cstride),
+                "lhn_bn_bwd_reduce: fused finalize slice C=%d coff=%d cstride=%d differs from y's C=%d coff=%d cstride=%d", fin.C, fin.coff,
+                fin.cstride, y->C, y->coff, y->cstride);
   hipLaunchKernelGGL(k_bn_bwd_reduce, dim3(grid_cap((int64_t)y->N * y->H, 8)), dim3(256), 0, (hipStream_t)stream, *y, *g, save, sums, fin);
   LHN_CHECK_LAUNCH("lhn_bn_bwd_reduce");
   return 0;
