@@ -465,7 +465,10 @@ int lhn_ca_mlp_fwd(const float* pooled /*[N,9,C]*/, const float* w3 /*[C,1,3,3]*
  * over N*count_scale samples.  Backward: pgrad_scale (1/world) scales d(gamma), d(beta), which come from global sums. */
 
 /* attention of `mynet` (models/pose_hg_ms_att.py:165-174,191-192) on the pooled [N,9,C] tensor:
- * gate = sigmoid(Linear(dropout(dw3x3(relu(BN(pooled))) + b3))); save = floats[3*N*C + 2*C] */
+ * gate = sigmoid(Linear(dropout(dw3x3(relu(BN(pooled))) + b3))); save = floats[3*N*C + 2*C]
+ * refused: N <= 0, C outside 1..256, gate_stride < gate_coff + C (backward: cstride < coff + C), a stage outside 0..2, stage 1 / 2
+ * without gsum or with count_scale < 1.
+ * backward: H < 2 or W < 2 is refused -- the segment layout of the pooled gradient (one slot per pixel) needs two pixels per axis */
 int lhn_att_mlp_fwd(const float* pooled, const float* gamma, const float* beta, float* rmean, float* rvar,
                     int64_t* nbt, const float* w3 /*[C,1,3,3]*/, const float* b3, const float* wl /*[C,C]*/,
                     const float* bl, const float* dropmask /*[N,C] or NULL*/, float* gate, int gate_stride,
@@ -483,7 +486,8 @@ int lhn_se_mlp_fwd(const float* pooled, const float* w1 /*[J,C]*/, const float* 
                    const float* b2, float* gate, int gate_stride, int gate_coff, float* save, int N, int C, int J,
                    void* stream);
 /* mode 1: SpatialWeighting of lite_hrnet.py:55-74 -- sigmoid(relu(.)) after both 1x1 convolutions (mode 0 = SEBlock).
- * b1 and b2 (and db1, db2) may both be NULL: the bias-free nn.Linear pair of hourglass_ablation.py:201-209 */
+ * b1 and b2 (and db1, db2) may both be NULL: the bias-free nn.Linear pair of hourglass_ablation.py:201-209
+ * refused: a mode other than 0 or 1; gate_stride < gate_coff + C (backward: cstride < coff + C); N <= 0, C outside 1..256, J outside 1..64 */
 int lhn_se_mlp_fwd2(const float* pooled, const float* w1, const float* b1, const float* w2, const float* b2, float* gate,
                     int gate_stride, int gate_coff, float* save, int N, int C, int J, int mode, void* stream);
 int lhn_se_mlp_bwd2(const float* pooled, const float* w1, const float* w2, const float* save, const float* dgate,
@@ -637,6 +641,7 @@ int lhn_conv_pw_bwd6(const lhn_view* x, const float* w, const lhn_view* y, const
                      void* stream);
 int lhn_avgpool_fwd3(const lhn_view* x, float* out /*[N,OH,OW,C]*/, int OH, int OW, float* pstat /*[N*OH*OW][2][C] or NULL*/,
                      const lhn_bn_slices* slices, void* stream);
+/* H < 2 or W < 2 is refused: the segment layout of the pooled gradient needs two pixels per axis */
 int lhn_ca_mlp_bwd2(const float* pooled, const float* w3, const float* gamma, const float* w1, const float* w2,
                     const float* dropmask, const float* save, const float* dgate, float* dpool, int cstride, int coff, int H,
                     int W, float* dw3, float* dgamma, float* dbeta, float* dw1, float* db1, float* dw2, float* db2, int N, int C,

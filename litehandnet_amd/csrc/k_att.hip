@@ -237,7 +237,9 @@ extern "C" int lhn_att_mlp_fwd(const float* pooled, const float* gamma, const fl
                                float* gate, int gate_stride, int gate_coff, float* save, int N, int C, float eps, float momentum,
                                int training, int stage, double* gsum, double count_scale, void* stream) {
   LHN_CHECK_ARG(pooled && gamma && beta && rmean && rvar && w3 && wl && bl && gate && save, "lhn_att_mlp_fwd: null pointer");
-  LHN_CHECK_ARG(C > 0 && C <= 256 && N > 0, "lhn_att_mlp_fwd: C=%d (<=256)", C);
+  LHN_CHECK_ARG(C > 0 && C <= 256 && N > 0, "lhn_att_mlp_fwd: N=%d C=%d (N > 0, 0 < C <= 256)", N, C);
+  LHN_CHECK_ARG(gate_coff >= 0 && gate_stride >= gate_coff + C, "lhn_att_mlp_fwd: gate_stride=%d < gate_coff=%d + C=%d", gate_stride,
+                gate_coff, C);
   hipStream_t s = (hipStream_t)stream;
   LHN_CHECK_ARG(stage == 0 || (gsum && stage >= 1 && stage <= 2 && count_scale >= 1), "lhn_att_mlp_fwd: stage %d needs gsum", stage);
   hipLaunchKernelGGL(k_att1, dim3((C + 31) / 32), dim3(1024), 0, s, pooled, gamma, beta, rmean, rvar, nbt, w3, b3, dropmask, save, N,
@@ -253,7 +255,9 @@ extern "C" int lhn_att_mlp_bwd(const float* pooled, const float* gamma, const fl
                                int stage, double* gsum, double count_scale, float pgrad_scale, void* stream) {
   LHN_CHECK_ARG(pooled && gamma && beta && w3 && wl && save && dgate && dpool && dgamma && dbeta && dw3 && dwl && dbl,
                 "lhn_att_mlp_bwd: null pointer");
-  LHN_CHECK_ARG(C > 0 && C <= 256 && N > 0, "lhn_att_mlp_bwd: C=%d (<=256)", C);
+  LHN_CHECK_ARG(C > 0 && C <= 256 && N > 0, "lhn_att_mlp_bwd: N=%d C=%d (N > 0, 0 < C <= 256)", N, C);
+  LHN_CHECK_ARG(H >= 2 && W >= 2, "lhn_att_mlp_bwd: H=%d W=%d: the segment layout of the pooled gradient needs H, W >= 2", H, W);
+  LHN_CHECK_ARG(coff >= 0 && cstride >= coff + C, "lhn_att_mlp_bwd: cstride=%d < coff=%d + C=%d", cstride, coff, C);
   hipStream_t s = (hipStream_t)stream;
   float* dad = save + (int64_t)N * C * 2 + 2 * C;
   LHN_CHECK_ARG(stage == 0 || (gsum && stage >= 1 && stage <= 2 && count_scale >= 1), "lhn_att_mlp_bwd: stage %d needs gsum", stage);
@@ -347,7 +351,10 @@ extern "C" int lhn_se_mlp_fwd(const float* pooled, const float* w1, const float*
 extern "C" int lhn_se_mlp_fwd2(const float* pooled, const float* w1, const float* b1, const float* w2, const float* b2, float* gate,
                                int gate_stride, int gate_coff, float* save, int N, int C, int J, int mode, void* stream) {
   LHN_CHECK_ARG(pooled && w1 && w2 && gate && save && !b1 == !b2, "lhn_se_mlp_fwd: null pointer (b1, b2: both or neither)");
-  LHN_CHECK_ARG(C > 0 && C <= 256 && J > 0 && J <= 64 && N > 0, "lhn_se_mlp_fwd: C=%d J=%d (C <= 256, J <= 64)", C, J);
+  LHN_CHECK_ARG(C > 0 && C <= 256 && J > 0 && J <= 64 && N > 0, "lhn_se_mlp_fwd: N=%d C=%d J=%d (N > 0, 0 < C <= 256, 0 < J <= 64)", N, C, J);
+  LHN_CHECK_ARG(mode == 0 || mode == 1, "lhn_se_mlp_fwd: mode=%d (0 or 1)", mode);
+  LHN_CHECK_ARG(gate_coff >= 0 && gate_stride >= gate_coff + C, "lhn_se_mlp_fwd: gate_stride=%d < gate_coff=%d + C=%d", gate_stride,
+                gate_coff, C);
   hipLaunchKernelGGL(k_se_fwd, dim3(N), dim3(128), 0, (hipStream_t)stream, pooled, w1, b1, w2, b2, save, gate, gate_stride, gate_coff,
                      N, C, J, mode);
   LHN_CHECK_LAUNCH("lhn_se_mlp_fwd");
@@ -366,7 +373,10 @@ extern "C" int lhn_se_mlp_bwd2(const float* pooled, const float* w1, const float
                                float* dpool, int cstride, int coff, int H, int W, float* dw1, float* db1, float* dw2, float* db2,
                                int N, int C, int J, int mode, void* stream) {
   LHN_CHECK_ARG(pooled && w1 && w2 && save && dgate && dpool && dw1 && dw2 && !db1 == !db2, "lhn_se_mlp_bwd: null pointer (db1, db2: both or neither)");
-  LHN_CHECK_ARG(C > 0 && C <= 256 && J > 0 && J <= 64 && N > 0 && H > 0 && W > 0, "lhn_se_mlp_bwd: C=%d J=%d", C, J);
+  LHN_CHECK_ARG(C > 0 && C <= 256 && J > 0 && J <= 64 && N > 0 && H > 0 && W > 0,
+                "lhn_se_mlp_bwd: N=%d C=%d J=%d H=%d W=%d (N, H, W > 0, 0 < C <= 256, 0 < J <= 64)", N, C, J, H, W);
+  LHN_CHECK_ARG(mode == 0 || mode == 1, "lhn_se_mlp_bwd: mode=%d (0 or 1)", mode);
+  LHN_CHECK_ARG(coff >= 0 && cstride >= coff + C, "lhn_se_mlp_bwd: cstride=%d < coff=%d + C=%d", cstride, coff, C);
   hipLaunchKernelGGL(k_se_bwd, dim3(lhn_deterministic_mode() ? 1 : N), dim3(256), 0, (hipStream_t)stream, pooled, w1, w2, save, dgate, dpool, cstride, coff,
                      1.f / (float)(H * W), dw1, db1, dw2, db2, N, C, J, mode);
   LHN_CHECK_LAUNCH("lhn_se_mlp_bwd");

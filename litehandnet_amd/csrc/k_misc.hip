@@ -2089,6 +2089,7 @@ int lhn_ca_mlp_bwd2(const float* pooled, const float* w3, const float* gamma, co
   LHN_CHECK_ARG(pooled && w3 && gamma && w1 && w2 && save && dgate && dpool && dw3 && dgamma && dbeta && dw1 && db1 && dw2 && db2,
                 "lhn_ca_mlp_bwd: null pointer");
   LHN_CHECK_ARG(C > 0 && C <= 256 && C % 2 == 0, "lhn_ca_mlp_bwd: C=%d", C);
+  LHN_CHECK_ARG(H >= 2 && W >= 2, "lhn_ca_mlp_bwd: H=%d W=%d: the segment layout of the pooled gradient needs H, W >= 2", H, W);
   hipStream_t s = (hipStream_t)stream;
   // scratch behind the forward's save area: dahat [N][C] | dv [N][C] | dh [N][C/2]  (save holds 6 N C + 2 C floats in all)
   float* dahat = const_cast<float*>(save) + (int64_t)N * C * 3 + (int64_t)N * (C / 2) + 2 * C;

@@ -173,7 +173,8 @@ __device__ __forceinline__ int lhn_bin_hi(int i, int S) { return ((i + 1) * S + 
 // The pooled gradient is stored per SEGMENT, not per bin: the three (possibly overlapping) bins cut each axis into at
 // most five segments -- {bin0}, {bin0,bin1}, {bin1}, {bin1,bin2}, {bin2} -- and the attention backward writes
 // dpool[n][sh*5+sw][c] = sum of (d loss / d pooled[bin]) / |bin| over the bins of segment (sh, sw).  A consumer then needs
-// ONE branch-free load per pixel instead of a divergent loop over up to four bins (H, W >= 2).
+// ONE branch-free load per pixel instead of a divergent loop over up to four bins.  H, W >= 2: on a 1-pixel axis the
+// pixel lies in all three bins but reads the {bin1} segment only, so the writers' entry points refuse such a map.
 #define LHN_DPOOL_SLOTS 25
 __device__ __forceinline__ int lhn_pool_seg(int h, int S) {
   return (h >= lhn_bin_lo(1, S)) + (h >= lhn_bin_hi(0, S)) + (h >= lhn_bin_lo(2, S)) + (h >= lhn_bin_hi(1, S));

@@ -581,11 +581,19 @@ class PlanBuilder:
         self.recs.append(dict(op=SHUFFLE, a=a, b=b, out=out))
         return out
 
+    def _dpool_segments(self, y, what):
+        """The backward of a 3x3-pooled attention stores its pooled gradient per segment (lhn_common.h: lhn_dpool_store), and a
+        1-pixel axis lies in all three bins but in one segment only: two thirds of that gradient would be lost."""
+        if self.with_backward and min(y.H, y.W) < 2:
+            raise _lib.LhnError(f"{what} on a {y.H} x {y.W} map: the segment layout of the pooled gradient needs H, W >= 2 "
+                                "(forward-only plans take any map)")
+
     def channel_attention(self, y, ca):
         """common.py:40-66 on the WHOLE buffer behind `y`: sets the buffer's gate.  Returns y."""
         b = self.bufs[y.buf]
         assert y.coff == 0 and y.C == b.C, "channel attention gates a whole buffer"
         assert not b.gate, "buffer is already gated"
+        self._dpool_segments(y, "channel attention")
         Cc = y.C
         pooled = self._ws("misc", self.N * 9 * Cc * 4)
         save = self._ws("misc", (6 * self.N * Cc + 2 * Cc) * 4)          # forward rows + backward scratch (lhn_ca_mlp_bwd)
@@ -629,6 +637,7 @@ class PlanBuilder:
         nn.Sequential (1 = BatchNorm2d, 3 = depthwise 3x3 conv, 6 = Linear).  Sets the buffer's gate, returns y."""
         b = self.bufs[y.buf]
         assert y.coff == 0 and y.C == b.C and not b.gate, "attention gates a whole, ungated buffer"
+        self._dpool_segments(y, "`mynet` attention")
         Cc = y.C
         rec = dict(op=ATT_MLP, y=y, att=att, pooled=self._ws("misc", self.N * 9 * Cc * 4),
                    save=self._ws("misc", (3 * self.N * Cc + 2 * Cc) * 4),

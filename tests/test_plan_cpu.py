@@ -311,3 +311,22 @@ def test_product_combine_with_activation_is_forward_only():
     pf = PlanBuilder(2, {}, image_hw=(16, 16), with_backward=False, p_drop=0.0)
     pf.set_output(pf.ew([pf.new(8, 8, 16), pf.new(2, 2, 16)], out_slope=0.1, mode=EW_MUL))
     assert pf.finalize()[4] == 0
+
+
+def test_pooled_attention_backward_needs_two_pixels_per_axis():
+    """The 3x3-pooled attentions store their pooled gradient per segment (lhn_common.h: lhn_dpool_store); a 1-pixel axis lies in all
+    three bins but in one segment, so a plan with backward must not gate such a map.  Forward-only plans take any map."""
+    from litehandnet_amd._lib import LhnError
+
+    for hw in ((1, 1), (1, 4), (4, 1)):
+        for gate in ("me_attention", "channel_attention"):
+            pb = PlanBuilder(2, {}, image_hw=(16, 16), with_backward=True, p_drop=0.0)
+            with pytest.raises(LhnError, match="segment layout of the pooled gradient"):
+                getattr(pb, gate)(pb.new(hw[0], hw[1], 16), None)
+            pf = PlanBuilder(2, {}, image_hw=(16, 16), with_backward=False, p_drop=0.0)
+            y = getattr(pf, gate)(pf.new(hw[0], hw[1], 16), None)
+            assert pf.bufs[y.buf].gate and not pf.bufs[y.buf].dpool
+    pb = PlanBuilder(2, {}, image_hw=(16, 16), with_backward=True, p_drop=0.0)           # the smallest map a backward plan gates
+    for gate in ("me_attention", "channel_attention"):
+        y = getattr(pb, gate)(pb.new(2, 2, 16), None)
+        assert pb.bufs[y.buf].gate and pb.bufs[y.buf].dpool
