@@ -518,14 +518,14 @@ int lhn_conv_dw_bwd(const lhn_view* x, const float* w, const lhn_view* y, const 
 /* ... and, when this convolution is the only reader of x and x is the output of a convolution + BatchNorm, the
  * BatchNorm-backward sums of THAT producer (sum du, sum du * xhat into bn_sums[LHN_STAT_REPLICAS][2][bn_C] at channel
  * bn_coff, mean / invstd from bn_save) -- the kernel has d(x), the raw x and its table in hand; lhn_bn_bwd_reduce of the
- * producer is then skipped.  3x3, stride 1, dilation 1, dx stored (not accumulated), x ungated.  bn_sums NULL: lhn_conv_dw_bwd. */
+ * producer is then skipped.  3x3, stride 1, dilation 1, dx stored (not accumulated), x ungated.  bn_sums NULL: no sums. */
 int lhn_conv_dw_bwd2(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate,
                      float* dw, int k, int stride, int pad, int dil, int nrep, int64_t rep_stride, double* bn_sums,
                      const float* bn_save, int bn_C, int bn_coff, void* stream);
 /* ... and with up to two gradient ADDENDS: dx = [dx +] dgrad + dx_add0 + dx_add1, where dx_add* point at buffers of dx's
  * geometry (same pixel stride; the pointer already carries any channel shift).  They are the output gradients of residual
  * sums that read x (litehourglass.py:41-49: `out = out + ca(cat)`): the sum's backward costs no pass of its own.  Needs the
- * tiled kernel (stride 1, "same" padding, W >= 8).  Both NULL: lhn_conv_dw_bwd. */
+ * tiled kernel (stride 1, "same" padding, W >= 8).  Both NULL: no addends. */
 int lhn_conv_dw_bwd3(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate,
                      float* dw, int k, int stride, int pad, int dil, int nrep, int64_t rep_stride, const float* dx_add0,
                      const float* dx_add1, void* stream);
@@ -572,14 +572,32 @@ int lhn_conv_pw_bwd3(const lhn_view* x, const float* w, const lhn_view* y, const
                      float* dw, float* dbias, int stride, const float* dy_nchw, int nrep, int64_t rep_stride,
                      const lhn_pw_opts* opts, const lhn_bnsum* bns /*fused kernel only: Cin * Cout < 64 * 128, stride 1*/, void* stream);
 /* The two backward calls above with the BatchNorm-backward finalize of y taken in the kernel's prologue (lhn_bnbwdsrc; fin NULL =
- * the calls above).  gy->coef must point at the coefficient table: it is written.  lhn_conv_dw_bwd4 joins lhn_conv_dw_bwd2 (bns: the
- * producer's sums, x's first channel at bns->coff) and lhn_conv_dw_bwd3 (addends); bns and addends exclude each other as they do there.
+ * the calls above).  gy->coef must point at the coefficient table: it is written.  lhn_conv_dw_bwd4 takes everything a depthwise
+ * backward may carry: bns (the producer's sums of lhn_conv_dw_bwd2, x's first channel at bns->coff; NULL or bns->sums NULL: none),
+ * the addends of lhn_conv_dw_bwd3, and fin; bns and addends exclude each other.
  * In-prologue fold: k_dw3_bwd_rows (3x3, stride 1, "same" padding, W >= 8; dilation 1 on maps of at most 256 pixels: the tile kernel
  * k_dwk_bwd_lds, same fold, LHN_DW_BWD_SMALL=0 keeps the row kernel) and k_pw_bwd_wr (the shapes listed at lhn_conv_pw_bwd3's
  * register-W dispatch); every other kernel gets a lhn_bn_bwd_finalize2 launch in front, from this call. */
 int lhn_conv_dw_bwd4(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate,
                      float* dw, int k, int stride, int pad, int dil, int nrep, int64_t rep_stride, const lhn_bnsum* bns,
                      const float* dx_add0, const float* dx_add1, const lhn_bnbwdsrc* fin, void* stream);
+/* Which kernel lhn_conv_dw_fwd3 (backward = 0) / lhn_conv_dw_bwd4 (backward = 1) launches for this shape and feature set: host-only
+ * (no device needed, nothing is launched), answered by the function the two calls themselves ask.  H, W, C are x's.
+ * features: what the call carries.  switches: -1 = as this process read them from the environment, else a set of LHN_DW_SW_* bits.
+ * Returns a static string (per thread, valid until the next call) in the spelling of profiles/dw_instances.md ("k_dw3_bwd_rows<1,BNS>
+ * ps=2", "k_dw_bwd_data<7> + k_dw_bwd_weight<7,1> x 7", with "lhn_bn_bwd_finalize2 + " in front when the finalize takes its own
+ * launch), or NULL when no kernel exists for the combination.  Arguments a call would refuse for another reason are not checked. */
+#define LHN_DW_F_NO_WEIGHT 1   /* w (and dw) NULL: the k = 1 identity */
+#define LHN_DW_F_EXTRA     2   /* forward: a second source */
+#define LHN_DW_F_BNSUM     4   /* backward: the producer's BatchNorm sums */
+#define LHN_DW_F_ADDS      8   /* backward: gradient addends */
+#define LHN_DW_F_FIN       16  /* backward: a finalize source (lhn_bnbwdsrc) */
+#define LHN_DW_F_NO_DX     32  /* backward: dx NULL */
+#define LHN_DW_F_DX_ACC    64  /* backward: dx accumulated */
+#define LHN_DW_SW_GATHER    1  /* LHN_DW_GATHER=1 */
+#define LHN_DW_SW_BWD_V1    2  /* LHN_DW_BWD_V1=1 */
+#define LHN_DW_SW_BWD_SMALL 4  /* the small-map route: set unless LHN_DW_BWD_SMALL=0 */
+const char* lhn_conv_dw_route(int backward, int H, int W, int C, int k, int stride, int pad, int dil, int features, int switches);
 int lhn_conv_pw_bwd4(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate,
                      float* dw, float* dbias, int stride, const float* dy_nchw, int nrep, int64_t rep_stride,
                      const lhn_pw_opts* opts, const lhn_bnsum* bns, const lhn_bnbwdsrc* fin, void* stream);

@@ -1,4 +1,4 @@
-// Depthwise k x k convolution (stride, dilation) and the 3-channel stem convolution, NHWC fp32.
+// Depthwise k x k convolution (stride, dilation), NHWC fp32.
 // HBM-bound: each thread owns 4 channels of one output pixel and gathers its taps through L1/L2
 // (neighbouring outputs share them), applying the producer's pending BatchNorm/activation on load;
 // the epilogue accumulates this layer's BatchNorm statistics (one double atomic per block+channel).
@@ -109,293 +109,6 @@ __global__ void __launch_bounds__(256) k_dw_fwd(lhn_view x, const float* __restr
   }
 }
 
-// ------------------------------------------------------------------ stem forward (NCHW 3-channel image -> NHWC)
-// thread = (output pixel, group of 8 output channels)
-__global__ void __launch_bounds__(256) k_stem_fwd(const float* __restrict__ img, const float* __restrict__ w, lhn_view y,
-                                                  double* __restrict__ stats, int Hi, int Wi, int K, int stride, int pad,
-                                                  lhn_bnfin fin) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int CO = y.C, CG = CO >> 3, KK = K * K, T = 3 * KK;
-  float* Ws = smem;                                  // [T][CO]
-  float* red = smem + T * CO;                        // [256][16]
-  const int tid = threadIdx.x;
-  for (int i = tid; i < T * CO; i += 256) {
-    const int co = i / T, t = i - co * T;
-    Ws[t * CO + co] = w[i];
-  }
-  __syncthreads();
-  const int cg = tid % CG, pl = tid / CG, PL = 256 / CG;
-  const int64_t total = (int64_t)y.N * y.H * y.W;
-  float s[8], q[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) s[j] = q[j] = 0.f;
-  for (int64_t pix = (int64_t)blockIdx.x * PL + pl; pix < total; pix += (int64_t)gridDim.x * PL) {
-    const int wo = (int)(pix % y.W);
-    const int64_t t = pix / y.W;
-    const int ho = (int)(t % y.H), n = (int)(t / y.H);
-    float acc[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-    for (int c = 0; c < 3; ++c) {
-      const float* plane = img + ((int64_t)n * 3 + c) * Hi * Wi;
-      for (int kh = 0; kh < K; ++kh) {
-        const int ih = ho * stride - pad + kh;
-        if (ih < 0 || ih >= Hi) continue;
-        for (int kw = 0; kw < K; ++kw) {
-          const int iw = wo * stride - pad + kw;
-          if (iw < 0 || iw >= Wi) continue;
-          const float v = plane[(int64_t)ih * Wi + iw];
-          const float* wr = Ws + (c * KK + kh * K + kw) * CO + cg * 8;
-          const f4 w0 = *reinterpret_cast<const f4*>(wr), w1 = *reinterpret_cast<const f4*>(wr + 4);
-          acc[0] += v * w0.x; acc[1] += v * w0.y; acc[2] += v * w0.z; acc[3] += v * w0.w;
-          acc[4] += v * w1.x; acc[5] += v * w1.y; acc[6] += v * w1.z; acc[7] += v * w1.w;
-        }
-      }
-    }
-    float* o = y.data + pix * y.cstride + y.coff + cg * 8;
-    *reinterpret_cast<f4*>(o) = (f4){acc[0], acc[1], acc[2], acc[3]};
-    *reinterpret_cast<f4*>(o + 4) = (f4){acc[4], acc[5], acc[6], acc[7]};
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      s[j] += acc[j];
-      q[j] += acc[j] * acc[j];
-    }
-  }
-  if (stats) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      red[tid * 16 + j] = s[j];
-      red[tid * 16 + 8 + j] = q[j];
-    }
-    __syncthreads();
-    if (tid < CO) {
-      const int g = tid >> 3, j = tid & 7;
-      double sd = 0, qd = 0;
-      for (int p = 0; p < PL; ++p) {
-        sd += red[(p * CG + g) * 16 + j];
-        qd += red[(p * CG + g) * 16 + 8 + j];
-      }
-      double* st = stats + (size_t)(blockIdx.x % LHN_STAT_REPLICAS) * 2 * CO;
-      atomicAdd(st + tid, sd);
-      atomicAdd(st + CO + tid, qd);
-    }
-    if (fin.counter && lhn_last_block(fin.counter)) lhn_bn_finalize_block(fin, stats);
-  }
-}
-
-
-// ------------------------------------------------------------------ stem forward, 3x3 -> 32 features (the stems of
-// litehourglass.py / liteHandNet.py / lite_hrnet.py) on MFMA: out[pixel][co] = patch[pixel][27 taps] * W^T is a GEMM with
-// K = 27 (padded to 32).  The block parks the im2col patch of a 256-pixel tile in LDS (thread = pixel: its 27 image taps are
-// loaded ONCE; the direct kernel k_stem_fwd re-reads them per group of 8 features and is bound by 216 LDS weight reads per
-// pixel: 125 us for a 184 MB problem); every wave holds all weights as 16 MFMA B registers and runs 2 x 16
-// v_mfma_f32_32x32x2_f32 over its 64 pixels.  The accumulator layout gives each lane ONE feature: stores are 128-byte rows,
-// statistics need no cross-lane work beyond the two lane halves.  The next tile's taps are loaded while this one computes.
-__global__ void __launch_bounds__(256) k_stem3_fwd_mfma(const float* __restrict__ img, const float* __restrict__ w, lhn_view y,
-                                                        double* __restrict__ stats, int Hi, int Wi, int stride, int pad, lhn_bnfin fin) {
-  constexpr int CO = 32, LDV = 36;
-  __shared__ __attribute__((aligned(16))) float Vs[256 * LDV];      // [pixel][tap], columns 27..31 stay zero
-  __shared__ double redd[4][2 * CO];
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, lh = lane >> 5;
-  // B fragments: MFMA step ks, lane (n = l31, k = lh) holds W[tap = 16 lh + ks][co = l31]  (the A reads use the same K order)
-  float wreg[16];
-#pragma unroll
-  for (int ks = 0; ks < 16; ++ks) {
-    const int tap = 16 * lh + ks;
-    wreg[ks] = tap < 27 ? w[l31 * 27 + tap] : 0.f;
-  }
-  for (int t = 27; t < 32; ++t) Vs[tid * LDV + t] = 0.f;
-  const int64_t total = (int64_t)y.N * y.H * y.W;
-  const int64_t ntiles = (total + 255) / 256;
-  float v[27];
-  auto issue = [&](int64_t tile) __attribute__((always_inline)) {
-    const int64_t pix = tile * 256 + tid;
-    const int64_t pc = pix < total ? pix : total - 1;
-    const int wo = (int)(pc % y.W);
-    const int64_t r = pc / y.W;
-    const int ho = (int)(r % y.H), n = (int)(r / y.H);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float* plane = img + ((int64_t)n * 3 + c) * Hi * Wi;
-#pragma unroll
-      for (int kh = 0; kh < 3; ++kh) {
-        const int ih = ho * stride - pad + kh, ihc = min(max(ih, 0), Hi - 1);
-#pragma unroll
-        for (int kw = 0; kw < 3; ++kw) {
-          const int iw = wo * stride - pad + kw, iwc = min(max(iw, 0), Wi - 1);
-          const float t = plane[(int64_t)ihc * Wi + iwc];
-          v[c * 9 + kh * 3 + kw] = (ih == ihc && iw == iwc) ? t : 0.f;
-        }
-      }
-    }
-  };
-  float s = 0.f, q = 0.f, kk = 0.f;      // this lane's feature: shifted sums over its pixels (see TileStat)
-  int cnt = 0;
-  int64_t tile = blockIdx.x;
-  if (tile < ntiles) issue(tile);
-  for (; tile < ntiles; tile += gridDim.x) {
-    __syncthreads();                       // the previous tile's A reads are done
-#pragma unroll
-    for (int t = 0; t < 27; ++t) Vs[tid * LDV + t] = v[t];
-    __syncthreads();
-    if (tile + gridDim.x < ntiles) issue(tile + gridDim.x);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int prow = wave * 64 + 32 * h;
-      const f4* ap = reinterpret_cast<const f4*>(Vs + (prow + l31) * LDV + 16 * lh);
-      const f4 a0 = ap[0], a1 = ap[1], a2 = ap[2], a3 = ap[3];
-      const float a[16] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w, a2.x, a2.y, a2.z, a2.w, a3.x, a3.y, a3.z, a3.w};
-      f16v acc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-      for (int ks = 0; ks < 16; ++ks) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[ks], wreg[ks], acc, 0, 0, 0);
-      const int64_t pbase = tile * 256 + prow + 4 * lh;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int64_t pix = pbase + (r & 3) + 8 * (r >> 2);
-        if (pix < total) {
-          y.data[pix * y.cstride + y.coff + l31] = acc[r];
-          if (cnt == 0) kk = acc[r];
-          const float d = acc[r] - kk;
-          s += d;
-          q += d * d;
-          ++cnt;
-        }
-      }
-    }
-  }
-  if (stats) {
-    const double k0 = kk, c0 = cnt;
-    double sd = (double)s + c0 * k0, qd = (double)q + 2.0 * k0 * (double)s + c0 * k0 * k0;
-    sd += __shfl_xor(sd, 32, 64);
-    qd += __shfl_xor(qd, 32, 64);
-    if (lh == 0) {
-      redd[wave][l31] = sd;
-      redd[wave][CO + l31] = qd;
-    }
-    __syncthreads();
-    if (tid < 2 * CO) {
-      double* st = stats + (size_t)(blockIdx.x % LHN_STAT_REPLICAS) * 2 * CO;
-      atomicAdd(st + tid, redd[0][tid] + redd[1][tid] + redd[2][tid] + redd[3][tid]);
-    }
-    if (fin.counter && lhn_last_block(fin.counter)) lhn_bn_finalize_block(fin, stats);
-  }
-}
-
-
-// ------------------------------------------------------------------ stem forward, 7x7 -> 64 features (hourglassnet.py:96) on MFMA
-// K = 147 taps padded to 160.  64-pixel tiles (42 KB of LDS: 3 blocks per CU); wave = (32-pixel group, 32-feature tile), its
-// weights are 80 MFMA B registers.  thread = (pixel, one of 4 tap groups) loads 37 taps; the next tile's are prefetched.
-// The direct kernel took 1.9 ms for this layer at batch 64 (147 x 8 scalar FMAs and 2 LDS reads per tap and thread).
-__global__ void __launch_bounds__(256, 2) k_stem7_fwd_mfma(const float* __restrict__ img, const float* __restrict__ w, lhn_view y,
-                                                        double* __restrict__ stats, int Hi, int Wi, int stride, int pad, lhn_bnfin fin) {
-  constexpr int CO = 64, T = 147, TP = 160, NKS = TP / 2, LDV = TP + 4, BMP = 64, G = 4, NR = 6, NV = NR * 7;      // thread = (pixel, tap-row group): rows (c, kh) g, g+4, .. of 21, 7 kw each
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* Vs = smem;                                   // [BMP][LDV], columns 147..159 stay zero
-  double* redd = reinterpret_cast<double*>(smem + BMP * LDV);      // [2 pixel groups][2 * CO]
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, lh = lane >> 5;
-  const int cot = wave & 1, pg = wave >> 1, co = cot * 32 + l31;
-  float wreg[NKS];                                    // step ks, lane (n = l31, k = lh): W[co][tap = NKS * lh + ks]
-#pragma unroll
-  for (int ks = 0; ks < NKS; ++ks) {
-    const int tap = NKS * lh + ks;
-    wreg[ks] = tap < T ? w[co * T + tap] : 0.f;
-  }
-  const int p = tid & (BMP - 1), g = tid >> 6;        // staging role: pixel of the tile, tap group
-  for (int t = T + g; t < TP; t += G) Vs[p * LDV + t] = 0.f;
-  const int64_t total = (int64_t)y.N * y.H * y.W;
-  const int64_t ntiles = (total + BMP - 1) / BMP;
-  float v[NV];
-  auto issue = [&](int64_t tile) __attribute__((always_inline)) {
-    const int64_t pix = tile * BMP + p;
-    const int64_t pc = pix < total ? pix : total - 1;
-    const int wo = (int)(pc % y.W);
-    const int64_t r = pc / y.W;
-    const int ho = (int)(r % y.H), n = (int)(r / y.H);
-    const float* base = img + (int64_t)n * 3 * Hi * Wi;
-    const int iw0 = wo * stride - pad;
-#pragma unroll
-    for (int jr = 0; jr < NR; ++jr) {
-      const int row = min(g + G * jr, 20), c = row / 7, kh = row - 7 * c;
-      const int ih = ho * stride - pad + kh, ihc = min(max(ih, 0), Hi - 1);
-      const float* rb = base + ((int64_t)c * Hi + ihc) * Wi;
-#pragma unroll
-      for (int kw = 0; kw < 7; ++kw) {
-        const int iw = iw0 + kw, iwc = min(max(iw, 0), Wi - 1);
-        const float q = rb[iwc];
-        v[jr * 7 + kw] = (ih == ihc && iw == iwc) ? q : 0.f;
-      }
-    }
-  };
-  float s = 0.f, q = 0.f, kk = 0.f;                   // this lane's feature: shifted sums (see TileStat)
-  int cnt = 0;
-  int64_t tile = blockIdx.x;
-  if (tile < ntiles) issue(tile);
-  for (; tile < ntiles; tile += gridDim.x) {
-    __syncthreads();
-#pragma unroll
-    for (int jr = 0; jr < NR; ++jr)
-      if (g + G * jr < 21)
-#pragma unroll
-        for (int kw = 0; kw < 7; ++kw) Vs[p * LDV + (g + G * jr) * 7 + kw] = v[jr * 7 + kw];
-    __syncthreads();
-    if (tile + gridDim.x < ntiles) issue(tile + gridDim.x);
-    const f4* ap = reinterpret_cast<const f4*>(Vs + (pg * 32 + l31) * LDV + NKS * lh);
-    f16v acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-    for (int c = 0; c < NKS / 4; ++c) {
-      if ((c & 3) == 0) asm volatile("" ::: "memory");      // at most 4 A fragments (16 registers) in flight: hoisted, all 20 spill
-      const f4 a = ap[c];
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, wreg[4 * c + 0], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, wreg[4 * c + 1], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, wreg[4 * c + 2], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, wreg[4 * c + 3], acc, 0, 0, 0);
-    }
-    const int64_t pbase = tile * BMP + pg * 32 + 4 * lh;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int64_t pix = pbase + (r & 3) + 8 * (r >> 2);
-      if (pix < total) {
-        y.data[pix * y.cstride + y.coff + co] = acc[r];
-        if (cnt == 0) kk = acc[r];
-        const float d = acc[r] - kk;
-        s += d;
-        q += d * d;
-        ++cnt;
-      }
-    }
-  }
-  if (stats) {
-    const double k0 = kk, c0 = cnt;
-    double sd = (double)s + c0 * k0, qd = (double)q + 2.0 * k0 * (double)s + c0 * k0 * k0;
-    sd += __shfl_xor(sd, 32, 64);
-    qd += __shfl_xor(qd, 32, 64);
-    __syncthreads();
-    if (lh == 0) {
-      redd[pg * 2 * CO + co] = sd;
-      redd[pg * 2 * CO + CO + co] = qd;
-    }
-    __syncthreads();
-    if (tid < 2 * CO) {
-      double* st = stats + (size_t)(blockIdx.x % LHN_STAT_REPLICAS) * 2 * CO;
-      atomicAdd(st + tid, redd[tid] + redd[2 * CO + tid]);
-    }
-    if (fin.counter && lhn_last_block(fin.counter)) lhn_bn_finalize_block(fin, stats);
-  }
-}
-
-static inline int grid_for(int64_t items_per_block_total, int per_block, int cap_per_cu) {
-  int64_t g = (items_per_block_total + per_block - 1) / per_block;
-  const int64_t cap = (int64_t)lhn_num_cus() * cap_per_cu;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-static inline bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
-
 // One extra input source: the consumed input is coef[0]*value(x) + coef[1]*value(ex.v) (MSRB's `out + ca(cat)`,
 // litehourglass.py:41-45, summed while the halo tile is staged instead of being written by an elementwise pass).
 struct DwExtra {
@@ -406,135 +119,8 @@ struct DwExtra {
   int so_cstride, so_coff;
 };
 
-int lhn_dwk_fwd_lds(const lhn_view* x, const float* w, const lhn_view* y, double* stats, int k, int dil, lhn_bnfin fin,
-                    hipStream_t s, const DwExtra* ex);
-struct DwBnSum;
-static int dws2_fwd(const lhn_view* x, const float* w, const lhn_view* y, double* stats, lhn_bnfin fin, hipStream_t s);
-static int dws2_bwd(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc, float* dw,
-                    int nrep, int64_t rep_stride, hipStream_t s);
-int lhn_dwk_bwd_lds(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc,
-                    float* dw, int k, int dil, int nrep, int64_t rep_stride, hipStream_t s, const DwBnSum* bs,
-                    const lhn_bnbwdsrc* fs = nullptr);
-static bool lhn_dw_bwd_v1();
-static bool lhn_dw_force_gather() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("LHN_DW_GATHER");
-    v = (e && e[0] == '1') ? 1 : 0;
-  }
-  return v == 1;
-}
-
-static int dw_fwd_extra(const lhn_view* x, const float* w, const lhn_view* y, double* stats, int k, int stride, int pad, int dil,
-                        lhn_bnfin fin, const lhn_view* extra, const float* coef, const lhn_view* so, hipStream_t s);
-
-extern "C" int lhn_conv_dw_fwd3(const lhn_view* x, const float* w, const lhn_view* y, double* stats, int k, int stride,
-                                int pad, int dil, const lhn_bnfin* finp, const lhn_view* extra, const float* coef2,
-                                const lhn_view* sum_out, void* stream) {
-  if (!extra) {
-    LHN_CHECK_ARG(!sum_out, "lhn_conv_dw_fwd3: sum_out without a second source");
-    return lhn_conv_dw_fwd(x, w, y, stats, k, stride, pad, dil, finp, stream);
-  }
-  lhn_bnfin fin;
-  if (finp && stats) fin = *finp; else fin.counter = nullptr;
-  LHN_CHECK_ARG(lhn_view_ok(x) && lhn_view_ok(y) && lhn_view_ok(extra) && w && coef2, "lhn_conv_dw_fwd2: bad view / null pointer");
-  LHN_CHECK_ARG(extra->C == x->C && extra->N == x->N && extra->H == x->H && extra->W == x->W, "lhn_conv_dw_fwd2: extra source geometry");
-  LHN_CHECK_ARG(x->C == y->C && y->N == x->N && y->H == x->H && y->W == x->W, "lhn_conv_dw_fwd2: same-size output");
-  LHN_CHECK_ARG(!sum_out || (sum_out->data && sum_out->C == x->C && sum_out->N == x->N && sum_out->H == x->H && sum_out->W == x->W &&
-                             sum_out->cstride % 4 == 0 && sum_out->coff % 4 == 0 && sum_out->coff + sum_out->C <= sum_out->cstride),
-                "lhn_conv_dw_fwd3: sum_out geometry (same pixels and channels as x)");
-  const int rc = dw_fwd_extra(x, w, y, stats, k, stride, pad, dil, fin, extra, coef2, sum_out, (hipStream_t)stream);
-  LHN_CHECK_ARG(rc == 1, "lhn_conv_dw_fwd2: a second source needs k=3, stride 1, 'same' padding, W >= 8 (got k=%d s=%d C=%d W=%d)",
-                k, stride, x->C, y->W);
-  LHN_CHECK_LAUNCH("lhn_conv_dw_fwd2");
-  return 0;
-}
-
-extern "C" int lhn_conv_dw_fwd2(const lhn_view* x, const float* w, const lhn_view* y, double* stats, int k, int stride,
-                                int pad, int dil, const lhn_bnfin* finp, const lhn_view* extra, const float* coef2, void* stream) {
-  return lhn_conv_dw_fwd3(x, w, y, stats, k, stride, pad, dil, finp, extra, coef2, nullptr, stream);
-}
-
-extern "C" int lhn_conv_dw_fwd(const lhn_view* x, const float* w, const lhn_view* y, double* stats, int k, int stride,
-                               int pad, int dil, const lhn_bnfin* finp, void* stream) {
-  lhn_bnfin fin;
-  if (finp && stats) fin = *finp; else fin.counter = nullptr;
-  LHN_CHECK_ARG(lhn_view_ok(x) && lhn_view_ok(y) && (w || k == 1), "lhn_conv_dw_fwd: bad view / null pointer (w may be NULL = ones only for k=1)");
-  LHN_CHECK_ARG(x->C == y->C && x->C % 4 == 0 && x->C <= 512, "lhn_conv_dw_fwd: channels %d -> %d (multiple of 4, <= 512)", x->C, y->C);
-  LHN_CHECK_ARG((k == 1 || k == 3 || k == 5 || k == 7) && stride >= 1 && dil >= 1 && pad >= 0, "lhn_conv_dw_fwd: k=%d stride=%d dil=%d", k, stride, dil);
-  const int Ho = (x->H + 2 * pad - dil * (k - 1) - 1) / stride + 1, Wo = (x->W + 2 * pad - dil * (k - 1) - 1) / stride + 1;
-  LHN_CHECK_ARG(y->N == x->N && y->H == Ho && y->W == Wo, "lhn_conv_dw_fwd: output %dx%d, expected %dx%d", y->H, y->W, Ho, Wo);
-  const size_t lds = (size_t)(k * k * x->C) * 4 + 256 * 2 * 16;
-  const int grid = grid_for((int64_t)y->N * Ho, 1, 8);
-  hipStream_t s = (hipStream_t)stream;
-  LHN_CHECK_ARG(lhn_no_pend(x), "lhn_conv_dw_fwd: lhn_view.pend is reserved (NULL)");
-  const int px = 0;
-  DwExtra ex0;
-  ex0.n = 0;
-  ex0.sum_out = nullptr;
-  if (w && stride == 1 && pad == dil * (k - 1) / 2 && x->C % 4 == 0 && y->W >= 8 && !lhn_dw_force_gather() &&
-      lhn_dwk_fwd_lds(x, w, y, stats, k, dil, fin, s, &ex0)) {
-  } else if (w && k == 3 && stride == 2 && pad == 1 && dil == 1 && x->C % 4 == 0 && !lhn_dw_force_gather() &&
-             dws2_fwd(x, w, y, stats, fin, s)) {
-  } else if (k == 3)
-    hipLaunchKernelGGL((k_dw_fwd<3>), dim3(grid), dim3(256), lds, s, *x, w, *y, stats, stride, pad, dil, fin, px);
-  else if (k == 7)
-    hipLaunchKernelGGL((k_dw_fwd<7>), dim3(grid), dim3(256), lds, s, *x, w, *y, stats, stride, pad, dil, fin, px);
-  else if (k == 1)
-    hipLaunchKernelGGL((k_dw_fwd<1>), dim3(grid), dim3(256), lds, s, *x, w, *y, stats, stride, pad, dil, fin, px);
-  else if (k == 5)
-    hipLaunchKernelGGL((k_dw_fwd<5>), dim3(grid), dim3(256), lds, s, *x, w, *y, stats, stride, pad, dil, fin, px);
-  LHN_CHECK_LAUNCH("lhn_conv_dw_fwd");
-  return 0;
-}
-
-extern "C" int lhn_conv_stem_fwd(const float* img, const float* w, const lhn_view* y, double* stats, int Hi, int Wi, int k,
-                                 int stride, int pad, const lhn_bnfin* finp, void* stream) {
-  lhn_bnfin fin;
-  if (finp && stats) fin = *finp; else fin.counter = nullptr;
-  LHN_CHECK_ARG(img && w && lhn_view_ok(y), "lhn_conv_stem_fwd: bad view / null pointer");
-  LHN_CHECK_ARG(y->C % 8 == 0 && pow2(y->C / 8) && y->C <= 256, "lhn_conv_stem_fwd: Cout=%d", y->C);
-  LHN_CHECK_ARG((k == 1 || k == 3 || k == 5 || k == 7) && stride >= 1, "lhn_conv_stem_fwd: k=%d", k);
-  const int Ho = (Hi + 2 * pad - k) / stride + 1, Wo = (Wi + 2 * pad - k) / stride + 1;
-  LHN_CHECK_ARG(y->H == Ho && y->W == Wo, "lhn_conv_stem_fwd: output %dx%d, expected %dx%d", y->H, y->W, Ho, Wo);
-  const int PL = 256 / (y->C / 8);
-  const size_t lds = (size_t)(3 * k * k * y->C) * 4 + 256 * 16 * 4;
-  const bool mfma = !lhn_dw_force_gather() && ((k == 7 && y->C == 64) || (k == 3 && y->C == 32));
-  // the direct kernel is launched without a dynamic-LDS opt-in: 64 KiB is what a launch may ask for unprepared
-  LHN_CHECK_ARG(mfma || lds <= 65536, "lhn_conv_stem_fwd: k=%d Cout=%d needs %zu B of LDS (limit 65536 B)", k, y->C, lds);
-  if (k == 7 && y->C == 64 && !lhn_dw_force_gather()) {
-    const size_t lds7 = (size_t)64 * 164 * 4 + 2 * 2 * 64 * 8;
-    static LhnKernelCfg cfg7;
-    int per_cu = 1;
-    if (!lhn_kernel_cfg(cfg7, &k_stem7_fwd_mfma, lds7, 3, &per_cu)) {
-      lhn_set_error("lhn_conv_stem_fwd: cannot reserve %zu B of LDS", lds7);
-      return 2;
-    }
-    const int64_t ntiles = ((int64_t)y->N * Ho * Wo + 63) / 64;
-    int grid = lhn_num_cus() * per_cu;
-    if (grid > ntiles) grid = (int)ntiles;
-    hipLaunchKernelGGL(k_stem7_fwd_mfma, dim3(grid), dim3(256), lds7, (hipStream_t)stream, img, w, *y, stats, Hi, Wi, stride, pad, fin);
-  } else if (k == 3 && y->C == 32 && !lhn_dw_force_gather()) {
-    // (3 / 6 / 12 blocks per CU measured in round 3: no difference, forward 2.680 / 2.677 / 2.682 ms)
-    hipLaunchKernelGGL(k_stem3_fwd_mfma, dim3(grid_for((int64_t)y->N * Ho * Wo, 256, 3)), dim3(256), 0, (hipStream_t)stream, img, w, *y,
-                       stats, Hi, Wi, stride, pad, fin);
-  } else
-    hipLaunchKernelGGL(k_stem_fwd, dim3(grid_for((int64_t)y->N * Ho * Wo, PL, 8)), dim3(256), lds, (hipStream_t)stream, img,
-                       w, *y, stats, Hi, Wi, k, stride, pad, fin);
-  LHN_CHECK_LAUNCH("lhn_conv_stem_fwd");
-  return 0;
-}
-
 // =====================================================================================================
 // Backward.  dy is formed on the fly:  du = lrelu'(u) * (gate*dz + pooled-gradient),  dy = A*du + B*y + C.
-__device__ __forceinline__ f4 dw_load_dy(const lhn_view& y, const lhn_gradview& g, const Xf4& xf, const Gr4& gr,
-                                         int64_t pix, int n, int h, int w, int ca) {
-  const f4 raw = *reinterpret_cast<const f4*>(y.data + pix * y.cstride + ca);
-  const f4 dz = *reinterpret_cast<const f4*>(g.dz + pix * y.cstride + ca);
-  const f4 du = lhn_grad_du(y, g, xf, raw, dz, n, h, w, ca);
-  return gr.A * du + gr.B * raw + gr.Cc;
-}
-
 // row-local dy loader: off = element offset of (n, h, w, channel ca) inside the y buffer
 __device__ __forceinline__ f4 dw_dy_at(const lhn_view& y, const lhn_gradview& g, const Xf4& xf, const Gr4& gr, f4 gate,
                                        size_t off, int n, int h, int w, int ca) {
@@ -660,428 +246,6 @@ __global__ void __launch_bounds__(256) k_dw_bwd_weight(lhn_view x, lhn_view y, l
       atomicAdd(dw + (4 * tid + 3) * K * K + tap, s.w);
     }
   }
-}
-
-// stem wgrad: thread = (pixel lane, 4 output channels); T = 3*KR*K accumulators of float4 for the kernel rows
-// [kh0, kh0 + KR) (K = 7, hourglassnet.py:100, runs one kernel row per launch: 147 float4 accumulators do not fit)
-template <int K, int KR>
-__global__ void __launch_bounds__(256) k_stem_bwd(const float* __restrict__ img, lhn_view y, lhn_gradview gy,
-                                                  float* __restrict__ dw, int Hi, int Wi, int stride, int pad, int nrep,
-                                                  int64_t rep_stride, int kh0) {
-  dw += (size_t)(blockIdx.x % nrep) * rep_stride;
-  constexpr int T = 3 * KR * K;
-  __shared__ f4 red[256];
-  const int C4 = y.C >> 2;
-  const int tid = threadIdx.x, c4 = tid % C4, pl = tid / C4, PL = 256 / C4;
-  const int cy = y.coff + 4 * c4;
-  const Xf4 yxf = lhn_load_xf(y, cy);
-  const Gr4 ygr = lhn_load_coef(gy, y.cstride, cy);
-  f4 acc[T];
-#pragma unroll
-  for (int i = 0; i < T; ++i) acc[i] = (f4){0.f, 0.f, 0.f, 0.f};
-  const int64_t total = (int64_t)y.N * y.H * y.W;
-  for (int64_t pix = (int64_t)blockIdx.x * PL + pl; pix < total; pix += (int64_t)gridDim.x * PL) {
-    const int wo = (int)(pix % y.W);
-    const int64_t t = pix / y.W;
-    const int ho = (int)(t % y.H), n = (int)(t / y.H);
-    const f4 dy = dw_load_dy(y, gy, yxf, ygr, pix, n, ho, wo, cy);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float* plane = img + ((int64_t)n * 3 + c) * Hi * Wi;
-#pragma unroll
-      for (int r = 0; r < KR; ++r) {
-        const int ih = ho * stride - pad + kh0 + r;
-#pragma unroll
-        for (int kw = 0; kw < K; ++kw) {
-          const int iw = wo * stride - pad + kw;
-          float v = 0.f;
-          if (ih >= 0 && ih < Hi && iw >= 0 && iw < Wi) v = plane[(int64_t)ih * Wi + iw];
-          acc[(c * KR + r) * K + kw] += dy * v;
-        }
-      }
-    }
-  }
-  constexpr int TW = 3 * K * K;            // weights per output channel
-#pragma unroll
-  for (int i = 0; i < T; ++i) {
-    __syncthreads();
-    red[tid] = acc[i];
-    __syncthreads();
-    if (tid < C4) {
-      f4 s = (f4){0.f, 0.f, 0.f, 0.f};
-      for (int j = 0; j < PL; ++j) s += red[j * C4 + tid];
-      const int c = i / (KR * K), r = (i / K) % KR, kw = i % K, e = c * K * K + (kh0 + r) * K + kw;
-      atomicAdd(dw + (4 * tid + 0) * TW + e, s.x);
-      atomicAdd(dw + (4 * tid + 1) * TW + e, s.y);
-      atomicAdd(dw + (4 * tid + 2) * TW + e, s.z);
-      atomicAdd(dw + (4 * tid + 3) * TW + e, s.w);
-    }
-  }
-}
-
-
-// ------------------------------------------------------------------ stem weight gradient, 3x3 -> 32 features, on MFMA:
-// dW[co][tap] = sum_pixels dy[pixel][co] * patch[pixel][tap] is a (32 x 27) = dY^T (32 x P) * V (P x 27) GEMM with the
-// pixels as K.  Per 256-pixel tile the block parks dy (formed on the fly from dz, raw y and the BatchNorm-backward
-// coefficients) and the im2col patch (27 taps, padded to 32 zero columns) in LDS; every wave then runs 32
-// v_mfma_f32_32x32x2_f32 over its 64 pixels into one 32x32 accumulator that lives across the whole launch.
-__global__ void __launch_bounds__(256) k_stem3_bwd_mfma(const float* __restrict__ img, lhn_view y, lhn_gradview gy, float* __restrict__ dw,
-                                                        int Hi, int Wi, int stride, int pad, int nrep, int64_t rep_stride) {
-  constexpr int CO = 32, LDY = CO + 4, LDV = 33;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* dYs = smem;                     // [256][LDY] pixel-major dy; reused for the final cross-wave sum (4096 floats)
-  float* Vs = smem + 256 * LDY;          // [256][LDV] pixel-major patch, columns 27..31 stay zero
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, lh = lane >> 5;
-  const int c4 = tid & 7, prow = tid >> 3;
-  const int cy = y.coff + 4 * c4;
-  const Xf4 yxf = lhn_load_xf(y, cy);
-  const Gr4 ygr = lhn_load_coef(gy, y.cstride, cy);
-  for (int t = 27; t < 32; ++t) Vs[tid * LDV + t] = 0.f;
-  f16v acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  const int64_t total = (int64_t)y.N * y.H * y.W;
-  const int64_t ntiles = (total + 255) / 256;
-  // raw loads of a tile go into registers one tile AHEAD (dy is formed when they are parked in LDS)
-  f4 yraw[8], zraw[8];
-  float v[27];
-  auto issue = [&](int64_t tile) __attribute__((always_inline)) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      int64_t pix = tile * 256 + prow + 32 * j;
-      pix = pix < total ? pix : total - 1;
-      yraw[j] = *reinterpret_cast<const f4*>(y.data + pix * y.cstride + cy);
-      zraw[j] = *reinterpret_cast<const f4*>(gy.dz + pix * y.cstride + cy);
-    }
-    const int64_t pix = tile * 256 + tid;
-    const int64_t pc = pix < total ? pix : total - 1;
-    const int wo = (int)(pc % y.W);
-    const int64_t r = pc / y.W;
-    const int ho = (int)(r % y.H), n = (int)(r / y.H);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float* plane = img + ((int64_t)n * 3 + c) * Hi * Wi;
-#pragma unroll
-      for (int kh = 0; kh < 3; ++kh) {
-        const int ih = ho * stride - pad + kh, ihc = min(max(ih, 0), Hi - 1);
-#pragma unroll
-        for (int kw = 0; kw < 3; ++kw) {
-          const int iw = wo * stride - pad + kw, iwc = min(max(iw, 0), Wi - 1);
-          const float t = plane[(int64_t)ihc * Wi + iwc];
-          v[c * 9 + kh * 3 + kw] = (ih == ihc && iw == iwc) ? t : 0.f;      // (rows past the end meet dy = 0)
-        }
-      }
-    }
-  };
-  int64_t tile = blockIdx.x;
-  if (tile < ntiles) issue(tile);
-  for (; tile < ntiles; tile += gridDim.x) {
-    __syncthreads();                       // the previous tile's MFMA reads are done
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int p = prow + 32 * j;
-      const int64_t pix = tile * 256 + p;
-      f4 d = (f4){0.f, 0.f, 0.f, 0.f};
-      if (pix < total) {
-        const int wo = (int)(pix % y.W);
-        const int64_t r = pix / y.W;
-        const f4 du = lhn_grad_du(y, gy, yxf, yraw[j], zraw[j], (int)(r / y.H), (int)(r % y.H), wo, cy);
-        d = ygr.A * du + ygr.B * yraw[j] + ygr.Cc;
-      }
-      *reinterpret_cast<f4*>(dYs + p * LDY + 4 * c4) = d;
-    }
-#pragma unroll
-    for (int t = 0; t < 27; ++t) Vs[tid * LDV + t] = v[t];
-    __syncthreads();
-    if (tile + gridDim.x < ntiles) issue(tile + gridDim.x);
-    const float* ar = dYs + (wave * 64 + lh) * LDY + l31;
-    const float* br = Vs + (wave * 64 + lh) * LDV + l31;
-#pragma unroll 8
-    for (int ks = 0; ks < 32; ++ks) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ar[2 * ks * LDY], br[2 * ks * LDV], acc, 0, 0, 0);
-  }
-  // cross-wave sum through LDS, then one float atomic per weight into this block's gradient replica
-  __syncthreads();
-  float* part = dYs;                                 // [4][16][64]
-#pragma unroll
-  for (int r = 0; r < 16; ++r) part[(wave * 16 + r) * 64 + lane] = acc[r];
-  __syncthreads();
-  dw += (size_t)(blockIdx.x % nrep) * rep_stride;
-  for (int i = tid; i < CO * 27; i += 256) {
-    const int co = i / 27, t = i - co * 27;
-    const int r = (co & 3) + 4 * (co >> 3), ln = t + 32 * ((co >> 2) & 1);      // accumulator row co = (r & 3) + 8 (r >> 2) + 4 lh
-    const float v = part[(0 * 16 + r) * 64 + ln] + part[(1 * 16 + r) * 64 + ln] + part[(2 * 16 + r) * 64 + ln] + part[(3 * 16 + r) * 64 + ln];
-    atomicAdd(dw + i, v);
-  }
-}
-
-
-// ------------------------------------------------------------------ stem weight gradient, 7x7 -> 64 features, on MFMA:
-// dW (64 x 147) = dY^T (64 x P) * patch (P x 147): 2 feature tiles x 5 tap tiles of 32 x 32 over the four waves (3, 3, 2, 2),
-// K = the 64 pixels of a tile.  Staging as in k_stem7_fwd_mfma (row-wise taps) + k_stem3_bwd_mfma (dy formed at commit).
-__global__ void __launch_bounds__(256, 2) k_stem7_bwd_mfma(const float* __restrict__ img, lhn_view y, lhn_gradview gy, float* __restrict__ dw,
-                                                           int Hi, int Wi, int stride, int pad, int nrep, int64_t rep_stride) {
-  constexpr int CO = 64, T = 147, LDY = CO + 4, LDV = 161, BMP = 64, G = 4, NR = 6;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* dYs = smem;                     // [BMP][LDY]
-  float* Vs = smem + BMP * LDY;          // [BMP][LDV], columns 147..159 stay zero
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, lh = lane >> 5;
-  const int c4 = tid & 15, prow = tid >> 4;
-  const int cy = y.coff + 4 * c4;
-  const Xf4 yxf = lhn_load_xf(y, cy);
-  const Gr4 ygr = lhn_load_coef(gy, y.cstride, cy);
-  const int p = tid & (BMP - 1), g = tid >> 6;
-  for (int t = T + g; t < 160; t += G) Vs[p * LDV + t] = 0.f;
-  f16v acc[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-  const int64_t total = (int64_t)y.N * y.H * y.W;
-  const int64_t ntiles = (total + BMP - 1) / BMP;
-  f4 yraw[4], zraw[4];
-  float v[NR * 7];
-  auto issue = [&](int64_t tile) __attribute__((always_inline)) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      int64_t pix = tile * BMP + prow + 16 * j;
-      pix = pix < total ? pix : total - 1;
-      yraw[j] = *reinterpret_cast<const f4*>(y.data + pix * y.cstride + cy);
-      zraw[j] = *reinterpret_cast<const f4*>(gy.dz + pix * y.cstride + cy);
-    }
-    const int64_t pix = tile * BMP + p;
-    const int64_t pc = pix < total ? pix : total - 1;
-    const int wo = (int)(pc % y.W);
-    const int64_t r = pc / y.W;
-    const int ho = (int)(r % y.H), n = (int)(r / y.H);
-    const float* base = img + (int64_t)n * 3 * Hi * Wi;
-    const int iw0 = wo * stride - pad;
-#pragma unroll
-    for (int jr = 0; jr < NR; ++jr) {
-      const int row = min(g + G * jr, 20), c = row / 7, kh = row - 7 * c;
-      const int ih = ho * stride - pad + kh, ihc = min(max(ih, 0), Hi - 1);
-      const float* rb = base + ((int64_t)c * Hi + ihc) * Wi;
-#pragma unroll
-      for (int kw = 0; kw < 7; ++kw) {
-        const int iw = iw0 + kw, iwc = min(max(iw, 0), Wi - 1);
-        const float q = rb[iwc];
-        v[jr * 7 + kw] = (ih == ihc && iw == iwc) ? q : 0.f;
-      }
-    }
-  };
-  int64_t tile = blockIdx.x;
-  if (tile < ntiles) issue(tile);
-  for (; tile < ntiles; tile += gridDim.x) {
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int pp = prow + 16 * j;
-      const int64_t pix = tile * BMP + pp;
-      f4 d = (f4){0.f, 0.f, 0.f, 0.f};
-      if (pix < total) {
-        const int wo = (int)(pix % y.W);
-        const int64_t r = pix / y.W;
-        const f4 du = lhn_grad_du(y, gy, yxf, yraw[j], zraw[j], (int)(r / y.H), (int)(r % y.H), wo, cy);
-        d = ygr.A * du + ygr.B * yraw[j] + ygr.Cc;
-      }
-      *reinterpret_cast<f4*>(dYs + pp * LDY + 4 * c4) = d;
-    }
-#pragma unroll
-    for (int jr = 0; jr < NR; ++jr)
-      if (g + G * jr < 21)
-#pragma unroll
-        for (int kw = 0; kw < 7; ++kw) Vs[p * LDV + (g + G * jr) * 7 + kw] = v[jr * 7 + kw];
-    __syncthreads();
-    if (tile + gridDim.x < ntiles) issue(tile + gridDim.x);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const int job = wave + 4 * i;                  // 10 jobs: feature tile = job & 1, tap tile = job >> 1
-      if (job < 10) {
-        const float* ar = dYs + lh * LDY + (job & 1) * 32 + l31;
-        const float* br = Vs + lh * LDV + (job >> 1) * 32 + l31;
-#pragma unroll 8
-        for (int ks = 0; ks < 32; ++ks) acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(ar[2 * ks * LDY], br[2 * ks * LDV], acc[i], 0, 0, 0);
-      }
-    }
-  }
-  dw += (size_t)(blockIdx.x % nrep) * rep_stride;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const int job = wave + 4 * i;
-    if (job < 10) {
-      const int t = (job >> 1) * 32 + l31;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int co = (job & 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (t < T) atomicAdd(dw + co * T + t, acc[i][r]);
-      }
-    }
-  }
-}
-
-static int dw_bwd_fused(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, float* dw, int k,
-                        int dil, int nrep, int64_t rep_stride, double* bn_sums, const float* bn_save, int bn_C, int bn_coff, hipStream_t s);
-
-extern "C" int lhn_conv_dw_bwd2(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
-                                int dx_accumulate, float* dw, int k, int stride, int pad, int dil, int nrep, int64_t rep_stride,
-                                double* bn_sums, const float* bn_save, int bn_C, int bn_coff, void* stream) {
-  if (!bn_sums) return lhn_conv_dw_bwd(x, w, y, gy, dx, dx_accumulate, dw, k, stride, pad, dil, nrep, rep_stride, stream);
-  if (nrep < 1) nrep = 1;
-  LHN_CHECK_ARG(lhn_view_ok(x) && lhn_view_ok(y) && gy && gy->dz && w && dw && dx && bn_save && lhn_no_pend(x) && lhn_no_pend(y),
-                "lhn_conv_dw_bwd2: bad view / null pointer");
-  LHN_CHECK_ARG(!dx_accumulate && !x->gate && stride == 1 && pad == dil * (k - 1) / 2 && x->C % 32 == 0 && x->W >= 8 && x->C == y->C &&
-                    bn_coff >= 0 && bn_coff + x->C <= bn_C,
-                "lhn_conv_dw_bwd2: fused BatchNorm sums need this convolution to be the only, ungated, stride-1 reader of x (dx stored)");
-  const int rc = dw_bwd_fused(x, w, y, gy, dx, dw, k, dil, nrep, rep_stride, bn_sums, bn_save, bn_C, bn_coff, (hipStream_t)stream);
-  LHN_CHECK_ARG(rc == 1, "lhn_conv_dw_bwd2: fused BatchNorm sums are built for the 3x3 / dilation 1 kernel (k=%d dil=%d)", k, dil);
-  LHN_CHECK_LAUNCH("lhn_conv_dw_bwd2");
-  return 0;
-}
-
-static int dw_bwd_addends(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc, float* dw,
-                          int k, int dil, int nrep, int64_t rep_stride, const float* a0, const float* a1, hipStream_t s);
-
-extern "C" int lhn_conv_dw_bwd3(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
-                                int dx_accumulate, float* dw, int k, int stride, int pad, int dil, int nrep, int64_t rep_stride,
-                                const float* dx_add0, const float* dx_add1, void* stream) {
-  if (!dx_add0 && !dx_add1) return lhn_conv_dw_bwd(x, w, y, gy, dx, dx_accumulate, dw, k, stride, pad, dil, nrep, rep_stride, stream);
-  if (nrep < 1) nrep = 1;
-  LHN_CHECK_ARG(lhn_view_ok(x) && lhn_view_ok(y) && gy && gy->dz && w && dw && dx && lhn_no_pend(x) && lhn_no_pend(y),
-                "lhn_conv_dw_bwd3: bad view / null pointer");
-  LHN_CHECK_ARG(stride == 1 && pad == dil * (k - 1) / 2 && x->C % 4 == 0 && x->W >= 8 && x->C == y->C,
-                "lhn_conv_dw_bwd3: gradient addends need the tiled stride-1 kernel (W >= 8)");
-  const int rc = dw_bwd_addends(x, w, y, gy, dx, dx_accumulate, dw, k, dil, nrep, rep_stride, dx_add0 ? dx_add0 : dx_add1,
-                                dx_add0 ? dx_add1 : nullptr, (hipStream_t)stream);
-  LHN_CHECK_ARG(rc == 1, "lhn_conv_dw_bwd3: no tiled kernel for k=%d dil=%d", k, dil);
-  LHN_CHECK_LAUNCH("lhn_conv_dw_bwd3");
-  return 0;
-}
-
-extern "C" int lhn_conv_dw_bwd(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
-                               int dx_accumulate, float* dw, int k, int stride, int pad, int dil, int nrep, int64_t rep_stride,
-                               void* stream) {
-  if (nrep < 1) nrep = 1;
-  LHN_CHECK_ARG(lhn_view_ok(x) && lhn_view_ok(y) && gy && gy->dz && ((w && dw) || k == 1) && lhn_no_pend(x) && lhn_no_pend(y), "lhn_conv_dw_bwd: bad view / null pointer");
-  LHN_CHECK_ARG(x->C == y->C && x->C % 4 == 0 && x->C <= 512, "lhn_conv_dw_bwd: channels");
-  LHN_CHECK_ARG(k == 1 || k == 3 || k == 7, "lhn_conv_dw_bwd: k=%d (1, 3 or 7)", k);
-  hipStream_t s = (hipStream_t)stream;
-  if (w && dw && stride == 1 && pad == dil * (k - 1) / 2 && x->C % 4 == 0 && x->W >= 8 && !lhn_dw_force_gather() &&
-      lhn_dwk_bwd_lds(x, w, y, gy, dx, dx_accumulate, dw, k, dil, nrep, rep_stride, s, nullptr)) {
-    LHN_CHECK_LAUNCH("lhn_conv_dw_bwd");
-    return 0;
-  }
-  if (w && dw && k == 3 && stride == 2 && pad == 1 && dil == 1 && x->C % 4 == 0 && !lhn_dw_force_gather() &&
-      dws2_bwd(x, w, y, gy, dx, dx_accumulate, dw, nrep, rep_stride, s)) {
-    LHN_CHECK_LAUNCH("lhn_conv_dw_bwd");
-    return 0;
-  }
-  if (dx) {
-    const size_t lds = (size_t)(k * k * x->C) * 4;
-    const int g = grid_for((int64_t)x->N * x->H, 1, 8);
-    if (k == 3)
-      hipLaunchKernelGGL((k_dw_bwd_data<3>), dim3(g), dim3(256), lds, s, *x, w, *y, *gy, dx, dx_accumulate, stride, pad, dil);
-    else if (k == 1)
-      hipLaunchKernelGGL((k_dw_bwd_data<1>), dim3(g), dim3(256), lds, s, *x, w, *y, *gy, dx, dx_accumulate, stride, pad, dil);
-    else
-      hipLaunchKernelGGL((k_dw_bwd_data<7>), dim3(g), dim3(256), lds, s, *x, w, *y, *gy, dx, dx_accumulate, stride, pad, dil);
-  }
-  const int gw = grid_for((int64_t)y->N * y->H, 1, 4);
-  if (!dw) {
-    // identity depthwise (no weight to learn)
-  } else if (k == 1) {
-    hipLaunchKernelGGL((k_dw_bwd_weight<1, 1>), dim3(gw), dim3(256), 0, s, *x, *y, *gy, dw, stride, pad, dil, 0, nrep, rep_stride);
-  } else if (k == 3) {
-    hipLaunchKernelGGL((k_dw_bwd_weight<3, 3>), dim3(gw), dim3(256), 0, s, *x, *y, *gy, dw, stride, pad, dil, 0, nrep, rep_stride);
-  } else {
-    for (int kh = 0; kh < 7; ++kh)
-      hipLaunchKernelGGL((k_dw_bwd_weight<7, 1>), dim3(gw), dim3(256), 0, s, *x, *y, *gy, dw, stride, pad, dil, kh, nrep, rep_stride);
-  }
-  LHN_CHECK_LAUNCH("lhn_conv_dw_bwd");
-  return 0;
-}
-
-static int dw_bwd_fin(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc, float* dw, int k,
-                      int dil, int nrep, int64_t rep_stride, const lhn_bnsum* bns, const float* a0, const float* a1, const lhn_bnbwdsrc* fin,
-                      hipStream_t s);
-// the shapes lhn_conv_dw_bwd / _bwd2 / _bwd3 hand to k_dw3_bwd_rows or, on small maps, to the FOLD instances of k_dwk_bwd_lds: both
-// fold the finalize in their prologue (lhn_dwk_bwd_lds decides between them)  (has_ext: sums or addends, which ignore LHN_DW_GATHER)
-static bool dw_bwd_folds(const lhn_view* x, const float* w, const float* dw, int k, int stride, int pad, int dil, bool has_ext) {
-  return w && dw && k == 3 && stride == 1 && (dil == 1 || dil == 2) && pad == dil && x->C % 4 == 0 && x->W >= 8 && !lhn_dw_bwd_v1() &&
-         (has_ext || !lhn_dw_force_gather());
-}
-extern "C" int lhn_conv_dw_bwd4(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
-                                int dx_accumulate, float* dw, int k, int stride, int pad, int dil, int nrep, int64_t rep_stride,
-                                const lhn_bnsum* bns, const float* dx_add0, const float* dx_add1, const lhn_bnbwdsrc* fin,
-                                void* stream) {
-  const bool has_bns = bns && bns->sums, has_add = dx_add0 || dx_add1;
-  LHN_CHECK_ARG(!(has_bns && has_add), "lhn_conv_dw_bwd4: producer sums and gradient addends exclude each other");
-  const bool folds = fin && fin->sums;
-  if (folds) {
-    LHN_CHECK_ARG(lhn_view_ok(x) && lhn_view_ok(y) && gy && gy->dz && gy->coef && fin->save_mean_invstd && fin->count > 0 &&
-                      fin->stat_channels >= y->C && x->C == y->C && lhn_no_pend(x) && lhn_no_pend(y),
-                  "lhn_conv_dw_bwd4: finalize source needs gy->coef, saved statistics and stat_channels >= C");
-    if (!dw_bwd_folds(x, w, dw, k, stride, pad, dil, has_bns || has_add)) {      // another kernel: the separate finalize launch, then as ever
-      const int rc = lhn_bn_bwd_finalize2(fin->sums, fin->gamma, fin->save_mean_invstd, const_cast<float*>(gy->coef), y->cstride, y->coff,
-                                          y->C, fin->stat_channels, fin->count, fin->dgamma, fin->dbeta, fin->pgrad_scale, stream);
-      if (rc) return rc;
-    }
-  }
-  if (!folds || !dw_bwd_folds(x, w, dw, k, stride, pad, dil, has_bns || has_add)) {
-    if (has_add) return lhn_conv_dw_bwd3(x, w, y, gy, dx, dx_accumulate, dw, k, stride, pad, dil, nrep, rep_stride, dx_add0, dx_add1, stream);
-    return lhn_conv_dw_bwd2(x, w, y, gy, dx, dx_accumulate, dw, k, stride, pad, dil, nrep, rep_stride, has_bns ? bns->sums : nullptr,
-                            has_bns ? bns->save : nullptr, has_bns ? bns->C : 0, has_bns ? bns->coff : 0, stream);
-  }
-  if (nrep < 1) nrep = 1;
-  LHN_CHECK_ARG(x->C <= 512 && (!has_add || dx), "lhn_conv_dw_bwd4: channels / addends without dx");
-  if (has_bns)      // the conditions of lhn_conv_dw_bwd2
-    LHN_CHECK_ARG(dx && bns->save && !dx_accumulate && !x->gate && dil == 1 && x->C % 32 == 0 && bns->coff >= 0 && bns->coff + x->C <= bns->C,
-                  "lhn_conv_dw_bwd4: fused BatchNorm sums need this convolution to be the only, ungated, stride-1 reader of x (dx stored, dilation 1)");
-  const int rc = dw_bwd_fin(x, w, y, gy, dx, dx_accumulate, dw, k, dil, nrep, rep_stride, has_bns ? bns : nullptr, dx_add0 ? dx_add0 : dx_add1,
-                            dx_add0 ? dx_add1 : nullptr, fin, (hipStream_t)stream);
-  LHN_CHECK_ARG(rc == 1, "lhn_conv_dw_bwd4: no row kernel for k=%d dil=%d", k, dil);
-  LHN_CHECK_LAUNCH("lhn_conv_dw_bwd4");
-  return 0;
-}
-
-extern "C" int lhn_conv_stem_bwd(const float* img, const lhn_view* y, const lhn_gradview* gy, float* dw, int Hi, int Wi, int k,
-                                 int stride, int pad, int nrep, int64_t rep_stride, void* stream) {
-  if (nrep < 1) nrep = 1;
-  LHN_CHECK_ARG(img && lhn_view_ok(y) && gy && gy->dz && dw, "lhn_conv_stem_bwd: bad view / null pointer");
-  LHN_CHECK_ARG(pow2(y->C / 4) && y->C <= 256 && (k == 1 || k == 3 || k == 7), "lhn_conv_stem_bwd: Cout=%d k=%d", y->C, k);
-  const int PL = 256 / (y->C / 4);
-  const int g = grid_for((int64_t)y->N * y->H * y->W, PL, 4);
-  if (k == 7 && y->C == 64 && !lhn_dw_force_gather()) {
-    const size_t lds = (size_t)64 * (68 + 161) * 4;
-    static LhnKernelCfg cfg7;
-    int per_cu = 1;
-    if (!lhn_kernel_cfg(cfg7, &k_stem7_bwd_mfma, lds, 2, &per_cu)) {
-      lhn_set_error("lhn_conv_stem_bwd: cannot reserve %zu B of LDS", lds);
-      return 2;
-    }
-    const int64_t ntiles = ((int64_t)y->N * y->H * y->W + 63) / 64;
-    int grid = lhn_num_cus() * per_cu;
-    if (grid > ntiles) grid = (int)ntiles;
-    hipLaunchKernelGGL(k_stem7_bwd_mfma, dim3(grid), dim3(256), lds, (hipStream_t)stream, img, *y, *gy, dw, Hi, Wi, stride, pad, nrep, rep_stride);
-  } else if (k == 3 && y->C == 32 && !lhn_dw_force_gather()) {
-    const size_t lds = (size_t)256 * (36 + 33) * 4;
-    static LhnKernelCfg cfg;
-    int per_cu = 1;
-    if (!lhn_kernel_cfg(cfg, &k_stem3_bwd_mfma, lds, 2, &per_cu)) {
-      lhn_set_error("lhn_conv_stem_bwd: cannot reserve %zu B of LDS", lds);
-      return 2;
-    }
-    const int64_t ntiles = ((int64_t)y->N * y->H * y->W + 255) / 256;
-    int grid = lhn_num_cus() * per_cu;
-    if (grid > ntiles) grid = (int)ntiles;
-    hipLaunchKernelGGL(k_stem3_bwd_mfma, dim3(grid), dim3(256), lds, (hipStream_t)stream, img, *y, *gy, dw, Hi, Wi, stride, pad, nrep, rep_stride);
-  } else if (k == 3)
-    hipLaunchKernelGGL((k_stem_bwd<3, 3>), dim3(g), dim3(256), 0, (hipStream_t)stream, img, *y, *gy, dw, Hi, Wi, stride, pad, nrep, rep_stride, 0);
-  else if (k == 1)
-    hipLaunchKernelGGL((k_stem_bwd<1, 1>), dim3(g), dim3(256), 0, (hipStream_t)stream, img, *y, *gy, dw, Hi, Wi, stride, pad, nrep, rep_stride, 0);
-  else
-    for (int kh = 0; kh < 7; ++kh)
-      hipLaunchKernelGGL((k_stem_bwd<7, 1>), dim3(g), dim3(256), 0, (hipStream_t)stream, img, *y, *gy, dw, Hi, Wi, stride, pad, nrep, rep_stride, kh);
-  LHN_CHECK_LAUNCH("lhn_conv_stem_bwd");
-  return 0;
 }
 
 // =====================================================================================================
@@ -1765,112 +929,6 @@ __global__ void __launch_bounds__(256, (BNS || DIL > 1) ? 2 : 3) k_dw3_bwd_rows(
   }
 }
 
-// blocks per XCD when the XCD-aware tile order applies (grid a multiple of 8 and of 8 * cgroups), else 0 = plain order.
-// Measured on MI355X (variant B, bs64 256x256): giving each XCD a contiguous run of tiles is SLOWER than the plain
-// round-robin order -- forward 3.08 vs 2.93 ms, train step 9.66 vs 9.55 ms: the halo re-reads already hit the Infinity
-// Cache, while eight XCDs each streaming one contiguous region load the HBM channels less evenly.  Off unless LHN_XCD_ORDER=1.
-static int dw3_xchunk(int grid, int cgroups) {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("LHN_XCD_ORDER");
-    on = (e && e[0] == '1') ? 1 : 0;
-  }
-  return (on && grid % (8 * cgroups) == 0) ? grid / 8 : 0;
-}
-static int dw3_grid(int ntile, int cgroups, int per_cu) {
-  int g = lhn_num_cus() * per_cu;
-  g -= g % cgroups;
-  if (g > ntile) g = ntile;       // ntile is a multiple of cgroups
-  if (g < cgroups) g = cgroups;
-  return g;
-}
-
-template <int K, int DIL, int NS = 1>
-static void launch_dwk_fwd(const lhn_view* x, const float* w, const lhn_view* y, double* stats, lhn_bnfin fin, hipStream_t s, int ps = 1,
-                           const DwExtra* exp = nullptr) {
-  DwExtra ex;
-  if (exp) ex = *exp; else { ex.n = 0; ex.sum_out = nullptr; }
-  constexpr int TH = 8, TW = 32, P = DIL * (K - 1) / 2;
-  const int cg = (x->C + 31) / 32;
-  const int sh = (y->H + ps - 1) / ps, sw = (y->W + ps - 1) / ps;       // largest parity sub-lattice
-  const int th = (sh + TH - 1) / TH, tw = (sw + TW - 1) / TW, ntile = y->N * ps * ps * th * tw * cg;
-  const size_t lds = (size_t)((TH + 2 * P) * (TW + 2 * P) * 8 + 512 + K * K * 8) * 16;
-  const int per_cu = lds > 80 * 1024 ? 1 : (lds > 52 * 1024 ? 2 : 3);
-  static LhnKernelCfg cfg;
-  (void)lhn_kernel_cfg(cfg, &k_dwk_fwd_lds<K, DIL, NS>, lds, 4, nullptr);
-  const int grid = dw3_grid(ntile, cg, per_cu * 2);      // (2 / 3 / 4 / 8 / 16 blocks per CU measured in round 3: forward 2.65 / 2.68 / 2.66 / 2.71 / 2.71 ms)
-  hipLaunchKernelGGL((k_dwk_fwd_lds<K, DIL, NS>), dim3(grid), dim3(256), lds, s, *x, w, *y, stats, th, tw, cg, fin, ps, ex, dw3_xchunk(grid, cg));
-}
-template <int K, int DIL, bool BNS = false, bool FOLD = false>
-static void launch_dwk_bwd(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc,
-                           float* dw, int nrep, int64_t rep_stride, hipStream_t s, int ps = 1, const DwBnSum* bsp = nullptr,
-                           const lhn_bnbwdsrc* fsp = nullptr) {
-  constexpr int TH = 8, TW = 16, P = DIL * (K - 1) / 2;
-  DwBnSum bs;
-  if (bsp) bs = *bsp; else { bs.sums = nullptr; bs.save = nullptr; bs.C = bs.coff = 0; bs.add[0] = bs.add[1] = nullptr; }
-  lhn_bnbwdsrc fs;
-  if (FOLD && fsp) fs = *fsp; else memset(&fs, 0, sizeof(fs));
-  const int cg = (x->C + 31) / 32;
-  const int sh = (x->H + ps - 1) / ps, sw = (x->W + ps - 1) / ps;
-  const int th = (sh + TH - 1) / TH, tw = (sw + TW - 1) / TW, ntile = x->N * ps * ps * th * tw * cg;
-  const size_t lds = (size_t)((TH + 2 * P) * (TW + 2 * P) * 16 + 256 + 2 * K * K * 8 + (BNS ? TH * TW * 8 + 16 : 0) + (FOLD ? 24 : 0)) * 16;
-  static LhnKernelCfg cfg;
-  (void)lhn_kernel_cfg(cfg, &k_dwk_bwd_lds<K, DIL, BNS, FOLD>, lds, 4, nullptr);
-  const int grid = dw3_grid(ntile, cg, 4);
-  hipLaunchKernelGGL((k_dwk_bwd_lds<K, DIL, BNS, FOLD>), dim3(grid), dim3(256), lds, s, *x, w, *y, *gy, dx, dx_acc, dw, th, tw,
-                     cg, nrep, rep_stride, ps, bs, dw3_xchunk(grid, cg), fs);
-}
-template <int DIL, bool BNS = false>
-static void launch_dw3_bwd_rows(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc,
-                                float* dw, int nrep, int64_t rep_stride, hipStream_t s, int ps = 1, const DwBnSum* bsp = nullptr,
-                                const lhn_bnbwdsrc* fsp = nullptr) {
-  constexpr int P = DIL, R = 2 * P + 2, WW = 32 + 2 * P;
-  DwBnSum bs;
-  if (bsp) bs = *bsp; else { bs.sums = nullptr; bs.save = nullptr; bs.C = bs.coff = 0; bs.add[0] = bs.add[1] = nullptr; }
-  lhn_bnbwdsrc fs;      // the fold's scratch is 16 KB of the dy ring (17,408 B at DIL = 1)
-  if (fsp) fs = *fsp; else memset(&fs, 0, sizeof(fs));
-  static_assert(R * WW * 8 * 16 >= 2 * LHN_FIN_THREADS * 8, "dy ring holds the replica fold's partials");
-  const int cg = (x->C + 31) / 32;
-  const int sh = (x->H + ps - 1) / ps, sw = (x->W + ps - 1) / ps;     // largest parity sub-lattice
-  const int nstrips = (sw + 31) / 32;
-  const size_t lds = (size_t)(2 * R * WW * 8 + 2 * 9 * 8 + 16 + (BNS ? R * 32 * 8 : 0)) * 16;
-  static LhnKernelCfg cfg;
-  int per_cu = 1;
-  (void)lhn_kernel_cfg(cfg, &k_dw3_bwd_rows<DIL, BNS>, lds, 8, &per_cu);
-  // row chunks: about one item per resident workgroup, at least 8 rows each (the 2*P halo rows are loaded once per item)
-  const int base = x->N * ps * ps * nstrips * cg;
-  int nch = (lhn_num_cus() * per_cu + base - 1) / base;
-  nch = std::max(1, std::min(nch, (sh + 7) / 8));
-  const int CH = (sh + nch - 1) / nch;
-  nch = (sh + CH - 1) / CH;
-  const int ntile = base * nch;
-  const int grid = dw3_grid(ntile, cg, per_cu);       // one round of resident workgroups
-  hipLaunchKernelGGL((k_dw3_bwd_rows<DIL, BNS>), dim3(grid), dim3(256), lds, s, *x, w, *y, *gy, dx, dx_acc, dw, nstrips, nch, CH, cg,
-                     nrep, rep_stride, ps, bs, fs);
-}
-// LHN_DW_BWD_V1=1 (read once): the 3x3 backward runs the 8 x 16 tile kernel k_dwk_bwd_lds instead of k_dw3_bwd_rows
-static bool lhn_dw_bwd_v1() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("LHN_DW_BWD_V1");
-    v = (e && e[0] == '1') ? 1 : 0;
-  }
-  return v == 1;
-}
-// The size rule of the small-map route (3x3, dilation 1): H * W <= 256.  Train step of variant B at batch 64, per launch, rows kernel
-// against the tile kernel with its separate finalize launch (profiles/dwsmall_launches.md): 8^2 21.8 us against 10.9 + 4.7, 16^2 24.2
-// against 14.0 + 4.8, 32^2 30.3 against 31.7 + 4.9 -- so 32^2 and everything between 16^2 and 32^2, which was not measured, stay on
-// k_dw3_bwd_rows, where 64^2 and 128^2 were tuned.  LHN_DW_BWD_SMALL=0 (read once): every size on k_dw3_bwd_rows, for A/B runs.
-static bool dw_bwd_small(const lhn_view* x) {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("LHN_DW_BWD_SMALL");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v == 1 && (int64_t)x->H * x->W <= 256;
-}
-
-
 // =====================================================================================================
 // Stride-2 3x3 depthwise (pad 1) with the input tile in LDS: the downsampling convolutions of the stems and of
 // lite_hrnet.py's fuse / transition layers (54 per Lite-HRNet-18 step).  The row-gather kernels they used to take
@@ -2108,6 +1166,92 @@ __global__ void __launch_bounds__(256, 2) k_dws2_bwd_lds(lhn_view x, const float
   }
 }
 
+// =====================================================================================================
+// Launchers: grid, dynamic LDS and arguments of every kernel above.
+//
+// blocks per XCD when the XCD-aware tile order applies (grid a multiple of 8 and of 8 * cgroups), else 0 = plain order.
+// Measured on MI355X (variant B, bs64 256x256): giving each XCD a contiguous run of tiles is SLOWER than the plain
+// round-robin order -- forward 3.08 vs 2.93 ms, train step 9.66 vs 9.55 ms: the halo re-reads already hit the Infinity
+// Cache, while eight XCDs each streaming one contiguous region load the HBM channels less evenly.  Off unless LHN_XCD_ORDER=1.
+static int dw3_xchunk(int grid, int cgroups) {
+  static int on = -1;
+  if (on < 0) {
+    const char* e = getenv("LHN_XCD_ORDER");
+    on = (e && e[0] == '1') ? 1 : 0;
+  }
+  return (on && grid % (8 * cgroups) == 0) ? grid / 8 : 0;
+}
+static int dw3_grid(int ntile, int cgroups, int per_cu) {
+  int g = lhn_num_cus() * per_cu;
+  g -= g % cgroups;
+  if (g > ntile) g = ntile;       // ntile is a multiple of cgroups
+  if (g < cgroups) g = cgroups;
+  return g;
+}
+
+template <int K, int DIL, int NS = 1>
+static void launch_dwk_fwd(const lhn_view* x, const float* w, const lhn_view* y, double* stats, lhn_bnfin fin, hipStream_t s, int ps = 1,
+                           const DwExtra* exp = nullptr) {
+  DwExtra ex;
+  if (exp) ex = *exp; else { ex.n = 0; ex.sum_out = nullptr; }
+  constexpr int TH = 8, TW = 32, P = DIL * (K - 1) / 2;
+  const int cg = (x->C + 31) / 32;
+  const int sh = (y->H + ps - 1) / ps, sw = (y->W + ps - 1) / ps;       // largest parity sub-lattice
+  const int th = (sh + TH - 1) / TH, tw = (sw + TW - 1) / TW, ntile = y->N * ps * ps * th * tw * cg;
+  const size_t lds = (size_t)((TH + 2 * P) * (TW + 2 * P) * 8 + 512 + K * K * 8) * 16;
+  const int per_cu = lds > 80 * 1024 ? 1 : (lds > 52 * 1024 ? 2 : 3);
+  static LhnKernelCfg cfg;
+  (void)lhn_kernel_cfg(cfg, &k_dwk_fwd_lds<K, DIL, NS>, lds, 4, nullptr);
+  const int grid = dw3_grid(ntile, cg, per_cu * 2);      // (2 / 3 / 4 / 8 / 16 blocks per CU measured in round 3: forward 2.65 / 2.68 / 2.66 / 2.71 / 2.71 ms)
+  hipLaunchKernelGGL((k_dwk_fwd_lds<K, DIL, NS>), dim3(grid), dim3(256), lds, s, *x, w, *y, stats, th, tw, cg, fin, ps, ex, dw3_xchunk(grid, cg));
+}
+template <int K, int DIL, bool BNS = false, bool FOLD = false>
+static void launch_dwk_bwd(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc,
+                           float* dw, int nrep, int64_t rep_stride, hipStream_t s, int ps = 1, const DwBnSum* bsp = nullptr,
+                           const lhn_bnbwdsrc* fsp = nullptr) {
+  constexpr int TH = 8, TW = 16, P = DIL * (K - 1) / 2;
+  DwBnSum bs;
+  if (bsp) bs = *bsp; else { bs.sums = nullptr; bs.save = nullptr; bs.C = bs.coff = 0; bs.add[0] = bs.add[1] = nullptr; }
+  lhn_bnbwdsrc fs;
+  if (FOLD && fsp) fs = *fsp; else memset(&fs, 0, sizeof(fs));
+  const int cg = (x->C + 31) / 32;
+  const int sh = (x->H + ps - 1) / ps, sw = (x->W + ps - 1) / ps;
+  const int th = (sh + TH - 1) / TH, tw = (sw + TW - 1) / TW, ntile = x->N * ps * ps * th * tw * cg;
+  const size_t lds = (size_t)((TH + 2 * P) * (TW + 2 * P) * 16 + 256 + 2 * K * K * 8 + (BNS ? TH * TW * 8 + 16 : 0) + (FOLD ? 24 : 0)) * 16;
+  static LhnKernelCfg cfg;
+  (void)lhn_kernel_cfg(cfg, &k_dwk_bwd_lds<K, DIL, BNS, FOLD>, lds, 4, nullptr);
+  const int grid = dw3_grid(ntile, cg, 4);
+  hipLaunchKernelGGL((k_dwk_bwd_lds<K, DIL, BNS, FOLD>), dim3(grid), dim3(256), lds, s, *x, w, *y, *gy, dx, dx_acc, dw, th, tw,
+                     cg, nrep, rep_stride, ps, bs, dw3_xchunk(grid, cg), fs);
+}
+template <int DIL, bool BNS = false>
+static void launch_dw3_bwd_rows(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc,
+                                float* dw, int nrep, int64_t rep_stride, hipStream_t s, int ps = 1, const DwBnSum* bsp = nullptr,
+                                const lhn_bnbwdsrc* fsp = nullptr) {
+  constexpr int P = DIL, R = 2 * P + 2, WW = 32 + 2 * P;
+  DwBnSum bs;
+  if (bsp) bs = *bsp; else { bs.sums = nullptr; bs.save = nullptr; bs.C = bs.coff = 0; bs.add[0] = bs.add[1] = nullptr; }
+  lhn_bnbwdsrc fs;      // the fold's scratch is 16 KB of the dy ring (17,408 B at DIL = 1)
+  if (fsp) fs = *fsp; else memset(&fs, 0, sizeof(fs));
+  static_assert(R * WW * 8 * 16 >= 2 * LHN_FIN_THREADS * 8, "dy ring holds the replica fold's partials");
+  const int cg = (x->C + 31) / 32;
+  const int sh = (x->H + ps - 1) / ps, sw = (x->W + ps - 1) / ps;     // largest parity sub-lattice
+  const int nstrips = (sw + 31) / 32;
+  const size_t lds = (size_t)(2 * R * WW * 8 + 2 * 9 * 8 + 16 + (BNS ? R * 32 * 8 : 0)) * 16;
+  static LhnKernelCfg cfg;
+  int per_cu = 1;
+  (void)lhn_kernel_cfg(cfg, &k_dw3_bwd_rows<DIL, BNS>, lds, 8, &per_cu);
+  // row chunks: about one item per resident workgroup, at least 8 rows each (the 2*P halo rows are loaded once per item)
+  const int base = x->N * ps * ps * nstrips * cg;
+  int nch = (lhn_num_cus() * per_cu + base - 1) / base;
+  nch = std::max(1, std::min(nch, (sh + 7) / 8));
+  const int CH = (sh + nch - 1) / nch;
+  nch = (sh + CH - 1) / CH;
+  const int ntile = base * nch;
+  const int grid = dw3_grid(ntile, cg, per_cu);       // one round of resident workgroups
+  hipLaunchKernelGGL((k_dw3_bwd_rows<DIL, BNS>), dim3(grid), dim3(256), lds, s, *x, w, *y, *gy, dx, dx_acc, dw, nstrips, nch, CH, cg,
+                     nrep, rep_stride, ps, bs, fs);
+}
 // returns 1 if the stride-2 tiled kernel was launched
 static int dws2_fwd(const lhn_view* x, const float* w, const lhn_view* y, double* stats, lhn_bnfin fin, hipStream_t s) {
   using T = DwS2;
@@ -2130,101 +1274,307 @@ static int dws2_bwd(const lhn_view* x, const float* w, const lhn_view* y, const 
   hipLaunchKernelGGL(k_dws2_bwd_lds, dim3(dw3_grid(ntile, cg, 4)), dim3(256), lds, s, *x, w, *y, *gy, dx, dx_acc, dw, th, tw, cg, nrep, rep_stride);
   return 1;
 }
-
-// returns 1 if an LDS-tiled kernel was launched
-int lhn_dwk_fwd_lds(const lhn_view* x, const float* w, const lhn_view* y, double* stats, int k, int dil, lhn_bnfin fin,
-                    hipStream_t s, const DwExtra* ex) {
-  if (ex && ex->n > 0) {     // two summed sources: 3x3, dilation 1 or 2 (parity sub-lattices) -- MSRB's second round
-    if (k == 3 && dil == 1) launch_dwk_fwd<3, 1, 2>(x, w, y, stats, fin, s, 1, ex);
-    else if (k == 3 && dil == 2 && y->W >= 16) launch_dwk_fwd<3, 1, 2>(x, w, y, stats, fin, s, 2, ex);
-    else return 0;
-    return 1;
-  }
-  if (k == 3 && dil == 1) launch_dwk_fwd<3, 1>(x, w, y, stats, fin, s, 1, ex);
-  else if (k == 3 && dil == 2 && y->W >= 16) launch_dwk_fwd<3, 1>(x, w, y, stats, fin, s, 2, ex);    // parity sub-lattices
-  else if (k == 3 && dil == 2) launch_dwk_fwd<3, 2>(x, w, y, stats, fin, s, 1, ex);
-  else if (k == 7 && dil == 1) launch_dwk_fwd<7, 1>(x, w, y, stats, fin, s, 1, ex);
-  else return 0;
-  return 1;
+// the row-gather kernels: any k, stride, padding and dilation
+template <int K>
+static void launch_dw_fwd_gather(const lhn_view* x, const float* w, const lhn_view* y, double* stats, int stride, int pad, int dil,
+                                 lhn_bnfin fin, hipStream_t s) {
+  const size_t lds = (size_t)(K * K * x->C) * 4 + 256 * 2 * 16;
+  const int grid = grid_for((int64_t)y->N * y->H, 1, 8);
+  hipLaunchKernelGGL((k_dw_fwd<K>), dim3(grid), dim3(256), lds, s, *x, w, *y, stats, stride, pad, dil, fin, 0);
 }
-int lhn_dwk_bwd_lds(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc,
-                    float* dw, int k, int dil, int nrep, int64_t rep_stride, hipStream_t s, const DwBnSum* bs,
-                    const lhn_bnbwdsrc* fs) {
-  // fs (the BatchNorm-backward finalize of y in the prologue): k_dw3_bwd_rows and the small-map instances of k_dwk_bwd_lds (every
-  // 3x3 shape that is not under LHN_DW_BWD_V1=1 reaches one of the two) -- dw_bwd_folds() is the callers' test
-  if (fs && (lhn_dw_bwd_v1() || k != 3)) return 0;
-  // 3x3, dilation 1 on a map of at most 256 pixels: the 8 x 16 tile kernel, whose whole halo tile is ONE batch of loads, where
-  // a row strip pays CH + 2 = 10 dependent memory latencies and a barrier per row whatever the map size (dw_bwd_small)
-  const bool small = k == 3 && dil == 1 && dw_bwd_small(x);
-  if (bs && bs->sums) {        // fused BatchNorm-backward sums of the producer: the 3x3 / dilation 1 instance only
-    if (!(k == 3 && dil == 1 && dx && !dx_acc)) return 0;
-    if (lhn_dw_bwd_v1()) launch_dwk_bwd<3, 1, true>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs);
-    else if (small) launch_dwk_bwd<3, 1, true, true>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs, fs);
-    else launch_dw3_bwd_rows<1, true>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs, fs);
-    return 1;
+// data gradient unless dx is NULL, then the weight gradient unless dw is NULL (identity depthwise: no weight to learn), KR kernel
+// rows per launch
+template <int K, int KR>
+static void launch_dw_bwd_gather(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc,
+                                 float* dw, int stride, int pad, int dil, int nrep, int64_t rep_stride, hipStream_t s) {
+  if (dx) {
+    const size_t lds = (size_t)(K * K * x->C) * 4;
+    const int g = grid_for((int64_t)x->N * x->H, 1, 8);
+    hipLaunchKernelGGL((k_dw_bwd_data<K>), dim3(g), dim3(256), lds, s, *x, w, *y, *gy, dx, dx_acc, stride, pad, dil);
   }
-  const bool v1 = lhn_dw_bwd_v1();
-  if (k == 3 && dil == 1) {
-    if (v1) launch_dwk_bwd<3, 1>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs);
-    else if (small) launch_dwk_bwd<3, 1, false, true>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs, fs);
-    else launch_dw3_bwd_rows<1>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs, fs);
-  } else if (k == 3 && dil == 2 && x->W >= 16) {       // parity sub-lattices
-    if (v1) launch_dwk_bwd<3, 1>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 2, bs);
-    else launch_dw3_bwd_rows<1>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 2, bs, fs);
-  } else if (k == 3 && dil == 2) {
-    if (v1) launch_dwk_bwd<3, 2>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs);
-    else launch_dw3_bwd_rows<2>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs, fs);
-  } else if (k == 7 && dil == 1) launch_dwk_bwd<7, 1>(x, w, y, gy, dx, dx_acc, dw, nrep, rep_stride, s, 1, bs);     // K = 7: tile kernel
-  else return 0;
-  return 1;
+  const int gw = grid_for((int64_t)y->N * y->H, 1, 4);
+  for (int kh = 0; dw && kh < K; kh += KR)
+    hipLaunchKernelGGL((k_dw_bwd_weight<K, KR>), dim3(gw), dim3(256), 0, s, *x, *y, *gy, dw, stride, pad, dil, kh, nrep, rep_stride);
 }
 
-static int dw_fwd_extra(const lhn_view* x, const float* w, const lhn_view* y, double* stats, int k, int stride, int pad, int dil,
-                        lhn_bnfin fin, const lhn_view* extra, const float* coef, const lhn_view* so, hipStream_t s) {
-  if (!(stride == 1 && pad == dil * (k - 1) / 2 && x->C % 4 == 0 && y->W >= 8)) return 0;
-  if (!lhn_no_pend(x) || !lhn_no_pend(extra)) return 0;
+// =====================================================================================================
+// Route: which kernel a depthwise call runs.  dw_fwd_route() and dw_bwd_route() are pure and the only place that knows the rules;
+// the dispatchers below and lhn_conv_dw_route() (the host-only query, which the tests and profiles/dw_instances.md read) call them.
+struct DwShape {
+  int H, W, C;                  // of x
+  int k, stride, pad, dil;
+  unsigned f;                   // LHN_DW_F_*: what the call carries
+};
+enum DwKern {
+  DW_NONE = 0,      // no kernel for this k / dilation with these features
+  DW_NARROW,        // none either: the features live in the tiled stride-1 kernels, which this geometry does not reach
+  DWF_LDS31, DWF_LDS32, DWF_LDS71, DWF_LDS31_NS2, DWF_S2, DWF_GATHER1, DWF_GATHER3, DWF_GATHER5, DWF_GATHER7,
+  DWB_ROWS1, DWB_ROWS1_BNS, DWB_ROWS2, DWB_LDS31, DWB_LDS31_BNS, DWB_LDS31_FOLD, DWB_LDS31_BNS_FOLD, DWB_LDS32, DWB_LDS71, DWB_S2,
+  DWB_GATHER1, DWB_GATHER3, DWB_GATHER7
+};
+struct DwRoute {
+  DwKern kern;
+  int ps;                       // 2: a dilation-2 convolution run as four dilation-1 convolutions on the parity sub-lattices
+  bool separate_finalize;       // a finalize source is present and the kernel does not take it in its prologue
+};
+
+// LHN_DW_SW_*, read from the environment once.  LHN_DW_GATHER=1: the row-gather kernels.  LHN_DW_BWD_V1=1: the 3x3 backward runs the
+// 8 x 16 tile kernel k_dwk_bwd_lds instead of k_dw3_bwd_rows.  LHN_DW_BWD_SMALL=0: no small-map route, for A/B runs.
+static unsigned dw_switches() {
+  static int v = -1;
+  if (v < 0) {
+    const char *v1 = getenv("LHN_DW_BWD_V1"), *sm = getenv("LHN_DW_BWD_SMALL");
+    v = (lhn_dw_force_gather() ? LHN_DW_SW_GATHER : 0) | ((v1 && v1[0] == '1') ? LHN_DW_SW_BWD_V1 : 0) |
+        ((sm && sm[0] == '0') ? 0 : LHN_DW_SW_BWD_SMALL);
+  }
+  return (unsigned)v;
+}
+
+// The tiled kernels are built for stride 1 with "same" padding on maps at least 8 wide: 3x3 at dilation 1 and 2 (W >= 16: on the
+// parity sub-lattices of the dilation-1 kernel) and 7x7; 3x3 / stride 2 / pad 1 has a tiled kernel of its own.
+static bool dw_tiled_geometry(const DwShape& s) { return s.stride == 1 && s.pad == s.dil * (s.k - 1) / 2 && s.W >= 8; }
+static int dw_parity_split(const DwShape& s) { return (s.k == 3 && s.dil == 2 && s.W >= 16) ? 2 : 1; }
+
+static DwRoute dw_fwd_route(const DwShape& s, unsigned sw) {
+  const bool tiled = dw_tiled_geometry(s);
+  const int ps = dw_parity_split(s);
+  if (s.f & LHN_DW_F_EXTRA)      // two summed sources (MSRB's second round): 3x3 on the dilation-1 kernel only; ignores LHN_DW_GATHER
+    return {(tiled && s.k == 3 && (s.dil == 1 || ps == 2)) ? DWF_LDS31_NS2 : DW_NONE, ps, false};
+  if (!(s.f & LHN_DW_F_NO_WEIGHT) && !(sw & LHN_DW_SW_GATHER)) {
+    if (tiled && s.k == 3 && (s.dil == 1 || ps == 2)) return {DWF_LDS31, ps, false};
+    if (tiled && s.k == 3 && s.dil == 2) return {DWF_LDS32, 1, false};
+    if (tiled && s.k == 7 && s.dil == 1) return {DWF_LDS71, 1, false};
+    if (s.k == 3 && s.stride == 2 && s.pad == 1 && s.dil == 1) return {DWF_S2, 1, false};
+  }
+  return {s.k == 1 ? DWF_GATHER1 : s.k == 3 ? DWF_GATHER3 : s.k == 5 ? DWF_GATHER5 : s.k == 7 ? DWF_GATHER7 : DW_NONE, 1, false};
+}
+
+// The small-map rule (3x3, dilation 1): H * W <= 256 pixels run the 8 x 16 tile kernel, whose whole halo tile is ONE batch of loads,
+// where a row strip pays CH + 2 = 10 dependent memory latencies and a barrier per row whatever the map size.  Train step of variant B
+// at batch 64, per launch, rows kernel against the tile kernel with its separate finalize launch (profiles/dwsmall_launches.md): 8^2
+// 21.8 us against 10.9 + 4.7, 16^2 24.2 against 14.0 + 4.8, 32^2 30.3 against 31.7 + 4.9 -- so 32^2 and everything between 16^2 and
+// 32^2, which was not measured, stay on k_dw3_bwd_rows, where 64^2 and 128^2 were tuned.  The route's instances are the FOLD ones
+// (they take the finalize in their prologue as the row kernel does), also when the call has no finalize source.
+static DwRoute dw_bwd_route(const DwShape& s, unsigned sw) {
+  const bool bns = s.f & LHN_DW_F_BNSUM, ext = s.f & (LHN_DW_F_BNSUM | LHN_DW_F_ADDS);     // ext: these ignore LHN_DW_GATHER
+  const bool v1 = sw & LHN_DW_SW_BWD_V1;
+  const bool small = (sw & LHN_DW_SW_BWD_SMALL) && s.k == 3 && s.dil == 1 && (int64_t)s.H * s.W <= 256;
+  const int ps = dw_parity_split(s);
+  DwRoute r = {DW_NONE, 1, false};
+  if (!(s.f & LHN_DW_F_NO_WEIGHT) && dw_tiled_geometry(s) && (ext || !(sw & LHN_DW_SW_GATHER))) {
+    if (bns) {       // the producer's BatchNorm sums: 3x3 / dilation 1 instances only, dx stored
+      if (s.k == 3 && s.dil == 1 && !(s.f & (LHN_DW_F_NO_DX | LHN_DW_F_DX_ACC)))
+        r.kern = v1 ? DWB_LDS31_BNS : small ? DWB_LDS31_BNS_FOLD : DWB_ROWS1_BNS;
+    } else if (s.k == 3 && (s.dil == 1 || ps == 2)) {
+      r.kern = v1 ? DWB_LDS31 : small ? DWB_LDS31_FOLD : DWB_ROWS1;
+      r.ps = ps;
+    } else if (s.k == 3 && s.dil == 2) {
+      r.kern = v1 ? DWB_LDS32 : DWB_ROWS2;
+    } else if (s.k == 7 && s.dil == 1) {
+      r.kern = DWB_LDS71;      // K = 7: the tile kernel, which never folds
+    }
+  } else if (ext) {
+    r.kern = DW_NARROW;
+  }
+  if (r.kern == DW_NONE && !ext) {
+    if (!(s.f & LHN_DW_F_NO_WEIGHT) && s.k == 3 && s.stride == 2 && s.pad == 1 && s.dil == 1 && !(sw & LHN_DW_SW_GATHER)) r.kern = DWB_S2;
+    else r.kern = s.k == 1 ? DWB_GATHER1 : s.k == 3 ? DWB_GATHER3 : s.k == 7 ? DWB_GATHER7 : DW_NONE;
+  }
+  const bool folds = r.kern == DWB_ROWS1 || r.kern == DWB_ROWS1_BNS || r.kern == DWB_ROWS2 || r.kern == DWB_LDS31_FOLD ||
+                     r.kern == DWB_LDS31_BNS_FOLD;
+  r.separate_finalize = (s.f & LHN_DW_F_FIN) && !folds;
+  return r;
+}
+
+// =====================================================================================================
+// Dispatchers: validate once, ask the route, issue the separate finalize launch when the route says so, launch.
+static int dw_fwd_run(const lhn_view* x, const float* w, const lhn_view* y, double* stats, int k, int stride, int pad, int dil,
+                      const lhn_bnfin* finp, const lhn_view* extra, const float* coef2, const lhn_view* sum_out, void* stream) {
+  lhn_bnfin fin;
+  if (finp && stats) fin = *finp; else fin.counter = nullptr;
+  if (!extra) {
+    LHN_CHECK_ARG(!sum_out, "lhn_conv_dw_fwd: sum_out without a second source");
+    LHN_CHECK_ARG(lhn_view_ok(x) && lhn_view_ok(y) && (w || k == 1), "lhn_conv_dw_fwd: bad view / null pointer (w may be NULL = ones only for k=1)");
+    LHN_CHECK_ARG(x->C == y->C && x->C % 4 == 0 && x->C <= 512, "lhn_conv_dw_fwd: channels %d -> %d (multiple of 4, <= 512)", x->C, y->C);
+    LHN_CHECK_ARG((k == 1 || k == 3 || k == 5 || k == 7) && stride >= 1 && dil >= 1 && pad >= 0, "lhn_conv_dw_fwd: k=%d stride=%d dil=%d", k, stride, dil);
+    const int Ho = (x->H + 2 * pad - dil * (k - 1) - 1) / stride + 1, Wo = (x->W + 2 * pad - dil * (k - 1) - 1) / stride + 1;
+    LHN_CHECK_ARG(y->N == x->N && y->H == Ho && y->W == Wo, "lhn_conv_dw_fwd: output %dx%d, expected %dx%d", y->H, y->W, Ho, Wo);
+    LHN_CHECK_ARG(lhn_no_pend(x), "lhn_conv_dw_fwd: lhn_view.pend is reserved (NULL)");
+  } else {
+    LHN_CHECK_ARG(lhn_view_ok(x) && lhn_view_ok(y) && lhn_view_ok(extra) && w && coef2, "lhn_conv_dw_fwd: bad view / null pointer");
+    LHN_CHECK_ARG(extra->C == x->C && extra->N == x->N && extra->H == x->H && extra->W == x->W, "lhn_conv_dw_fwd: extra source geometry");
+    LHN_CHECK_ARG(x->C == y->C && y->N == x->N && y->H == x->H && y->W == x->W, "lhn_conv_dw_fwd: same-size output");
+    LHN_CHECK_ARG(!sum_out || (sum_out->data && sum_out->C == x->C && sum_out->N == x->N && sum_out->H == x->H && sum_out->W == x->W &&
+                               sum_out->cstride % 4 == 0 && sum_out->coff % 4 == 0 && sum_out->coff + sum_out->C <= sum_out->cstride),
+                  "lhn_conv_dw_fwd: sum_out geometry (same pixels and channels as x)");
+  }
+  const DwShape sh = {x->H, x->W, x->C, k, stride, pad, dil, (w ? 0u : LHN_DW_F_NO_WEIGHT) | (extra ? LHN_DW_F_EXTRA : 0u)};
+  const DwRoute r = dw_fwd_route(sh, dw_switches());
+  LHN_CHECK_ARG(!extra || (r.kern != DW_NONE && lhn_no_pend(x) && lhn_no_pend(extra)),
+                "lhn_conv_dw_fwd: a second source needs k=3, stride 1, 'same' padding, W >= 8 (got k=%d s=%d C=%d W=%d)", k, stride, x->C, y->W);
   DwExtra ex;
-  ex.v = *extra;
-  ex.coef[0] = coef[0];
-  ex.coef[1] = coef[1];
-  ex.n = 1;
-  ex.sum_out = so ? so->data : nullptr;
-  ex.so_cstride = so ? so->cstride : 0;
-  ex.so_coff = so ? so->coff : 0;
-  return lhn_dwk_fwd_lds(x, w, y, stats, k, dil, fin, s, &ex);
+  memset(&ex, 0, sizeof(ex));
+  if (extra) {
+    ex.v = *extra;
+    ex.coef[0] = coef2[0];
+    ex.coef[1] = coef2[1];
+    ex.n = 1;
+    ex.sum_out = sum_out ? sum_out->data : nullptr;
+    ex.so_cstride = sum_out ? sum_out->cstride : 0;
+    ex.so_coff = sum_out ? sum_out->coff : 0;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  switch (r.kern) {
+    case DWF_LDS31: launch_dwk_fwd<3, 1>(x, w, y, stats, fin, s, r.ps, &ex); break;
+    case DWF_LDS32: launch_dwk_fwd<3, 2>(x, w, y, stats, fin, s, 1, &ex); break;
+    case DWF_LDS71: launch_dwk_fwd<7, 1>(x, w, y, stats, fin, s, 1, &ex); break;
+    case DWF_LDS31_NS2: launch_dwk_fwd<3, 1, 2>(x, w, y, stats, fin, s, r.ps, &ex); break;
+    case DWF_S2:
+      if (dws2_fwd(x, w, y, stats, fin, s)) break;
+      [[fallthrough]];      // (its LDS reservation was refused: the gather kernel computes the same)
+    case DWF_GATHER3: launch_dw_fwd_gather<3>(x, w, y, stats, stride, pad, dil, fin, s); break;
+    case DWF_GATHER1: launch_dw_fwd_gather<1>(x, w, y, stats, stride, pad, dil, fin, s); break;
+    case DWF_GATHER5: launch_dw_fwd_gather<5>(x, w, y, stats, stride, pad, dil, fin, s); break;
+    case DWF_GATHER7: launch_dw_fwd_gather<7>(x, w, y, stats, stride, pad, dil, fin, s); break;
+    default: LHN_CHECK_ARG(false, "lhn_conv_dw_fwd: no kernel for k=%d", k);
+  }
+  LHN_CHECK_LAUNCH("lhn_conv_dw_fwd");
+  return 0;
 }
 
-static int dw_bwd_addends(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc, float* dw,
-                          int k, int dil, int nrep, int64_t rep_stride, const float* a0, const float* a1, hipStream_t s) {
-  DwBnSum bs;
-  bs.sums = nullptr;
-  bs.save = nullptr;
-  bs.C = bs.coff = 0;
-  bs.add[0] = a0;
-  bs.add[1] = a1;
-  return lhn_dwk_bwd_lds(x, w, y, gy, dx, dx_acc, dw, k, dil, nrep, rep_stride, s, &bs);
+static int dw_bwd_run(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate, float* dw,
+                      int k, int stride, int pad, int dil, int nrep, int64_t rep_stride, const lhn_bnsum* bns, const float* dx_add0,
+                      const float* dx_add1, const lhn_bnbwdsrc* fin, void* stream) {
+  if (nrep < 1) nrep = 1;
+  if (bns && !bns->sums) bns = nullptr;
+  if (fin && !fin->sums) fin = nullptr;
+  const bool has_add = dx_add0 || dx_add1;
+  const bool same = stride == 1 && pad == dil * (k - 1) / 2;
+  LHN_CHECK_ARG(!(bns && has_add), "lhn_conv_dw_bwd: producer sums and gradient addends exclude each other");
+  if (fin)
+    LHN_CHECK_ARG(lhn_view_ok(x) && lhn_view_ok(y) && gy && gy->dz && gy->coef && fin->save_mean_invstd && fin->count > 0 &&
+                      fin->stat_channels >= y->C && x->C == y->C && lhn_no_pend(x) && lhn_no_pend(y),
+                  "lhn_conv_dw_bwd: finalize source needs gy->coef, saved statistics and stat_channels >= C");
+  if (bns) {
+    LHN_CHECK_ARG(lhn_view_ok(x) && lhn_view_ok(y) && gy && gy->dz && w && dw && dx && bns->save && lhn_no_pend(x) && lhn_no_pend(y),
+                  "lhn_conv_dw_bwd: bad view / null pointer");
+    LHN_CHECK_ARG(!dx_accumulate && !x->gate && same && x->C % 32 == 0 && x->C == y->C && bns->coff >= 0 && bns->coff + x->C <= bns->C,
+                  "lhn_conv_dw_bwd: fused BatchNorm sums need this convolution to be the only, ungated, stride-1 reader of x (dx stored)");
+  } else if (has_add) {
+    LHN_CHECK_ARG(lhn_view_ok(x) && lhn_view_ok(y) && gy && gy->dz && w && dw && dx && lhn_no_pend(x) && lhn_no_pend(y),
+                  "lhn_conv_dw_bwd: bad view / null pointer");
+    LHN_CHECK_ARG(same && x->C == y->C, "lhn_conv_dw_bwd: gradient addends need the tiled stride-1 kernel (W >= 8)");
+  } else {
+    LHN_CHECK_ARG(lhn_view_ok(x) && lhn_view_ok(y) && gy && gy->dz && ((w && dw) || k == 1) && lhn_no_pend(x) && lhn_no_pend(y),
+                  "lhn_conv_dw_bwd: bad view / null pointer");
+    LHN_CHECK_ARG(x->C == y->C && x->C % 4 == 0 && x->C <= 512, "lhn_conv_dw_bwd: channels");
+    LHN_CHECK_ARG(k == 1 || k == 3 || k == 7, "lhn_conv_dw_bwd: k=%d (1, 3 or 7)", k);
+  }
+  const DwShape sh = {x->H, x->W, x->C, k, stride, pad, dil,
+                      ((w && dw) ? 0u : LHN_DW_F_NO_WEIGHT) | (bns ? LHN_DW_F_BNSUM : 0u) | (has_add ? LHN_DW_F_ADDS : 0u) |
+                          (fin ? LHN_DW_F_FIN : 0u) | (dx ? 0u : LHN_DW_F_NO_DX) | (dx_accumulate ? LHN_DW_F_DX_ACC : 0u)};
+  const DwRoute r = dw_bwd_route(sh, dw_switches());
+  if (bns) {
+    LHN_CHECK_ARG(r.kern != DW_NARROW,
+                  "lhn_conv_dw_bwd: fused BatchNorm sums need this convolution to be the only, ungated, stride-1 reader of x (dx stored)");
+    LHN_CHECK_ARG(r.kern != DW_NONE, "lhn_conv_dw_bwd: fused BatchNorm sums are built for the 3x3 / dilation 1 kernel (k=%d dil=%d)", k, dil);
+  } else if (has_add) {
+    LHN_CHECK_ARG(r.kern != DW_NARROW, "lhn_conv_dw_bwd: gradient addends need the tiled stride-1 kernel (W >= 8)");
+    LHN_CHECK_ARG(r.kern != DW_NONE, "lhn_conv_dw_bwd: no tiled kernel for k=%d dil=%d", k, dil);
+  }
+  // (a finalize that rides in the kernel: the plain call's channel limit, whatever else the call carries)
+  LHN_CHECK_ARG(!fin || r.separate_finalize || x->C <= 512, "lhn_conv_dw_bwd: channels");
+  if (r.separate_finalize) {
+    const int rc = lhn_bn_bwd_finalize2(fin->sums, fin->gamma, fin->save_mean_invstd, const_cast<float*>(gy->coef), y->cstride, y->coff,
+                                        y->C, fin->stat_channels, fin->count, fin->dgamma, fin->dbeta, fin->pgrad_scale, stream);
+    if (rc) return rc;
+  }
+  const DwBnSum bs = {bns ? bns->sums : nullptr, bns ? bns->save : nullptr, bns ? bns->C : 0, bns ? bns->coff : 0,
+                      {dx_add0 ? dx_add0 : dx_add1, dx_add0 ? dx_add1 : nullptr}};
+  const lhn_bnbwdsrc* fs = r.separate_finalize ? nullptr : fin;
+  const int acc = bns ? 0 : dx_accumulate;
+  hipStream_t s = (hipStream_t)stream;
+  switch (r.kern) {
+    case DWB_ROWS1: launch_dw3_bwd_rows<1>(x, w, y, gy, dx, acc, dw, nrep, rep_stride, s, r.ps, &bs, fs); break;
+    case DWB_ROWS1_BNS: launch_dw3_bwd_rows<1, true>(x, w, y, gy, dx, acc, dw, nrep, rep_stride, s, 1, &bs, fs); break;
+    case DWB_ROWS2: launch_dw3_bwd_rows<2>(x, w, y, gy, dx, acc, dw, nrep, rep_stride, s, 1, &bs, fs); break;
+    case DWB_LDS31: launch_dwk_bwd<3, 1>(x, w, y, gy, dx, acc, dw, nrep, rep_stride, s, r.ps, &bs); break;
+    case DWB_LDS31_BNS: launch_dwk_bwd<3, 1, true>(x, w, y, gy, dx, acc, dw, nrep, rep_stride, s, 1, &bs); break;
+    case DWB_LDS31_FOLD: launch_dwk_bwd<3, 1, false, true>(x, w, y, gy, dx, acc, dw, nrep, rep_stride, s, 1, &bs, fs); break;
+    case DWB_LDS31_BNS_FOLD: launch_dwk_bwd<3, 1, true, true>(x, w, y, gy, dx, acc, dw, nrep, rep_stride, s, 1, &bs, fs); break;
+    case DWB_LDS32: launch_dwk_bwd<3, 2>(x, w, y, gy, dx, acc, dw, nrep, rep_stride, s, 1, &bs); break;
+    case DWB_LDS71: launch_dwk_bwd<7, 1>(x, w, y, gy, dx, acc, dw, nrep, rep_stride, s, 1, &bs); break;
+    case DWB_S2:
+      if (dws2_bwd(x, w, y, gy, dx, acc, dw, nrep, rep_stride, s)) break;
+      [[fallthrough]];      // (its LDS reservation was refused: the gather pair computes the same)
+    case DWB_GATHER3: launch_dw_bwd_gather<3, 3>(x, w, y, gy, dx, acc, dw, stride, pad, dil, nrep, rep_stride, s); break;
+    case DWB_GATHER1: launch_dw_bwd_gather<1, 1>(x, w, y, gy, dx, acc, dw, stride, pad, dil, nrep, rep_stride, s); break;
+    case DWB_GATHER7: launch_dw_bwd_gather<7, 1>(x, w, y, gy, dx, acc, dw, stride, pad, dil, nrep, rep_stride, s); break;
+    default: LHN_CHECK_ARG(false, "lhn_conv_dw_bwd: no kernel for k=%d", k);
+  }
+  LHN_CHECK_LAUNCH("lhn_conv_dw_bwd");
+  return 0;
 }
 
-static int dw_bwd_fin(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc, float* dw, int k,
-                      int dil, int nrep, int64_t rep_stride, const lhn_bnsum* bns, const float* a0, const float* a1, const lhn_bnbwdsrc* fin,
-                      hipStream_t s) {
-  DwBnSum bs;
-  bs.sums = bns ? bns->sums : nullptr;
-  bs.save = bns ? bns->save : nullptr;
-  bs.C = bns ? bns->C : 0;
-  bs.coff = bns ? bns->coff : 0;
-  bs.add[0] = a0;
-  bs.add[1] = a1;
-  return lhn_dwk_bwd_lds(x, w, y, gy, dx, dx_acc, dw, k, dil, nrep, rep_stride, s, &bs, fin);
+// =====================================================================================================
+// Entry points.  The numbered forms differ in what a call may carry; each forwards to the widest.
+extern "C" int lhn_conv_dw_fwd(const lhn_view* x, const float* w, const lhn_view* y, double* stats, int k, int stride,
+                               int pad, int dil, const lhn_bnfin* finp, void* stream) {
+  return lhn_conv_dw_fwd3(x, w, y, stats, k, stride, pad, dil, finp, nullptr, nullptr, nullptr, stream);
+}
+extern "C" int lhn_conv_dw_fwd2(const lhn_view* x, const float* w, const lhn_view* y, double* stats, int k, int stride,
+                                int pad, int dil, const lhn_bnfin* finp, const lhn_view* extra, const float* coef2, void* stream) {
+  return lhn_conv_dw_fwd3(x, w, y, stats, k, stride, pad, dil, finp, extra, coef2, nullptr, stream);
+}
+extern "C" int lhn_conv_dw_fwd3(const lhn_view* x, const float* w, const lhn_view* y, double* stats, int k, int stride,
+                                int pad, int dil, const lhn_bnfin* finp, const lhn_view* extra, const float* coef2,
+                                const lhn_view* sum_out, void* stream) {
+  return dw_fwd_run(x, w, y, stats, k, stride, pad, dil, finp, extra, coef2, sum_out, stream);
 }
 
-static int dw_bwd_fused(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, float* dw, int k,
-                        int dil, int nrep, int64_t rep_stride, double* bn_sums, const float* bn_save, int bn_C, int bn_coff, hipStream_t s) {
-  DwBnSum bs;
-  bs.sums = bn_sums;
-  bs.save = bn_save;
-  bs.C = bn_C;
-  bs.coff = bn_coff;
-  bs.add[0] = bs.add[1] = nullptr;
-  return lhn_dwk_bwd_lds(x, w, y, gy, dx, 0, dw, k, dil, nrep, rep_stride, s, &bs);
+extern "C" int lhn_conv_dw_bwd(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
+                               int dx_accumulate, float* dw, int k, int stride, int pad, int dil, int nrep, int64_t rep_stride,
+                               void* stream) {
+  return lhn_conv_dw_bwd4(x, w, y, gy, dx, dx_accumulate, dw, k, stride, pad, dil, nrep, rep_stride, nullptr, nullptr, nullptr, nullptr, stream);
+}
+extern "C" int lhn_conv_dw_bwd2(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
+                                int dx_accumulate, float* dw, int k, int stride, int pad, int dil, int nrep, int64_t rep_stride,
+                                double* bn_sums, const float* bn_save, int bn_C, int bn_coff, void* stream) {
+  const lhn_bnsum bns = {bn_sums, bn_save, bn_C, bn_coff};
+  return lhn_conv_dw_bwd4(x, w, y, gy, dx, dx_accumulate, dw, k, stride, pad, dil, nrep, rep_stride, &bns, nullptr, nullptr, nullptr, stream);
+}
+extern "C" int lhn_conv_dw_bwd3(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
+                                int dx_accumulate, float* dw, int k, int stride, int pad, int dil, int nrep, int64_t rep_stride,
+                                const float* dx_add0, const float* dx_add1, void* stream) {
+  return lhn_conv_dw_bwd4(x, w, y, gy, dx, dx_accumulate, dw, k, stride, pad, dil, nrep, rep_stride, nullptr, dx_add0, dx_add1, nullptr, stream);
+}
+extern "C" int lhn_conv_dw_bwd4(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
+                                int dx_accumulate, float* dw, int k, int stride, int pad, int dil, int nrep, int64_t rep_stride,
+                                const lhn_bnsum* bns, const float* dx_add0, const float* dx_add1, const lhn_bnbwdsrc* fin,
+                                void* stream) {
+  return dw_bwd_run(x, w, y, gy, dx, dx_accumulate, dw, k, stride, pad, dil, nrep, rep_stride, bns, dx_add0, dx_add1, fin, stream);
+}
+
+// Host only: the name of what dw_fwd_run / dw_bwd_run would launch (include/lhn.h).
+extern "C" const char* lhn_conv_dw_route(int backward, int H, int W, int C, int k, int stride, int pad, int dil, int features,
+                                         int switches) {
+  static const char* const name[] = {
+      nullptr, nullptr, "k_dwk_fwd_lds<3,1>", "k_dwk_fwd_lds<3,2>", "k_dwk_fwd_lds<7,1>", "k_dwk_fwd_lds<3,1,2>", "k_dws2_fwd_lds",
+      "k_dw_fwd<1>", "k_dw_fwd<3>", "k_dw_fwd<5>", "k_dw_fwd<7>",
+      "k_dw3_bwd_rows<1>", "k_dw3_bwd_rows<1,BNS>", "k_dw3_bwd_rows<2>", "k_dwk_bwd_lds<3,1>", "k_dwk_bwd_lds<3,1,BNS>",
+      "k_dwk_bwd_lds<3,1,false,true>", "k_dwk_bwd_lds<3,1,BNS,true>", "k_dwk_bwd_lds<3,2>", "k_dwk_bwd_lds<7,1>", "k_dws2_bwd_lds"};
+  static const char* const gdata[] = {"k_dw_bwd_data<1>", "k_dw_bwd_data<3>", "k_dw_bwd_data<7>"};
+  static const char* const gweight[] = {"k_dw_bwd_weight<1,1>", "k_dw_bwd_weight<3,3>", "k_dw_bwd_weight<7,1> x 7"};
+  const DwShape sh = {H, W, C, k, stride, pad, dil, (unsigned)features};
+  const DwRoute r = (backward ? dw_bwd_route : dw_fwd_route)(sh, switches < 0 ? dw_switches() : (unsigned)switches);
+  if (r.kern == DW_NONE || r.kern == DW_NARROW) return nullptr;
+  static thread_local char buf[128];
+  const char* fin = r.separate_finalize ? "lhn_bn_bwd_finalize2 + " : "";
+  if (r.kern >= DWB_GATHER1) {
+    const bool d = !(features & LHN_DW_F_NO_DX), wg = !(features & LHN_DW_F_NO_WEIGHT);
+    snprintf(buf, sizeof(buf), "%s%s%s%s", fin, d ? gdata[r.kern - DWB_GATHER1] : "", d && wg ? " + " : "", wg ? gweight[r.kern - DWB_GATHER1] : "");
+  } else {
+    snprintf(buf, sizeof(buf), "%s%s%s", fin, name[r.kern], r.ps == 2 ? " ps=2" : "");
+  }
+  return buf;
 }

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <mutex>
 #include "../../include/lhn.h"
@@ -53,6 +54,25 @@ static inline int lhn_device_slot() {
 }
 int lhn_num_cus();   // lhn_api.cpp: CUs of the current device; grid caps for persistent grid-stride kernels
 bool lhn_deterministic_mode();   // LHN_DETERMINISTIC=1, see lhn_api.cpp
+// grid of a persistent kernel: one block per `per_block` items, at most `cap_per_cu` blocks per CU
+static inline int grid_for(int64_t items_per_block_total, int per_block, int cap_per_cu) {
+  int64_t g = (items_per_block_total + per_block - 1) / per_block;
+  const int64_t cap = (int64_t)lhn_num_cus() * cap_per_cu;
+  if (g > cap) g = cap;
+  if (g < 1) g = 1;
+  return (int)g;
+}
+static inline bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+// LHN_DW_GATHER=1 (read once per translation unit): the depthwise and stem convolutions run their row-gather kernels
+// (k_conv_dw.hip, k_conv_stem.hip)
+static inline bool lhn_dw_force_gather() {
+  static int v = -1;
+  if (v < 0) {
+    const char* e = getenv("LHN_DW_GATHER");
+    v = (e && e[0] == '1') ? 1 : 0;
+  }
+  return v == 1;
+}
 // k_bottleneck.hip: lhn_bottleneck_fwd with the choice of skipping the tap-major copy of w2 (relayout = 0: wt_scratch holds it already)
 int lhn_bottleneck_fwd_impl(const lhn_view* x, int Cm, const float* w1, const float* b1, const float* t1, const float* w2, const float* t2,
                             const float* w3, const float* b3, const float* t3, float out_slope, const lhn_view* y, float* wt_scratch,

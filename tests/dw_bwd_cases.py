@@ -4,7 +4,7 @@ what the same operation loses in the kernels' own precision).  Imported by tests
 process with its own environment, e.g. LHN_DW_BWD_V1=1, LHN_DW_GATHER=1 or LHN_DETERMINISTIC=1) it writes the kernel outputs of
 the named cases to an .npz file.
 
-kernel_of(name) repeats the dispatch of lhn_conv_dw_bwd / lhn_dwk_bwd_lds; profiles/dw_instances.md is printed from it."""
+kernel_of(name) asks the library which kernels a case runs (lhn_conv_dw_route); profiles/dw_instances.md is printed from it."""
 import ctypes as C
 import os
 import sys
@@ -81,22 +81,18 @@ def out_hw(name):
     return f(h), f(w)
 
 
-def kernel_of(name, gather=False, v1=False):
-    """The kernels lhn_conv_dw_bwd / _bwd2 / _bwd3 launch for a case (gather: LHN_DW_GATHER=1, v1: LHN_DW_BWD_V1=1)."""
+F_NO_WEIGHT, F_BNSUM, F_ADDS, F_DX_ACC = 1, 4, 8, 64        # LHN_DW_F_* (include/lhn.h)
+SW_GATHER, SW_BWD_V1, SW_BWD_SMALL = 1, 2, 4                # LHN_DW_SW_*
+
+
+def kernel_of(name, gather=False, v1=False, small=True):
+    """The kernels lhn_conv_dw_bwd / _bwd2 / _bwd3 launch for a case, asked of the library (lhn_conv_dw_route: host only).
+    gather: LHN_DW_GATHER=1, v1: LHN_DW_BWD_V1=1, small=False: LHN_DW_BWD_SMALL=0.  None: no kernel for the case."""
     n, h, w, cs, coff, c, dil, flags, k, stride, pad = _ALL[name]
     f = flags.split()
-    bns, adds = "bns" in f, ("add0" in f or "add1" in f)
-    if "wnull" not in f and k in (3, 7) and stride == 1 and pad == dil * (k - 1) // 2 and w >= 8 and (not gather or bns or adds):
-        if k == 7:
-            return "k_dwk_bwd_lds<7,1>"
-        ps, d = (2, 1) if (dil == 2 and w >= 16) else (1, dil)
-        kern = f"k_dwk_bwd_lds<3,{d}{',BNS' if bns else ''}>" if v1 else f"k_dw3_bwd_rows<{d}{',BNS' if bns else ''}>"
-        return kern + (" ps=2" if ps == 2 else "")
-    if "wnull" not in f and k == 3 and stride == 2 and pad == 1 and dil == 1 and not gather:
-        return "k_dws2_bwd_lds"
-    if "wnull" in f:
-        return f"k_dw_bwd_data<{k}>"
-    return f"k_dw_bwd_data<{k}> + k_dw_bwd_weight<{k},{1 if k == 7 else k}>" + (" x 7" if k == 7 else "")
+    feat = (F_NO_WEIGHT * ("wnull" in f) | F_BNSUM * ("bns" in f) | F_ADDS * ("add0" in f or "add1" in f) | F_DX_ACC * ("acc" in f))
+    r = _lib.lib().lhn_conv_dw_route(1, h, w, c, k, stride, pad, dil, feat, SW_GATHER * gather | SW_BWD_V1 * v1 | SW_BWD_SMALL * small)
+    return r.decode() if r is not None else None
 
 
 def _rand(shape, seed, scale=1.0):
@@ -263,7 +259,8 @@ def _check_reference():
             e = rel_err(r32[kk], r64[kk])
             assert np.isfinite(3 * e), f"{nm} {kk}"
             worst = max(worst, e)
-        print(f"{nm:22s} {kernel_of(nm):50s} v1: {kernel_of(nm, v1=True):28s} gather: {kernel_of(nm, gather=True)}")
+        print(f"{nm:22s} {kernel_of(nm):50s} small=0: {kernel_of(nm, small=False):50s} v1: {kernel_of(nm, v1=True):50s} "
+              f"gather: {kernel_of(nm, gather=True)}")
     print(f"{len(CASES)} cases, worst float32 error {worst:.2e}, {time.time() - t0:.1f} s")
 
 

@@ -5,7 +5,7 @@ LHN_DETERMINISTIC=1) it writes the kernel outputs of the named cases to an .npz 
     python tests/dw_fwd_cases.py OUT.npz REPEATS NAME ...
     python tests/dw_fwd_cases.py --check-reference        (CPU only: every case's inputs, both references, the dispatch table)
 
-kernel_of(name) repeats the dispatch of lhn_conv_dw_fwd / lhn_dwk_fwd_lds; profiles/dw_instances.md is printed from it."""
+kernel_of(name) asks the library which kernel a case runs (lhn_conv_dw_route); profiles/dw_instances.md is printed from it."""
 import ctypes as C
 import os
 import sys
@@ -121,22 +121,12 @@ def out_hw(c):
 
 
 def kernel_of(name, gather=False):
-    """The kernel lhn_conv_dw_fwd / lhn_conv_dw_fwd3 launch for a case (gather: under LHN_DW_GATHER=1)."""
+    """The kernel lhn_conv_dw_fwd / lhn_conv_dw_fwd3 launch for a case, asked of the library (lhn_conv_dw_route: host only).
+    gather: under LHN_DW_GATHER=1.  None: no kernel for the case."""
     c = _ALL[name]
-    k, s, d, p, f = c["k"], c["s"], c["d"], c["p"], c["flags"]
-    wo = out_hw(c)[1]
-    if "extra" in f:
-        return "k_dwk_fwd_lds<3,1,2>" + (" ps=2" if d == 2 else "")
-    if "wnull" not in f and s == 1 and p == d * (k - 1) // 2 and wo >= 8 and not gather:
-        if k == 3 and d == 1:
-            return "k_dwk_fwd_lds<3,1>"
-        if k == 3 and d == 2:
-            return "k_dwk_fwd_lds<3,1> ps=2" if wo >= 16 else "k_dwk_fwd_lds<3,2>"
-        if k == 7 and d == 1:
-            return "k_dwk_fwd_lds<7,1>"
-    if "wnull" not in f and k == 3 and s == 2 and p == 1 and d == 1 and not gather:
-        return "k_dws2_fwd_lds"
-    return f"k_dw_fwd<{k}>"
+    feat = 1 * ("wnull" in c["flags"]) | 2 * ("extra" in c["flags"])        # LHN_DW_F_NO_WEIGHT, LHN_DW_F_EXTRA (include/lhn.h)
+    r = _lib.lib().lhn_conv_dw_route(0, c["h"], c["w"], c["c"], c["k"], c["s"], c["p"], c["d"], feat, 1 if gather else 0)   # LHN_DW_SW_GATHER
+    return r.decode() if r is not None else None
 
 
 def xcd_grid(name, cus=256):

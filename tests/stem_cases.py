@@ -1,4 +1,4 @@
-"""Cases of the stem convolution (lhn_conv_stem_fwd / lhn_conv_stem_bwd, csrc/k_conv_dw.hip: dense k x k on the 3-channel NCHW image)
+"""Cases of the stem convolution (lhn_conv_stem_fwd / lhn_conv_stem_bwd, csrc/k_conv_stem.hip: dense k x k on the 3-channel NCHW image)
 run through the C ABI, with a plain torch reference on the CPU (float64, or float32 to measure what the same operation loses in
 the kernels' own precision).  Imported by tests/test_stem_gpu.py; run as a script (a child process with its own environment:
 LHN_DW_GATHER=1 or LHN_DETERMINISTIC=1) it writes the kernel outputs of the named cases to an .npz file:
@@ -301,8 +301,8 @@ def offset_premise(name, g=None):
 def _check_reference():
     import time
     t0, worst = time.time(), 0.0
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "litehandnet_amd", "csrc", "k_conv_dw.hip")).read()
-    fwd_src = src[src.index('extern "C" int lhn_conv_stem_fwd'):src.index("// Backward.  dy is formed on the fly")]
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "litehandnet_amd", "csrc", "k_conv_stem.hip")).read()
+    fwd_src = src[src.index('extern "C" int lhn_conv_stem_fwd'):src.index("stem backward (weight gradient")]
     bwd_src = src[src.index('extern "C" int lhn_conv_stem_bwd'):]
     for s, kind in ((fwd_src, "fwd"), (bwd_src, "bwd")):      # the two conditions kernel_of repeats, as the launchers spell them
         i7 = s.index("if (k == 7 && y->C == 64 && !lhn_dw_force_gather())")

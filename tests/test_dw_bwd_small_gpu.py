@@ -1,4 +1,4 @@
-"""The small-map route of the 3x3 / dilation-1 depthwise backward (lhn_dwk_bwd_lds: maps of at most 256 pixels run the 8 x 16 tile
+"""The small-map route of the 3x3 / dilation-1 depthwise backward (dw_bwd_route: maps of at most 256 pixels run the 8 x 16 tile
 kernel k_dwk_bwd_lds with the BatchNorm-backward finalize folded into its prologue instead of the row kernel k_dw3_bwd_rows), through
 lhn_conv_dw_bwd4 with the finalize source, so every case exercises the fold.
 
