@@ -446,6 +446,37 @@ int lhn_bilinear_bwd(const lhn_view* src, const lhn_view* dst, const float* ddst
 int lhn_shuffle2_fwd(const lhn_view* a, const lhn_view* b, const lhn_view* dst, void* stream);
 int lhn_shuffle2_bwd(const lhn_view* a, const lhn_view* b, const lhn_view* dst, const float* ddst, float* da, int acc_a,
                      float* db, int acc_b, void* stream);
+/* ConditionalChannelWeighting (lite_hrnet.py:110-143) of an inference plan as four grouped launches: every call serves all B = 2..4
+ * branches of the block in ONE grid.  Branch b has x2[b] (the upper half of the block's input, [N, H_b, W_b, C_b]), x1[b] (the lower
+ * half), y[b] (the depthwise convolution's raw output; its table is the eval-mode BatchNorm with the convolution's bias folded in)
+ * and out[b] (2 * C_b channels).  The smallest map (hm, wm) is the last branch's, Ct = sum of C_b; tables and gates of the inputs
+ * are applied on load.
+ *   lhn_ccw_pool_fwd     pooled[N, hm, wm, Ct]: branch b's channels at their running offset = adaptive_avg_pool2d(value(x2[b]), (hm, wm))
+ *   lhn_ccw_gate_fwd     g[npix, Ct] = sigmoid(relu(t2(W2 . sigmoid(relu(t1(W1 . pooled)))))) per pooled pixel; t1 / t2: [3][t*_stride]
+ *                        eval tables (bias folded into the shift, as lhn_bn_finalize with conv_bias does) of which the first mid / Ct
+ *                        columns are read; Ct <= 320, mid <= 40, any values inside
+ *   lhn_ccw_dw_fwd       y[b] = dw3x3(value(x2[b]) * up(g_b)), stride 1, zero padding of the PRODUCT, up = nearest upsample by
+ *                        H_b / hm; every tile also writes the per-channel sum of value(y[b]) over its pixels into `scratch`
+ *   lhn_ccw_shuffle_fwd  per workgroup: folds its sample's tile sums in a fixed order to the global mean, runs the SpatialWeighting
+ *                        MLP (C_b -> J -> C_b, the arithmetic of lhn_se_mlp_fwd2 mode 1), then stores out[b][2j] = value(x1[b])[j],
+ *                        out[b][2j+1] = value(y[b])[j] * gate[n][j], plain like lhn_shuffle2_fwd.  y[b].gate is not read: the gate
+ *                        lives in the launch.
+ * No float atomics: repeated calls give identical bits.  B outside 2..4, a map that is not an integer multiple of the last one,
+ * branches not ordered from the largest map to the smallest, C_b above 160 (or J outside 1..40), an output that overlaps an input's
+ * channels in the same buffer or a missing scratch returns the invalid-argument status ("unsupported shape") before any launch and
+ * writes nothing.  Any N, any map size down to 1 x 1. */
+typedef struct lhn_ccw_se {
+  const float *w1 /*[J,C]*/, *b1 /*[J] or NULL*/, *w2 /*[C,J]*/, *b2 /*[C] or NULL*/;
+  int32_t J;
+} lhn_ccw_se;
+int64_t lhn_ccw_scratch_bytes(int N, int B, const int* H, const int* W, const int* C);   /* host-only; 0 = unsupported */
+int lhn_ccw_pool_fwd(const lhn_view* x2 /*[B]*/, int B, float* pooled, void* stream);
+int lhn_ccw_gate_fwd(const float* pooled, int64_t npix, int Ct, int mid, const float* w1 /*[mid,Ct]*/, const float* t1, int t1_stride,
+                     const float* w2 /*[Ct,mid]*/, const float* t2, int t2_stride, float* g, void* stream);
+int lhn_ccw_dw_fwd(const lhn_view* x2 /*[B]*/, int B, const float* g /*[N,hm,wm,Ct]*/, const float* const* w /*[B] of [C_b,1,3,3]*/,
+                   const lhn_view* y /*[B]*/, void* scratch, void* stream);
+int lhn_ccw_shuffle_fwd(const lhn_view* x1 /*[B]*/, const lhn_view* y /*[B]*/, int B, const lhn_ccw_se* se /*[B]*/, const void* scratch,
+                        const lhn_view* out /*[B]*/, void* stream);
 int lhn_maxpool2_fwd(const lhn_view* x, const lhn_view* y, void* stream);
 int lhn_avgpool_fwd(const lhn_view* x, float* out /*[N,OH,OW,x.C]*/, int OH, int OW, void* stream);
 /* ... into channels [out_coff, out_coff + x.C) of an [N,OH,OW,out_cstride] tensor: the pooled branches of

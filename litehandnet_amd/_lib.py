@@ -27,6 +27,11 @@ class GradView(C.Structure):
     _fields_ = [("dz", C.c_void_p), ("dpool", C.c_void_p), ("coef", C.c_void_p)]
 
 
+class CcwSe(C.Structure):
+    """lhn_ccw_se: SpatialWeighting's parameters of one branch (lhn_ccw_shuffle_fwd)."""
+    _fields_ = [("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p), ("J", C.c_int32)]
+
+
 class Op(C.Structure):
     _fields_ = [("kind", C.c_int32),
                 ("in_buf", C.c_int32 * 3), ("in_coff", C.c_int32 * 3), ("in_C", C.c_int32 * 3), ("reserved", C.c_int32 * 6),
@@ -53,6 +58,7 @@ SYMBOLS = [
     "lhn_conv_kxk_bwd", "lhn_ew_bwd", "lhn_ew_bwd2", "lhn_maxpool2_bwd", "lhn_maxpool2_bwd2", "lhn_maxpool2_bwd3", "lhn_ew_bwd3", "lhn_ew_bwd_multi", "lhn_avgpool_bwd3", "lhn_conv_pw_bwd3", "lhn_avgpool_bwd", "lhn_gate_bwd_reduce", "lhn_gate_bwd_reduce2", "lhn_gate_bwd_reduce3", "lhn_adam_step", "lhn_avgpool_fwd3", "lhn_avgpool_fwd4", "lhn_ca_mlp_bwd2",
     "lhn_ca_mlp_bwd", "lhn_reduce_replicas", "lhn_fold_stat_replicas", "lhn_plan_create", "lhn_plan_destroy", "lhn_plan_run", "lhn_plan_run_range",
     "lhn_cbam_layout", "lhn_cbam_fwd", "lhn_cbam_bwd",
+    "lhn_ccw_scratch_bytes", "lhn_ccw_pool_fwd", "lhn_ccw_gate_fwd", "lhn_ccw_dw_fwd", "lhn_ccw_shuffle_fwd",
 ]
 
 
@@ -89,6 +95,22 @@ def lib():
         # (x, w, y, wsplit, relay, stream)
         _lib.lhn_conv_kxk_fwd_bf16x3.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _lib.lhn_conv_kxk_fwd_bf16x3.restype = C.c_int
+        # (N, B, H[B], W[B], C[B]) -> bytes, 0 = unsupported; host only
+        _lib.lhn_ccw_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.lhn_ccw_scratch_bytes.restype = C.c_int64
+        # (x2[B], B, pooled, stream)
+        _lib.lhn_ccw_pool_fwd.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.lhn_ccw_pool_fwd.restype = C.c_int
+        # (pooled, npix, Ct, mid, w1, t1, t1_stride, w2, t2, t2_stride, g, stream)
+        _lib.lhn_ccw_gate_fwd.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                          C.c_void_p, C.c_void_p]
+        _lib.lhn_ccw_gate_fwd.restype = C.c_int
+        # (x2[B], B, g, w[B], y[B], scratch, stream)
+        _lib.lhn_ccw_dw_fwd.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        _lib.lhn_ccw_dw_fwd.restype = C.c_int
+        # (x1[B], y[B], B, se[B], scratch, out[B], stream)
+        _lib.lhn_ccw_shuffle_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+        _lib.lhn_ccw_shuffle_fwd.restype = C.c_int
         _lib.lhn_cbam_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _lib.lhn_cbam_layout.restype = C.c_int
         # (p, r, w1, w2, w7, out, save, stream)

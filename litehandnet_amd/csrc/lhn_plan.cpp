@@ -24,6 +24,7 @@ enum {
   OP_STEM = 1, OP_PW = 2, OP_DW = 3, OP_KXK = 4, OP_FINALIZE = 5, OP_EW = 6, OP_MAXPOOL = 7, OP_AVGPOOL = 8,
   OP_CA_MLP = 9, OP_TABLE_FILL = 10, OP_MEMSET = 11, OP_ATT_MLP = 12, OP_SE_MLP = 13, OP_SHUFFLE = 14,
   OP_PWDW = 15, OP_DWPW = 16, OP_MSRB = 17, OP_CBAM = 18, OP_BNECK = 19, OP_STEMTAIL = 20,
+  OP_CCW_POOL = 21, OP_CCW_GATE = 22, OP_CCW_DW = 23, OP_CCW_SHUFFLE = 24, OP_CCW_ARG = 25,
   OP_STEM_BWD = 101, OP_PW_BWD = 102, OP_DW_BWD = 103, OP_KXK_BWD = 104, OP_BN_BWD = 105, OP_EW_BWD = 106,
   OP_MAXPOOL_BWD = 107, OP_AVGPOOL_BWD = 108, OP_GATE_REDUCE = 109, OP_CA_MLP_BWD = 110, OP_ATT_MLP_BWD = 111, OP_SE_MLP_BWD = 112,
   OP_SHUFFLE_BWD = 113, OP_CBAM_BWD = 114,
@@ -528,6 +529,81 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
                                 &y, reinterpret_cast<float*>(at(ws, o.ws[0])), o.i[0], o.i[0], at(ws, o.ws[1]), stream);
         break;
       }
+      case OP_CCW_ARG:  // one branch of a ConditionalChannelWeighting block, read by the CCW launch behind it; launches nothing
+        break;
+      case OP_CCW_POOL:
+      case OP_CCW_DW:
+      case OP_CCW_SHUFFLE: {  // i[0] = B; the B ops in front are OP_CCW_ARG, one per branch: in[0] = x2, in[1] = x1, in[2] = y (raw depthwise
+        // output), out = the shuffled output, p = w_dw, SpatialWeighting's w1, b1, w2, b2, i[0] = its J.  POOL: out = the pooled
+        // concatenation (whole buffer); DW: in[0] = g (whole buffer), ws[0] = scratch; SHUFFLE: ws[0] = scratch.  Inference plans only.
+        if (training) {
+          lhn_set_error("lhn_plan_run: a grouped channel-weighting launch has no batch statistics (inference plans only)");
+          rc = 1;
+          break;
+        }
+        const int B = o.i[0];
+        if (B < 2 || B > 4 || oi < (size_t)B) {
+          lhn_set_error("lhn_plan_run: channel-weighting op at index %zu: %d branches", oi, B);
+          rc = 1;
+          break;
+        }
+        lhn_view x2[4], x1[4], y[4], out[4];
+        const float* w[4];
+        lhn_ccw_se se[4];
+        for (int b = 0; b < B && rc == 0; ++b) {
+          const lhn_op& g = ops[oi - B + b];
+          if (g.kind != OP_CCW_ARG || g.in_buf[0] < 0 || g.in_buf[1] < 0 || g.in_buf[2] < 0 || g.out_buf < 0) {
+            lhn_set_error("lhn_plan_run: channel-weighting op at index %zu: branch %d is not described", oi, b);
+            rc = 1;
+            break;
+          }
+          x2[b] = mkview(P, ws, g.in_buf[0], g.in_coff[0], g.in_C[0]);
+          x1[b] = mkview(P, ws, g.in_buf[1], g.in_coff[1], g.in_C[1]);
+          y[b] = mkview(P, ws, g.in_buf[2], g.in_coff[2], g.in_C[2], false);      // (its gate lives in the shuffle launch)
+          out[b] = mkview(P, ws, g.out_buf, g.out_coff, g.out_C);
+          w[b] = prm<const float>(params, g.p[0]);
+          se[b].w1 = prm<const float>(params, g.p[1]); se[b].b1 = prm<const float>(params, g.p[2]);
+          se[b].w2 = prm<const float>(params, g.p[3]); se[b].b2 = prm<const float>(params, g.p[4]);
+          se[b].J = g.i[0];
+        }
+        if (rc) break;
+        if ((o.kind == OP_CCW_POOL && o.out_buf < 0) || (o.kind == OP_CCW_DW && o.in_buf[0] < 0)) {
+          lhn_set_error("lhn_plan_run: channel-weighting op at index %zu: missing buffer", oi);
+          rc = 1;
+          break;
+        }
+        if (o.kind == OP_CCW_POOL)
+          rc = lhn_ccw_pool_fwd(x2, B, reinterpret_cast<float*>(at(ws, P->bufs[o.out_buf].data_off)), stream);
+        else if (o.kind == OP_CCW_DW)
+          rc = lhn_ccw_dw_fwd(x2, B, reinterpret_cast<const float*>(at(ws, P->bufs[o.in_buf[0]].data_off)), w, y, at(ws, o.ws[0]), stream);
+        else
+          rc = lhn_ccw_shuffle_fwd(x1, y, B, se, at(ws, o.ws[0]), out, stream);
+        break;
+      }
+      case OP_CCW_GATE: {  // in[0] = pooled (whole buffer), in[1] / in[2] = the outputs of the two 1x1 convolutions (only their tables exist:
+        // eval BatchNorm with the bias folded in), out = g (whole buffer); p = W1, W2; i[0] = mid.  Inference plans only.
+        if (training) {
+          lhn_set_error("lhn_plan_run: a grouped channel-weighting launch has no batch statistics (inference plans only)");
+          rc = 1;
+          break;
+        }
+        if (o.in_buf[0] < 0 || o.in_buf[1] < 0 || o.in_buf[2] < 0 || o.out_buf < 0) {
+          lhn_set_error("lhn_plan_run: channel-weighting gate at index %zu: missing buffer", oi);
+          rc = 1;
+          break;
+        }
+        const lhn_buf &pb = P->bufs[o.in_buf[0]], &b1 = P->bufs[o.in_buf[1]], &b2 = P->bufs[o.in_buf[2]], &gb = P->bufs[o.out_buf];
+        if (gb.C != pb.C || gb.H != pb.H || gb.W != pb.W) {
+          lhn_set_error("lhn_plan_run: channel-weighting gate at index %zu: pooled and g differ", oi);
+          rc = 1;
+          break;
+        }
+        rc = lhn_ccw_gate_fwd(reinterpret_cast<const float*>(at(ws, pb.data_off)), (int64_t)pb.N * pb.H * pb.W, pb.C, o.i[0],
+                              prm<const float>(params, o.p[0]), reinterpret_cast<const float*>(at(ws, b1.table_off)), b1.C,
+                              prm<const float>(params, o.p[1]), reinterpret_cast<const float*>(at(ws, b2.table_off)), b2.C,
+                              reinterpret_cast<float*>(at(ws, gb.data_off)), stream);
+        break;
+      }
       case OP_FINALIZE: {
         if (skip_tables) break;
         const lhn_buf& b = P->bufs[o.out_buf];
@@ -537,7 +613,7 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
                              prm<const float>(params, o.p[1]), prm<float>(params, o.p[2]), prm<float>(params, o.p[3]),
                              prm<int64_t>(params, o.p[4]), reinterpret_cast<float*>(at(ws, b.table_off)), b.C, o.out_coff,
                              o.out_C, reinterpret_cast<float*>(at(ws, o.ws[1])), (double)sb.N * sb.H * sb.W, o.f[0], o.f[1],
-                             o.f[2], training, nullptr, stream);
+                             o.f[2], training, prm<const float>(params, o.p[5]), stream);      // p[5]: bias of the convolution in front, or -1
         break;
       }
       case OP_EW: {

@@ -10,7 +10,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .plan import CompiledPlan, PlanBuilder, infer_bf16x3_enabled, infer_fuse_bneck_enabled, infer_fuse_stem_enabled, infer_fuse_dwpw_enabled, infer_fuse_enabled, infer_fuse_msrb_enabled
+from .plan import CompiledPlan, PlanBuilder, infer_bf16x3_enabled, infer_fuse_bneck_enabled, infer_fuse_ccw_enabled, infer_fuse_stem_enabled, infer_fuse_dwpw_enabled, infer_fuse_enabled, infer_fuse_msrb_enabled
 
 
 class PlanModule(nn.Module):
@@ -214,8 +214,10 @@ class Engine:
         fuse_bneck = bool(infer_fuse_bneck_enabled() and not with_backward and (deployed or not self.module.training))
         bf16x3 = bool(infer_bf16x3_enabled() and not with_backward and (deployed or not self.module.training))   # plan.set_infer_bf16x3
         fuse_stem = bool(infer_fuse_stem_enabled() and not with_backward and (deployed or not self.module.training))
+        fuse_ccw = bool(infer_fuse_ccw_enabled() and not with_backward and (deployed or not self.module.training))   # plan.set_infer_fuse_ccw / LHN_INFER_FUSE_CCW
         # (fuse stays last, fuse_dwpw before it, fuse_msrb before that: callers index the key from its end; fuse_stem stands ahead of bf16x3)
         key = (tuple(x.shape), bool(with_backward), float(p_drop), x.device.index, fuse_stem, bf16x3, fuse_bneck, fuse_msrb, fuse_dwpw, fuse)
+        key = key[:4] + (fuse_ccw,) + key[4:]      # ... and fuse_ccw ahead of fuse_stem: k[-1] .. k[-6] keep their meaning, k[-7] is the new flag
         plan = self.plans.get(key)
         tensors = self._state(x.device)
         if plan is not None and len(plan.state_tensors) == len(tensors) and all(
@@ -225,7 +227,7 @@ class Engine:
         self._ensure_grads(tensors, x.device)
         index = {id(t): j for j, t in enumerate(tensors)}
         pb = PlanBuilder(N, index, image_hw=(H, W), with_backward=with_backward, p_drop=p_drop, infer_fuse=fuse, infer_fuse_dwpw=fuse_dwpw,
-                         infer_fuse_msrb=fuse_msrb, infer_fuse_bneck=fuse_bneck, infer_bf16x3=bf16x3, infer_fuse_stem=fuse_stem)
+                         infer_fuse_msrb=fuse_msrb, infer_fuse_bneck=fuse_bneck, infer_bf16x3=bf16x3, infer_fuse_stem=fuse_stem, infer_fuse_ccw=fuse_ccw)
         if self.full:
             if Cc != 3:
                 raise _lib.LhnError("the backbone consumes a 3-channel image")

@@ -34,6 +34,9 @@ BNECK = 19             # inference plans only: BottleNeck (1x1 -> 3x3 -> 1x1 + r
                        # see PlanBuilder.fuse_bottleneck
 STEMTAIL = 20          # inference plans only: the stem after its first convolution (depthwise K x K, 1x1, 3x3 stride 2, max pool, 1x1) in one
                        # launch (lhn_stem_tail_fwd), see PlanBuilder.fuse_stem
+CCW_POOL, CCW_GATE, CCW_DW, CCW_SHUFFLE = 21, 22, 23, 24   # inference plans only: a ConditionalChannelWeighting block of Lite-HRNet as four launches, each
+                       # over all 2..4 branches (lhn_ccw_pool_fwd / _gate_fwd / _dw_fwd / _shuffle_fwd), see PlanBuilder.fuse_ccw
+CCW_ARG = 25           # ... and the description of one branch (views and parameters) in front of the launches that read it: launches nothing
 STEM_BWD, PW_BWD, DW_BWD, KXK_BWD, BN_BWD, EW_BWD, MAXPOOL_BWD, AVGPOOL_BWD, GATE_REDUCE, CA_MLP_BWD, ATT_MLP_BWD, SE_MLP_BWD, SHUFFLE_BWD = range(101, 114)
 CBAM_BWD = 114
 SLOPE_SILU = 2.0       # LHN_SLOPE_SILU in include/lhn.h: the combine applies SiLU instead of a leaky ReLU
@@ -69,7 +72,7 @@ def _switch(name):
 # (PlanBuilder attribute and keyword, environment variable, pass method, counter attribute, what the pass does).  Every one is off
 # unless NAME=1 is in the environment or its set_* function below switched it on in the process.  PlanBuilder's keywords differ in
 # their defaults, and tests rely on it: infer_fuse, infer_fuse_dwpw and infer_fuse_msrb default to None = follow the process switch,
-# infer_fuse_bneck, infer_bf16x3 and infer_fuse_stem to False (Engine.plan_for passes all six).
+# infer_fuse_bneck, infer_bf16x3, infer_fuse_stem and infer_fuse_ccw to False (Engine.plan_for passes all seven).
 INFER_SWITCHES = (
     ("infer_fuse_stem", "LHN_INFER_FUSE_STEM", "fuse_stem", "n_fused_stem", "the stem after its first convolution is one launch"),
     ("infer_fuse_msrb", "LHN_INFER_FUSE_MSRB", "fuse_msrb_round", "n_fused_msrb", "an MSRB round and its attention's pooling are one pass"),
@@ -77,6 +80,7 @@ INFER_SWITCHES = (
     ("infer_fuse", "LHN_INFER_FUSE", "fuse_pw_dw", "n_fused", "RepBasicUnit's 1x1 -> depthwise 3x3 is one launch"),
     ("infer_fuse_bneck", "LHN_INFER_FUSE_BNECK", "fuse_bottleneck", "n_fused_bneck", "a BottleNeck is one launch"),
     ("infer_bf16x3", "LHN_INFER_BF16X3", "mark_bf16x3", "n_bf16x3", "dense 3x3 convolutions run on the split-bf16 MFMA"),
+    ("infer_fuse_ccw", "LHN_INFER_FUSE_CCW", "fuse_ccw", "n_fused_ccw", "a Lite-HRNet channel-weighting block is four grouped launches"),
 )
 _INFER_ENV = {row[0]: row[1] for row in INFER_SWITCHES}
 _INFER_OVERRIDE = {}       # switch name -> bool: what _set_infer_switch put in front of the environment
@@ -157,6 +161,17 @@ def infer_bf16x3_enabled():
     """LHN_INFER_BF16X3=1 (default off): plans without a backward run their stride-1 dense 3x3 convolutions with 32 / 64 / 128
     channels on the bf16 MFMA with a three-term split (lhn_conv_kxk_fwd_bf16x3) instead of the fp32 MFMA."""
     return _infer_switch("infer_bf16x3")
+
+
+def set_infer_fuse_ccw(on):
+    """_set_infer_switch for the ConditionalChannelWeighting inference pass (PlanBuilder.fuse_ccw)."""
+    _set_infer_switch("infer_fuse_ccw", on)
+
+
+def infer_fuse_ccw_enabled():
+    """LHN_INFER_FUSE_CCW=1 (default off): plans without a backward run each ConditionalChannelWeighting block of Lite-HRNet -- 22 / 28
+    launches over 3 / 4 branches -- as four launches, each over all branches (PlanBuilder.FUSE_CCW_BRANCHES: two-branch blocks stay)."""
+    return _infer_switch("infer_fuse_ccw")
 
 
 # What lhn_conv_kxk_fwd_bf16x3 is built for (csrc/k_conv_kxk_bf16.hip: kxk_bf16x3_channels and the checks of the entry point) ...
@@ -297,7 +312,7 @@ class PlanBuilder:
     _no_grad_buf = -1   # the image never needs a gradient
 
     def __init__(self, N, state_index, image_hw=None, with_backward=True, p_drop=0.0, infer_fuse=None, infer_fuse_dwpw=None,
-                 infer_fuse_msrb=None, infer_fuse_bneck=False, infer_bf16x3=False, infer_fuse_stem=False):
+                 infer_fuse_msrb=None, infer_fuse_bneck=False, infer_bf16x3=False, infer_fuse_stem=False, infer_fuse_ccw=False):
         self.N = N
         # The inference switches (INFER_SWITCHES): None = the process-wide switch.  The rewritten launches have no batch statistics,
         # so the caller passes False for a plan that will run train-mode BatchNorm under no_grad (Engine.plan_for).
@@ -856,10 +871,15 @@ class PlanBuilder:
         return not _biased_bn(q)
 
     @staticmethod
-    def _tables(q, fill=False):
+    def _tables(q, fill=False, bias=False):
         """The records that fill the table of convolution record q's output without q: FINALIZE when q has a BatchNorm; else, with `fill`,
         a TABLE_FILL for its pending bias / activation.  fuse_pw_dw and fuse_msrb_round drop the original TABLE_FILL and emit this one
-        ahead of their launch; the other passes leave the original where it stands and ask for none."""
+        ahead of their launch; the other passes leave the original where it stands and ask for none.  `bias` (fuse_ccw): the FINALIZE
+        folds a bias in front of the BatchNorm into the shift, as the unfused convolution's own finalize does, and covers the
+        BatchNorm's channels only (a 7 / 17 / 37-wide one sits in a view padded to a multiple of 4)."""
+        if q["bn"] is not None and bias:
+            t = q["out"]
+            return [dict(op=FINALIZE, out=TRef(t.buf, t.coff, q["bn"].num_features, t.H, t.W), bn=q["bn"], slope=q["slope"], bias=q["conv"].bias)]
         if q["bn"] is not None:
             return [dict(op=FINALIZE, out=q["out"], bn=q["bn"], slope=q["slope"])]
         if fill and (q["conv"].bias is not None or q["slope"] != 1.0):
@@ -1231,6 +1251,152 @@ class PlanBuilder:
         self.n_bf16x3 += n
         return n
 
+    # What the lhn_ccw_* entry points are built for (csrc/k_hrnet.hip: CCW_MAX_C, CCW_MAX_CT, CCW_MAX_MID), and the numbers of branches the
+    # pass rewrites.  The entry points take 2..4; the two-branch blocks (stage 2: the largest maps, 12 launches saved per block) did not
+    # pass the keep-or-drop rule on their own and are left as they are (profiles/infer_fuse_ccw.md).
+    FUSE_CCW_MAX = (160, 320, 40)
+    FUSE_CCW_BRANCHES = (3, 4)
+
+    def _sole_act(self, r, uses):
+        """The sigmoid(relu(.)) combine that is the only reader of the 1x1 record r's output, or None."""
+        e = self._sole_reader(r["out"], r, uses, EW)
+        if e is None or e.get("mode") or e.get("coefs") is not None or e.get("lazy") or "flat" in e or len(e["srcs"]) != 1:
+            return None
+        t, y = e["srcs"][0], e["out"]
+        if e["slope"] != SLOPE_RELU_SIGMOID or isinstance(t, TCat) or (t.buf, t.coff, t.C) != (r["out"].buf, 0, r["out"].C):
+            return None
+        return e if self._whole_fresh(y, t.C) and (y.H, y.W) == (t.H, t.W) else None
+
+    def _ccw_pw(self, r):
+        """True when r is one of CrossResolutionWeighting's 1x1 convolutions: stride 1, one plain source, a BatchNorm (a bias in front
+        of it is fine, and so is a 7 / 17 / 37-wide side padded to a multiple of 4) and no activation of its own."""
+        return r is not None and r["op"] == PW and r["stride"] == 1 and not r["nchw"] and r["bn_repeat"] == 1 and self._xs(r)[1] == 1 and \
+            r["bn"] is not None and r["slope"] == 1.0 and not isinstance(r["x"], TCat) and r["x"].buf >= 0
+
+    def _fusable_ccw(self, r1, uses):
+        """The records of the ConditionalChannelWeighting block (lite_hrnet.py:76-143) whose first 1x1 is r1, or None.  The pattern: B =
+        2..4 adaptive average pools to one (hm, wm) that tile a whole fresh buffer; r1 (Ct -> mid, BatchNorm) over all of it, a
+        sigmoid(relu(.)) combine, a second 1x1 (mid -> Ct, BatchNorm) and its combine into g; per branch a product of the pooled view
+        with its slice of g, a 3x3 depthwise convolution + BatchNorm of that product into a buffer of its own, a SpatialWeighting gate
+        (SE_MLP mode 1) on that buffer and a SHUFFLE of it behind a view like the pooled one -- each intermediate with that one reader.
+        Maps ordered from the largest to the smallest and integer multiples of the last."""
+        cmax, ctmax, midmax = self.FUSE_CCW_MAX
+        if not self._ccw_pw(r1):
+            return None
+        P = r1["x"]
+        if not self._whole_fresh(P, P.C) or P.C > ctmax:
+            return None
+        pools = []
+        for u, key in uses.get(P.buf, ()):
+            if u["op"] == AVGPOOL and key == "out" and not u["ca"] and (u["OH"], u["OW"]) == (P.H, P.W):
+                pools.append(u)
+            elif not (u is r1 and key == "x"):
+                return None
+        pools.sort(key=lambda u: u["out"].coff)
+        B, off = len(pools), 0
+        if B not in self.FUSE_CCW_BRANCHES:
+            return None
+        for u in pools:
+            x = u["x"]
+            if isinstance(x, TCat) or x.buf < 0 or (u["out"].coff, u["out"].C) != (off, x.C) or x.C > cmax or x.H % P.H or x.W % P.W:
+                return None
+            off += x.C
+        if off != P.C or any(a["x"].H < b["x"].H or a["x"].W < b["x"].W for a, b in zip(pools, pools[1:])) or \
+                (pools[-1]["x"].H, pools[-1]["x"].W) != (P.H, P.W):
+            return None
+        mid = r1["conv"].weight.shape[0]
+        e1 = self._sole_act(r1, uses)
+        if e1 is None or mid > midmax or r1["bn"].num_features != mid or r1["conv"].weight.shape[1] != P.C:
+            return None
+        r2 = self._sole_reader(e1["out"], e1, uses, PW)
+        if not self._ccw_pw(r2) or tuple(r2["conv"].weight.shape[:2]) != (P.C, mid) or r2["out"].C != P.C or r2["bn"].num_features != P.C:
+            return None
+        e2 = self._sole_act(r2, uses)
+        if e2 is None or len({P.buf, r1["out"].buf, e1["out"].buf, r2["out"].buf, e2["out"].buf}) != 5:
+            return None
+        g = e2["out"]
+        muls = [u for u, key in uses.get(g.buf, ()) if not (u is e2 and key == "out")]
+        if len(muls) != B or len({id(u) for u in muls}) != B:
+            return None
+        branches, off = [], 0
+        for pool in pools:
+            x2 = pool["x"]
+            m = next((u for u in muls if u["op"] == EW and u.get("mode") == EW_MUL and len(u["srcs"]) == 2 and
+                      not isinstance(u["srcs"][1], TCat) and (u["srcs"][1].buf, u["srcs"][1].coff, u["srcs"][1].C) == (g.buf, off, x2.C)), None)
+            off += x2.C
+            if m is None or m.get("coefs") is not None or m["slope"] != 1.0 or m["srcs"][0] != x2:
+                return None
+            dw = self._sole_reader(m["out"], m, uses, DW)
+            if dw is None or (dw["k"], dw["stride"], dw["pad"], dw["dil"]) != (3, 1, 1, 1) or dw["conv"].weight is None or dw["bn"] is None or \
+                    dw["slope"] != 1.0 or dw.get("bn_repeat", 1) != 1 or self._xs(dw)[1] != 1 or (dw["x"].coff, dw["x"].C) != (0, x2.C):
+                return None
+            y = dw["out"]
+            if isinstance(y, TCat) or y.buf < 0 or (y.coff, y.C) != (0, x2.C) or self.bufs[y.buf].C != x2.C or \
+                    any(v is not None and v.buf == y.buf for v in (self.in_ref, self.out_ref)):
+                return None
+            se = sh = None
+            for u, key in uses.get(y.buf, ()):
+                if u is dw and key == "out":
+                    continue
+                if u["op"] == SE_MLP and key == "y" and se is None:
+                    se = u
+                elif u["op"] == SHUFFLE and key == "b" and sh is None:
+                    sh = u
+                else:
+                    return None
+            if se is None or sh is None or se["mode"] != 1 or se.get("pool_fused") or not 1 <= se["J"] <= midmax:
+                return None
+            x1, out = sh["a"], sh["out"]
+            if isinstance(x1, TCat) or x1.buf < 0 or (x1.H, x1.W, x1.C) != (x2.H, x2.W, x2.C) or sh["b"] != y or not self._whole_fresh(out, 2 * x2.C):
+                return None
+            if out.buf in (x1.buf, x2.buf, y.buf) or y.buf in (x1.buf, x2.buf, g.buf, P.buf):
+                return None
+            branches.append(dict(pool=pool, mul=m, dw=dw, se=se, sh=sh, x2=x2, x1=x1, y=y, out=out))
+        return dict(r1=r1, e1=e1, r2=r2, e2=e2, mid=mid, pooled=P, g=g, branches=branches)
+
+    def fuse_ccw(self):
+        """Inference plans with the switch on (infer_fuse_ccw): a ConditionalChannelWeighting block of Lite-HRNet (lite_hrnet.py:110-143)
+        -- per branch a pool into the concatenation, a product with the upsampled gate, a depthwise 3x3, SpatialWeighting's pool and MLP
+        and a channel shuffle, and the two 1x1 + activation pairs they share: 16 / 22 / 28 launches over 2 / 3 / 4 branches -- becomes
+        FOUR records, each one launch over all branches: CCW_POOL, CCW_GATE, CCW_DW (which also leaves the per-tile sums SpatialWeighting
+        pools from) and CCW_SHUFFLE (which folds them, runs the MLP and applies the gate while shuffling).  The pass matches the record
+        pattern of _fusable_ccw, not the module class.  The buffers between the steps that the launches keep in registers -- both 1x1
+        outputs, the first activation and the products -- keep their tables and lose their data.  The tables the launches read (both
+        1x1 BatchNorms and the depthwise ones, biases folded in) are emitted ahead of them by what fills them without the convolution
+        (_tables), under LHN_RUN_TABLES_CURRENT like every other table launch.  The records stand where the last shuffle stood.  A block
+        whose maps are not integer multiples of its smallest one stays as it is, and so does one whose number of branches is not in
+        FUSE_CCW_BRANCHES.  Plans with a backward are never rewritten."""
+        if self.with_backward or not self.infer_fuse_ccw:
+            return 0
+        uses = self._uses()
+        order = {id(r): j for j, r in enumerate(self.recs)}
+        at, drop = {}, set()
+        for r1 in self.recs:
+            m = self._fusable_ccw(r1, uses)
+            if m is None:
+                continue
+            br = m["branches"]
+            nbytes = _lib.lib().lhn_ccw_scratch_bytes(self.N, len(br), *((C.c_int * len(br))(*[getattr(b["x2"], k) for b in br]) for k in "HWC"))
+            if nbytes <= 0:
+                continue
+            scratch = self._ws("misc", nbytes)
+            x2, x1, ys, outs = ([b[k] for b in br] for k in ("x2", "x1", "y", "out"))
+            args = dict(x2=x2, x1=x1, ys=ys, outs=outs, dws=[b["dw"]["conv"] for b in br], ses=[(b["se"]["down"], b["se"]["up"], b["se"]["J"]) for b in br])
+            fused = [dict(op=CCW_POOL, out=m["pooled"], **args),
+                     dict(op=CCW_GATE, x=m["pooled"], mids=[m["r1"]["out"], m["r2"]["out"]], out=m["g"], conv=m["r1"]["conv"], conv2=m["r2"]["conv"],
+                          mid=m["mid"]),
+                     dict(op=CCW_DW, g=m["g"], scratch=scratch, **args),
+                     dict(op=CCW_SHUFFLE, scratch=scratch, **args)]
+            old = [m["r1"], m["e1"], m["r2"], m["e2"]] + [b[k] for b in br for k in ("pool", "mul", "dw", "se", "sh")]
+            last = max(old, key=lambda u: order[id(u)])
+            at[id(last)] = [t for q in [m["r1"], m["r2"]] + [b["dw"] for b in br] for t in self._tables(q, bias=True)] + fused
+            drop |= {id(u) for u in old}
+            for t in [m["r1"]["out"], m["e1"]["out"], m["r2"]["out"]] + [b["mul"]["out"] for b in br]:
+                self.bufs[t.buf].fused = True
+        n = self._splice(at, drop)
+        self.n_fused_ccw += n
+        return n
+
     # ------------------------------------------------------------------ finalize: the passes in the order they run
     def finalize(self):
         """Lower the records to what lhn_plan_create takes: (Buf array, forward Op array, backward Op array or None, n_fwd, n_bwd)."""
@@ -1275,6 +1441,7 @@ class PlanBuilder:
     def _lower_forward(self):
         emit = {STEM: self._fwd_conv, PW: self._fwd_conv, DW: self._fwd_conv, KXK: self._fwd_conv, PWDW: self._fwd_pwdw, DWPW: self._fwd_dwpw,
                 MSRB: self._fwd_msrb, BNECK: self._fwd_bneck, STEMTAIL: self._fwd_stemtail,
+                CCW_POOL: self._fwd_ccw, CCW_GATE: self._fwd_ccw, CCW_DW: self._fwd_ccw, CCW_SHUFFLE: self._fwd_ccw,
                 FINALIZE: self._fwd_table, TABLE_FILL: self._fwd_table, EW: self._fwd_ew, SHUFFLE: self._fwd_pool,
                 MAXPOOL: self._fwd_pool, AVGPOOL: self._fwd_pool, CA_MLP: self._fwd_ca, SE_MLP: self._fwd_se, ATT_MLP: self._fwd_att,
                 CBAM: self._fwd_cbam}
@@ -1344,12 +1511,30 @@ class PlanBuilder:
                          p=(self._p(r["conv"].weight), self._p(r["conv2"].weight)), ws=(self._abs(r["pooled"]), self._abs(r["scratch"])),
                          i=(r["OH"],) + e1 + (0, 0, 2 if two else 1), f=(0.0, 0.0, 0.0, 0.0) + tuple(r["coefs"]))]
 
+    def _fwd_ccw(self, r):
+        """CCW_GATE: in = pooled, the two 1x1 outputs (tables only), out = g, p = W1, W2, i[0] = mid.  The other three stand behind one
+        CCW_ARG op per branch (an op has three input slots and twelve parameters: a block has up to 16 views and 20): in = x2, x1, y,
+        out = the shuffled output, p = w_dw, SpatialWeighting's w1, b1, w2, b2, i[0] = its J.  i[0] = B; CCW_POOL: out = pooled;
+        CCW_DW: in[0] = g, ws[0] = scratch; CCW_SHUFFLE: ws[0] = scratch."""
+        mk = self._mk
+        if r["op"] == CCW_GATE:
+            return [mk(CCW_GATE, ins=[r["x"]] + r["mids"], out=r["out"], p=(self._p(r["conv"].weight), self._p(r["conv2"].weight)), i=(r["mid"],))]
+        args = [mk(CCW_ARG, ins=(x2, x1, y), out=o, p=(self._p(dw.weight),) + tuple(self._p(t) for t in (dn.weight, dn.bias, up.weight, up.bias)), i=(J,))
+                for x2, x1, y, o, dw, (dn, up, J) in zip(r["x2"], r["x1"], r["ys"], r["outs"], r["dws"], r["ses"])]
+        B = len(args)
+        if r["op"] == CCW_POOL:
+            return args + [mk(CCW_POOL, out=r["out"], i=(B,))]
+        if r["op"] == CCW_DW:
+            return args + [mk(CCW_DW, ins=(r["g"],), ws=(self._abs(r["scratch"]),), i=(B,))]
+        return args + [mk(CCW_SHUFFLE, ws=(self._abs(r["scratch"]),), i=(B,))]
+
     def _fwd_table(self, r):
         """FINALIZE: eval-mode table of a convolution that runs inside a PWDW / DWPW / MSRB launch (no statistics to fold); TABLE_FILL: the
         pending bias / activation of a BatchNorm-free convolution."""
         if r["op"] == FINALIZE:
             bn = r["bn"]
-            return [self._mk(FINALIZE, out=r["out"], p=self._p_bn(bn), f=(bn.eps, bn.momentum, r["slope"]))]
+            cb = (self._p(r["bias"]),) if r.get("bias") is not None else ()      # p[5]: a convolution bias folded into the shift (fuse_ccw)
+            return [self._mk(FINALIZE, out=r["out"], p=self._p_bn(bn) + cb, f=(bn.eps, bn.momentum, r["slope"]))]
         return [self._mk(TABLE_FILL, out=r["out"], p=(self._p(r["bias"]),), i=(1,), f=(1.0, 0.0, r["slope"]))]
 
     def _fwd_ew(self, r):
