@@ -601,14 +601,14 @@ int lhn_avgpool_bwd3(const lhn_view* x, const float* dout, int OH, int OW, int o
                      int dx_accumulate, const lhn_bnsum* bns, void* stream);
 int lhn_conv_pw_bwd3(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate,
                      float* dw, float* dbias, int stride, const float* dy_nchw, int nrep, int64_t rep_stride,
-                     const lhn_pw_opts* opts, const lhn_bnsum* bns /*fused kernel only: Cin * Cout < 64 * 128, stride 1*/, void* stream);
+                     const lhn_pw_opts* opts, const lhn_bnsum* bns /*or NULL; stride 1, and a shape lhn_conv_pw_route has a kernel for*/, void* stream);
 /* The two backward calls above with the BatchNorm-backward finalize of y taken in the kernel's prologue (lhn_bnbwdsrc; fin NULL =
  * the calls above).  gy->coef must point at the coefficient table: it is written.  lhn_conv_dw_bwd4 takes everything a depthwise
  * backward may carry: bns (the producer's sums of lhn_conv_dw_bwd2, x's first channel at bns->coff; NULL or bns->sums NULL: none),
  * the addends of lhn_conv_dw_bwd3, and fin; bns and addends exclude each other.
  * In-prologue fold: k_dw3_bwd_rows (3x3, stride 1, "same" padding, W >= 8; dilation 1 on maps of at most 256 pixels: the tile kernel
- * k_dwk_bwd_lds, same fold, LHN_DW_BWD_SMALL=0 keeps the row kernel) and k_pw_bwd_wr (the shapes listed at lhn_conv_pw_bwd3's
- * register-W dispatch); every other kernel gets a lhn_bn_bwd_finalize2 launch in front, from this call. */
+ * k_dwk_bwd_lds, same fold, LHN_DW_BWD_SMALL=0 keeps the row kernel) and k_pw_bwd_wr; every other kernel gets a lhn_bn_bwd_finalize2
+ * launch in front, from this call (lhn_conv_dw_route / lhn_conv_pw_route name it where it is issued). */
 int lhn_conv_dw_bwd4(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate,
                      float* dw, int k, int stride, int pad, int dil, int nrep, int64_t rep_stride, const lhn_bnsum* bns,
                      const float* dx_add0, const float* dx_add1, const lhn_bnbwdsrc* fin, void* stream);
@@ -632,6 +632,38 @@ const char* lhn_conv_dw_route(int backward, int H, int W, int C, int k, int stri
 int lhn_conv_pw_bwd4(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate,
                      float* dw, float* dbias, int stride, const float* dy_nchw, int nrep, int64_t rep_stride,
                      const lhn_pw_opts* opts, const lhn_bnsum* bns, const lhn_bnbwdsrc* fin, void* stream);
+/* Which kernels lhn_conv_pw_fwd2 (backward = 0) / lhn_conv_pw_bwd6 (backward = 1) launch for this shape and feature set, in order:
+ * host-only (no device needed, nothing is launched), answered by the two functions the calls themselves ask (pw_fwd_route /
+ * pw_bwd_route, csrc/k_conv_pw.hip).  N, H, W are x's; w_rows / w_cols: lhn_pw_opts' fields, 0 = Cout / Cin.  features: what the call
+ * carries.  switches: -1 = as this process read them from the environment, else a set of LHN_PW_SW_* bits.
+ * Returns a static string (per thread, valid until the next call): the template instances as a kernel trace prints them, joined
+ * with " + ", " x n" behind a launch that repeats ("k_dy_inplace + k_pw_fwd_wr<256, 4, 1> x 2 + k_kxk_wgrad<128, 4, 1, true> x 2"),
+ * with "lhn_bn_bwd_finalize2 + " in front, " + lhn_bn_finalize" or " + lhn_gate_bwd_reduce3" behind where the call issues that launch
+ * itself; profiles/pw_instances.md is printed from it.  NULL: no kernel exists for the combination (the call is refused before any
+ * launch), or the stride is not 1 or 2.  Other arguments a call would refuse for another reason are not checked. */
+#define LHN_PW_F_NCHW      1     /* y_nchw / dy_nchw */
+#define LHN_PW_F_STATS     2     /* forward: BatchNorm statistics */
+#define LHN_PW_F_FUSE_FIN  4     /* forward: a fused finalize is asked for (lhn_bnfin) */
+#define LHN_PW_F_EXTRA1    8     /* forward: one summed-on-load source */
+#define LHN_PW_F_EXTRA2    16    /* forward: two */
+#define LHN_PW_F_SUM_OUT   32    /* forward: sum_out */
+#define LHN_PW_F_BNSUM     64    /* backward: reader-side BatchNorm sums (lhn_bnsum) */
+#define LHN_PW_F_FIN       128   /* backward: a finalize source (lhn_bnbwdsrc) */
+#define LHN_PW_F_GATESUM   256   /* backward: gate sums (lhn_gatesum) */
+#define LHN_PW_F_NO_DX     512   /* backward: dx NULL */
+#define LHN_PW_F_DX_ACC    1024  /* backward: dx accumulated (part of the call's description; no rule of the route reads it today) */
+#define LHN_PW_F_DZ_DEAD   2048  /* backward: LHN_PW_BWD_DZ_DEAD */
+#define LHN_PW_F_UNALIGNED 4096  /* a pointer the vector paths need at 16 bytes is not (forward: w, y_nchw; backward: dy_nchw, x's data),
+                                    or the NCHW batch stride is no multiple of 4 floats */
+#define LHN_PW_F_DBIAS     8192  /* backward: dbias given (an NCHW gradient's bias sums are a launch of their own on k_pw_bwd) */
+#define LHN_PW_SW_LDSW          1   /* LHN_PW_LDSW=1 */
+#define LHN_PW_SW_K256          2   /* K = 256 in one pass: set unless LHN_PW_K256=0 */
+#define LHN_PW_SW_BWD_NARROW    4   /* the narrow register-W backward: set unless LHN_PW_BWD_NARROW=0 */
+#define LHN_PW_SW_BWD_SPLIT     8   /* LHN_PW_BWD_SPLIT=1 */
+#define LHN_PW_SW_HEAD_STREAM   16  /* the streaming head kernels: set unless LHN_HEAD_STREAM=0 */
+#define LHN_PW_SW_DETERMINISTIC 32  /* LHN_DETERMINISTIC=1 */
+const char* lhn_conv_pw_route(int backward, int N, int H, int W, int Cin, int Cout, int stride, int w_rows, int w_cols, int features,
+                              int switches);
 int lhn_avgpool_bwd(const lhn_view* x, const float* dout /*[N,OH,OW,C]*/, int OH, int OW, float* dx,
                     int dx_accumulate, void* stream);
 int lhn_gate_bwd_reduce(const lhn_view* y, const float* dz, float* dgate /*[N][C] dense*/, void* stream);
@@ -663,10 +695,9 @@ int lhn_gate_bwd_reduce3(const lhn_view* y, const float* dz, float* dgate, float
  * their index in the buffer; mean | invstd by the lhn_bn_slices rule, channels outside every slice use 0 and 1).  The buffers must be
  * zero before the call (the plan keeps them in the arena its backward zeroes).  The sums are those of the buffer only when this call's
  * dx is its whole gradient (no other reader); dx must be STORED: gs with dx_accumulate != 0 is refused.
- * lhn_conv_pw_bwd5 = lhn_conv_pw_bwd4 + gs (NULL: no sums).  The streaming head kernel (k_head_bwd: Cin = 128 whole weight rows,
- * Cout <= 32, stride 1, dy_nchw, H*W % 64 == 0) adds them in its own launch; for every other shape, under LHN_HEAD_STREAM=0 and in
- * deterministic mode the call runs the present kernels and then the lhn_gate_bwd_reduce3 launch itself (x must then be the whole
- * buffer): the result never depends on the kernel chosen. */
+ * lhn_conv_pw_bwd5 = lhn_conv_pw_bwd4 + gs (NULL: no sums).  The streaming head kernel k_head_bwd adds them in its own launch; where
+ * it does not run (lhn_conv_pw_route: " + lhn_gate_bwd_reduce3") the call issues the lhn_gate_bwd_reduce3 launch itself behind its
+ * kernels (x must then be the whole buffer): the result never depends on the kernel chosen. */
 typedef struct lhn_gatesum {
   float*               dgate;    /* [3][N][cstride]: dgate | T0,T1 interleaved per image as [N][2][cstride] */
   const lhn_bn_slices* slices;   /* saved statistics of the buffer's BatchNorm slices (sums unused), or NULL */
@@ -676,11 +707,11 @@ int lhn_conv_pw_bwd5(const lhn_view* x, const float* w, const lhn_view* y, const
                      const lhn_pw_opts* opts, const lhn_bnsum* bns, const lhn_bnbwdsrc* fin, const lhn_gatesum* gs, void* stream);
 /* lhn_conv_pw_bwd6 = lhn_conv_pw_bwd5 + flags (0 = lhn_conv_pw_bwd5).
  * LHN_PW_BWD_DZ_DEAD: the caller reads gy->dz (y's channels of the gradient buffer) no more after this call and does not expect
- * dy = d loss / d (convolution output) there either.  The wide register-W kernel (128 -> 128, 64 -> 128, 128 -> 64; stride 1, NHWC)
- * then keeps dy in LDS and only READS dz: one write pass over the output's gradient less.  Without the flag those shapes leave dy in
- * place of dz, as the three-launch split path always did.  The flag is a permission, not a request: kernels that need dy in memory
- * (the split path under LHN_PW_BWD_SPLIT=1 or LHN_PW_LDSW=1) still form it in place, and kernels that never stored it (k_pw_bwd, the
- * narrow register-W instances, strided and NCHW shapes) ignore it.  So with the flag the contents of gy->dz after the call are
+ * dy = d loss / d (convolution output) there either.  The wide register-W instances (lhn_conv_pw_route: k_pw_bwd_wr with a fifth
+ * argument `true`) then run as their `false` twins, which keep dy in LDS and only READ dz: one write pass over the output's gradient
+ * less.  Without the flag those shapes leave dy in place of dz, as the three-launch split path always did.  The flag is a permission,
+ * not a request: the split path still forms dy in place and kernels that never stored it ignore it.  So with the flag the contents of
+ * gy->dz after the call are
  * unspecified (dz or dy); dx, dW, dbias, the coefficients and every sum are the same bits either way in deterministic mode: the
  * result never depends on the flag or on the kernel chosen. */
 #define LHN_PW_BWD_DZ_DEAD 1

@@ -14,18 +14,8 @@
 #include <stdlib.h>
 #include "lhn_common.h"
 
-// LHN_HEAD_STREAM=0 (read once): the head stays on k_pw_fwd / k_pw_bwd + k_bias_grad_nchw and the plan runs every gate-gradient
-// pass as its own launch (A/B comparisons)
-bool lhn_head_stream_on() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("LHN_HEAD_STREAM");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v == 1;
-}
-
-constexpr int HCIN = 128, HLDX = HCIN + 4;
+// Which calls come here is pw_fwd_route / pw_bwd_route's decision (k_conv_pw.hip; lhn_head_shape and the LHN_HEAD_STREAM switch).
+constexpr int HCIN = HEAD_CIN, HLDX = HCIN + 4;
 constexpr int HLDR = HCIN + 8;      // raw copy: lane halves sit four rows apart, 4 * 136 floats = 32 banks apart (no conflict)
 
 // ----------------------------------------------------------------------------------------------------- forward

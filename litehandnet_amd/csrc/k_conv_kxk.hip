@@ -635,93 +635,48 @@ extern "C" int lhn_conv_kxk_bwd(const lhn_view* x, const float* w, const lhn_vie
   return 0;
 }
 
-// 1x1 backward as two launches (dgrad = the implicit-GEMM kernel with one tap, wgrad = the per-tap kernel with one
-// tap): used by lhn_conv_pw_bwd for large Cin*Cout where the fused kernel is LDS-bound to one block per CU.  Channel counts
-// above 128 (hourglass: 256) run as 128-wide slices: dgrad accumulates over output-channel slices (its K), wgrad runs once
-// per input-channel slice with the output channels on gridDim.z.  Returns -1 when a shape has no instance (the caller then
-// takes the fused kernel).
-int lhn_pw_dgrad_wr(const lhn_view* dyv, const float* w, const lhn_view* dxv, int wstride, int accumulate, hipStream_t s);
-
+// 1x1 backward as three launches (k_dy_inplace, dgrad, wgrad = the per-tap kernel with one tap): lhn_conv_pw_bwd takes it for large
+// Cin*Cout where the fused kernel is LDS-bound to one block per CU.  Channel counts above 128 (hourglass: 256) run as 128-wide
+// slices: dgrad accumulates over output-channel slices (its K), wgrad runs once per input-channel slice with the output channels
+// on gridDim.z.  pw_bwd_route (k_conv_pw.hip) has checked that every slice has an instance (lhn_pw_split_instance) and says which
+// kernel the data gradient takes: dy is formed in place, so nothing can be refused from here on.
 int lhn_pw_bwd_split(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate,
-                     float* dw, float* dbias, int nrep, int64_t rep_stride, hipStream_t s) {
+                     float* dw, float* dbias, int nrep, int64_t rep_stride, int dgrad, hipStream_t s) {
   const int Cin = x->C, Cout = y->C;
-  auto dgrad_ok = [&](int co, int nt) { return (co == 64 && (nt == 4 || nt == 2)) || (co == 128 && (nt == 4 || nt == 2 || nt == 1)) || (co == 32 && nt == 4); };
-  auto wgrad_ok = [&](int ci, int nto) { return (ci == 64 && (nto == 4 || nto == 2)) || (ci == 128 && (nto == 4 || nto == 2 || nto == 1)) || (ci == 32 && nto == 4); };
-  // every slice must have an instance BEFORE anything is launched (dy is formed in place: no way back afterwards)
   const int ntd = Cin >= 128 ? 4 : (Cin + 31) / 32;                  // dgrad: features per block = 32*ntd, the rest on gridDim.y
-  if (Cin > 128 && Cin % 128 != 0) return -1;
-  for (int co0 = 0; co0 < Cout; co0 += 128)
-    if (dx && !dgrad_ok(Cout - co0 < 128 ? Cout - co0 : 128, ntd)) return -1;
   const int nto = Cout >= 128 ? 4 : (Cout + 31) / 32;
-  if (Cout > 128 && Cout % 128 != 0) return -1;
-  for (int k0 = 0; k0 < Cin; k0 += 128)
-    if (!wgrad_ok(Cin - k0 < 128 ? Cin - k0 : 128, nto)) return -1;
   launch_dy_inplace(y, gy, s, dbias, nrep, rep_stride);
-  int rc = -1;
-  bool dgrad_done = false;
-  if (dx && Cout == 256 && x->C % 32 == 0) {
-    // K = 256 in one pass on the register-W kernel (dy as input, W transposed): no second K slice accumulating into dx
-    lhn_view dyv = *y;
-    dyv.data = const_cast<float*>(gy->dz);
-    dyv.table = nullptr;
-    dyv.gate = nullptr;
-    dyv.pend = nullptr;
-    dgrad_done = true;
-    for (int ci0 = 0; ci0 < Cin && dgrad_done; ci0 += 128) {
-      lhn_view dxv = *x;
-      dxv.data = dx;
-      dxv.table = nullptr;
-      dxv.gate = nullptr;
-      dxv.pend = nullptr;
-      dxv.coff = x->coff + ci0;
-      dxv.C = Cin - ci0 < 128 ? Cin - ci0 : 128;
-      const int r2 = lhn_pw_dgrad_wr(&dyv, w + ci0, &dxv, Cin, dx_accumulate, s);
-      if (r2 > 0) return r2;
-      if (r2 < 0) {
-        if (ci0 > 0) return 3;
-        dgrad_done = false;
-      }
-    }
-  }
-  if (dx && !dgrad_done) {
-    for (int co0 = 0; co0 < Cout; co0 += 128) {
-      const int cc = Cout - co0 < 128 ? Cout - co0 : 128;
-      lhn_view yv = *y;
-      yv.coff += co0;
-      yv.C = cc;
-      const float* wv = w + (size_t)co0 * Cin;
-      const int acc = dx_accumulate || co0 > 0, nsplit = (Cin + 32 * ntd - 1) / (32 * ntd);
-      // the register-resident-weights 1x1 kernel (k_conv_pw.hip) run on dy with W transposed, <= 128 input channels per launch
-      if ((cc == 32 || cc == 64 || cc == 128) && x->C % 32 == 0) {
-        lhn_view dyv = yv;
-        dyv.data = const_cast<float*>(gy->dz);
-        dyv.table = nullptr;
-        dyv.gate = nullptr;
-        dyv.pend = nullptr;
-        bool ok = true;
-        for (int ci0 = 0; ci0 < Cin && ok; ci0 += 128) {
-          lhn_view dxv = *x;
-          dxv.data = dx;
-          dxv.table = nullptr;
-          dxv.gate = nullptr;
-          dxv.pend = nullptr;
-          dxv.coff = x->coff + ci0;
-          dxv.C = Cin - ci0 < 128 ? Cin - ci0 : 128;
-          const int r2 = lhn_pw_dgrad_wr(&dyv, wv + ci0, &dxv, Cin, acc, s);
-          if (r2 > 0) return r2;
-          if (r2 < 0) {
-            if (ci0 > 0) return 3;      // (cannot happen: the first slice decides whether there is an instance)
-            ok = false;
-          }
-        }
-        if (ok) continue;
-      }
-      rc = -1;
-#define PB(CO, NTV) if (cc == CO && ntd == NTV) rc = launch_kxk<CO, NTV, 1, 1, true>(x, wv, &yv, gy, nullptr, dx, acc, 1, x->C, s, nullptr, nsplit);
-      PB(64, 4) PB(128, 4) PB(128, 2) PB(64, 2) PB(128, 1) PB(32, 4)
+  // K = 256 in one pass on the register-W kernel (dy as input, W transposed: no second K slice accumulating into dx), else <= 128
+  const int costep = dgrad == LHN_PW_DGRAD_WR256 ? 256 : 128;
+  for (int co0 = 0; dgrad != LHN_PW_DGRAD_NONE && co0 < Cout; co0 += costep) {
+    const int cc = Cout - co0 < costep ? Cout - co0 : costep;
+    lhn_view yv = *y;
+    yv.coff += co0;
+    yv.C = cc;
+    const float* wv = w + (size_t)co0 * Cin;
+    const int acc = dx_accumulate || co0 > 0, nsplit = (Cin + 32 * ntd - 1) / (32 * ntd);
+    int rc = 0;
+    if (dgrad == LHN_PW_DGRAD_KXK) {
+      switch (cc * 10 + ntd) {
+#define PB(CO, NTV) case CO * 10 + NTV: rc = launch_kxk<CO, NTV, 1, 1, true>(x, wv, &yv, gy, nullptr, dx, acc, 1, x->C, s, nullptr, nsplit); break;
+        PB(64, 4) PB(128, 4) PB(128, 2) PB(64, 2) PB(128, 1) PB(32, 4)
 #undef PB
-      if (rc) return rc < 0 ? 3 : rc;
+        default: LHN_CHECK_ARG(false, "lhn_conv_pw_bwd: no one-tap dgrad instance for %d features", cc);
+      }
+    } else {      // the register-resident-weights 1x1 kernel (k_conv_pw.hip) run on dy with W transposed, <= 128 input channels per launch
+      lhn_view dyv = yv, dxv = *x;
+      dyv.data = const_cast<float*>(gy->dz);
+      dxv.data = dx;
+      dyv.table = dxv.table = nullptr;
+      dyv.gate = dxv.gate = nullptr;
+      dyv.pend = dxv.pend = nullptr;
+      for (int ci0 = 0; ci0 < Cin && !rc; ci0 += 128) {
+        dxv.coff = x->coff + ci0;
+        dxv.C = Cin - ci0 < 128 ? Cin - ci0 : 128;
+        rc = lhn_pw_dgrad_wr(&dyv, wv + ci0, &dxv, Cin, acc, s);
+      }
     }
+    if (rc) return rc;
   }
   for (int k0 = 0; k0 < Cin; k0 += 128) {
     const int kc = Cin - k0 < 128 ? Cin - k0 : 128;
@@ -729,11 +684,14 @@ int lhn_pw_bwd_split(const lhn_view* x, const float* w, const lhn_view* y, const
     xv.coff += k0;
     xv.C = kc;
     const int cosplit = (Cout + 32 * nto - 1) / (32 * nto);
-    rc = -1;
-#define PW(CI, NTV) if (kc == CI && nto == NTV) rc = launch_kxk_wgrad<CI, NTV, 1, true>(&xv, y, gy, dw + k0, 1, nrep, rep_stride, s, cosplit, Cin);
-    PW(64, 4) PW(128, 4) PW(128, 2) PW(64, 2) PW(128, 1) PW(32, 4)
+    int rc = 0;
+    switch (kc * 10 + nto) {
+#define PW(CI, NTV) case CI * 10 + NTV: rc = launch_kxk_wgrad<CI, NTV, 1, true>(&xv, y, gy, dw + k0, 1, nrep, rep_stride, s, cosplit, Cin); break;
+      PW(64, 4) PW(128, 4) PW(128, 2) PW(64, 2) PW(128, 1) PW(32, 4)
 #undef PW
-    if (rc) return rc < 0 ? 3 : rc;
+      default: LHN_CHECK_ARG(false, "lhn_conv_pw_bwd: no one-tap wgrad instance for %d channels", kc);
+    }
+    if (rc) return rc;
   }
   return 0;
 }

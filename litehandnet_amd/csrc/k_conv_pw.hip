@@ -486,198 +486,6 @@ static int launch_pw_fwd_wr(const lhn_view* x, const float* w, const float* bias
   return 0;
 }
 
-// LHN_PW_LDSW=1: always take the LDS-resident-W kernel (A/B comparisons)
-static bool pw_wr_off() {
-  static int off = -1;
-  if (off < 0) {
-    const char* e = getenv("LHN_PW_LDSW");
-    off = (e && e[0] == '1') ? 1 : 0;
-  }
-  return off == 1;
-}
-
-// returns -1 when the register-resident-weights kernel has no instance for the shape
-static int pw_fwd_wr(const lhn_view* x, const float* w, const float* bias, const lhn_view* y, double* stats, int cout, hipStream_t s,
-                     const PwExtra* ex, const PwGeom& geo, int wt = 0, const lhn_bnfin* fin = nullptr) {
-  if (pw_wr_off()) return -1;
-  const int ci = x->C, ncot = cout <= 32 ? 1 : cout <= 64 ? 2 : 4;
-  const bool ms = ex && ex->n > 0;
-  // K = 256 (hourglassnet.py: every 1x1 of the C = 256 residuals) in ONE pass: 128 VGPRs of W per lane, no second K slice that
-  // re-reads and re-writes y
-  if (ci == 256 && !ms) {
-    if (ncot == 4) return launch_pw_fwd_wr<256, 4, 1>(x, w, bias, y, stats, cout, s, ex, geo, wt, fin);
-    return -1;      // (64 features per block would need 64-pixel tiles: 256 VGPRs and spills)
-  }
-  if (ms) {
-    if (ci == 128 && ncot == 4) return launch_pw_fwd_wr<128, 4, 3>(x, w, bias, y, stats, cout, s, ex, geo, 0, fin);
-    if (ci == 64 && ncot == 2) return launch_pw_fwd_wr<64, 2, 3>(x, w, bias, y, stats, cout, s, ex, geo, 0, fin);
-    return -1;
-  }
-#define WR(CI, NC) if (ci == CI && ncot == NC) return launch_pw_fwd_wr<CI, NC, 1>(x, w, bias, y, stats, cout, s, ex, geo, wt, fin);
-  WR(128, 4) WR(128, 2) WR(64, 4) WR(64, 2) WR(64, 1) WR(32, 4) WR(32, 2) WR(32, 1)
-#undef WR
-  return -1;
-}
-
-// Data gradient of a 1x1 on the same kernel: dx[.., ci0 + n] (+)= sum_k dy[.., k] * W[co0 + k][ci0 + n].  dyv: the plain dy
-// (k_dy_inplace ran) as a view of C = 32/64/128 output features, dxv: <= 128 input channels of the gradient buffer,
-// w = &W[co0][ci0], wstride = Cin of the whole weight.  Returns -1 when there is no instance for the shape.
-int lhn_pw_dgrad_wr(const lhn_view* dyv, const float* w, const lhn_view* dxv, int wstride, int accumulate, hipStream_t s) {
-  if (pw_wr_off()) return -1;
-  PwGeom g;
-  g.wstride = wstride;
-  g.kvalid = dyv->C;
-  g.wrows = dxv->C;
-  g.yacc = accumulate;
-  g.statC = dxv->C;
-  g.nchw_bstride = 0;
-  return pw_fwd_wr(dyv, w, nullptr, dxv, nullptr, dxv->C, s, nullptr, g, 1);
-}
-
-// the streaming kernels of the heatmap head (k_conv_head.hip)
-constexpr int HEAD_CIN = 128;
-bool lhn_head_stream_on();
-int lhn_head_fwd(const lhn_view* x, const float* w, const float* bias, float* y_nchw, int cout, int HoWo, int64_t bstride, hipStream_t s);
-int lhn_head_bwd(const lhn_view* x, const float* w, const float* dy, float* dx, int dx_acc, float* dw, float* dbias, int cout, int HoWo,
-                 int64_t bstride, int nrep, int64_t rep_stride, const lhn_gatesum* gs, hipStream_t s);
-
-// smallest tile width (16/32/64/128) that holds `c` input channels; 0 = none
-static inline int pw_cin_tile(int c) { return c <= 16 ? 16 : c <= 32 ? 32 : c <= 64 ? 64 : c <= 128 ? 128 : 0; }
-
-// one (input slice, output slice) launch
-static int pw_fwd_slice(const lhn_view* x, const float* w, const float* bias, const lhn_view* y, double* stats, int stride,
-                        float* y_nchw, int cout, const lhn_bnfin* fin, const PwGeom& geo, hipStream_t s, const PwExtra* ex = nullptr) {
-  const int ci = x->C == 256 ? 256 : pw_cin_tile(x->C), nt = (cout + 31) / 32 == 3 ? 4 : (cout + 31) / 32;
-  int rc = -1;
-  // fast path: whole-K slice with full-width rows, plain NHWC store (a fused finalize only when this launch is the whole conv)
-  // (slices of a C = 256 convolution qualify too: the kernel takes the whole weight's row stride, accumulates later K slices
-  // into y and addresses the statistics of the whole BatchNorm)
-  if (stride == 1 && !y_nchw && x->C == ci && geo.kvalid == ci && geo.wstride % 4 == 0 && geo.wrows == cout &&
-      !(geo.yacc && ex && ex->n > 0) && !(fin && stats && (geo.yacc || geo.statC != cout)) && (reinterpret_cast<uintptr_t>(w) & 15) == 0) {
-    rc = pw_fwd_wr(x, w, bias, y, stats, cout, s, ex, geo, 0, stats ? fin : nullptr);
-    if (rc != -1) return rc;
-  }
-  if (ex && ex->n > 0) {      // summed-on-load sources: the square 1x1 of MSRB (litehourglass.py:30,49), C = 64 / 128
-    if (ci == 128 && nt == 4) rc = launch_pw_fwd<128, 4, 3>(x, w, bias, y, stats, stride, y_nchw, cout, fin, geo, s, ex);
-    else if (ci == 64 && nt == 2) rc = launch_pw_fwd<64, 2, 3>(x, w, bias, y, stats, stride, y_nchw, cout, fin, geo, s, ex);
-    return rc;
-  }
-#define PW_CASE(CI, NTV) \
-  if (ci == CI && nt == NTV) rc = launch_pw_fwd<CI, NTV>(x, w, bias, y, stats, stride, y_nchw, cout, fin, geo, s, ex);
-  PW_CASE(32, 1) PW_CASE(32, 2) PW_CASE(32, 4) PW_CASE(64, 1) PW_CASE(64, 2) PW_CASE(64, 4) PW_CASE(128, 1)
-  PW_CASE(128, 2) PW_CASE(128, 4) PW_CASE(16, 1) PW_CASE(16, 2) PW_CASE(16, 4)
-#undef PW_CASE
-  return rc;
-}
-
-extern "C" int lhn_conv_pw_fwd2(const lhn_view* x, const float* w, const float* bias, const lhn_view* y, double* stats,
-                                int stride, float* y_nchw, const lhn_bnfin* fin, const lhn_pw_opts* opts, void* stream) {
-  LHN_CHECK_ARG(lhn_view_ok(x) && w && y, "lhn_conv_pw_fwd: bad input view / null pointer");
-  LHN_CHECK_ARG(stride == 1 || stride == 2, "lhn_conv_pw_fwd: stride %d", stride);
-  LHN_CHECK_ARG(y->N == x->N && y->H == (x->H + stride - 1) / stride && y->W == (x->W + stride - 1) / stride,
-                "lhn_conv_pw_fwd: output geometry %dx%dx%d does not match input %dx%dx%d / stride %d", y->N, y->H, y->W,
-                x->N, x->H, x->W, stride);
-  const int Cout = y->C, Cin = x->C, HoWo = y->H * y->W;
-  if (y_nchw) {
-    LHN_CHECK_ARG(HoWo % 4 == 0 && Cout > 0, "lhn_conv_pw_fwd: NCHW output needs H*W %% 4 == 0");
-    LHN_CHECK_ARG(!stats, "lhn_conv_pw_fwd: no statistics on the NCHW head");
-  } else {
-    LHN_CHECK_ARG(lhn_view_ok(y), "lhn_conv_pw_fwd: bad output view");
-  }
-  LHN_CHECK_ARG((int64_t)y->N * y->H * y->W < (1ll << 31) - 256, "lhn_conv_pw_fwd: too many pixels");
-  // weight tensor: [w_rows][w_cols], w_cols real input channels (<= Cin, the view may be padded to a multiple of 4),
-  // w_rows real output features (<= Cout)
-  const int wcols = (opts && opts->w_cols > 0) ? opts->w_cols : Cin, wrows = (opts && opts->w_rows > 0) ? opts->w_rows : Cout;
-  LHN_CHECK_ARG(wcols <= Cin && wcols > Cin - 4 && wrows <= Cout, "lhn_conv_pw_fwd: weight [%d][%d] does not fit views %d -> %d",
-                wrows, wcols, Cin, Cout);
-  const int64_t bstride = (opts && opts->nchw_batch_stride > 0) ? opts->nchw_batch_stride : (int64_t)Cout * HoWo;
-  hipStream_t s = (hipStream_t)stream;
-  const bool single = Cin <= 128 && Cout <= 128;
-  PwExtra ex;
-  ex.n = 0;
-  ex.sum_out = nullptr;
-  ex.so_cstride = ex.so_coff = 0;
-  LHN_CHECK_ARG(lhn_no_pend(x), "lhn_conv_pw_fwd: lhn_view.pend is reserved (NULL)");
-  // the heatmap head (128 -> <= 32 features, NCHW, bias, no statistics, one source) on its streaming kernel (k_conv_head.hip);
-  // LHN_HEAD_STREAM=0, LHN_PW_LDSW=1 ("no register-W kernel") and every other NCHW shape (H's stacked 256 -> 21, padded heads,
-  // K slices) keep k_pw_fwd below
-  if (y_nchw && lhn_head_stream_on() && !pw_wr_off() && stride == 1 && Cin == HEAD_CIN && wcols == Cin && Cout <= 32 && wrows == Cout && !(opts && (opts->n_extra > 0 || opts->sum_out)) &&
-      bstride % 4 == 0 && ((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(y_nchw)) & 15) == 0) {
-    const int rc = lhn_head_fwd(x, w, bias, y_nchw, Cout, HoWo, bstride, s);
-    if (rc) return rc;
-    LHN_CHECK_LAUNCH("lhn_conv_pw_fwd");
-    return 0;
-  }
-  if (opts && opts->n_extra > 0) {
-    LHN_CHECK_ARG(opts->n_extra <= 2 && opts->extra && single && stride == 1, "lhn_conv_pw_fwd: extra sources need stride 1 and <= 128 channels");
-    ex.n = opts->n_extra;
-    for (int e = 0; e < ex.n; ++e) {
-      const lhn_view* v = &opts->extra[e];
-      LHN_CHECK_ARG(lhn_view_ok(v) && v->C == Cin && v->N == x->N && v->H == x->H && v->W == x->W && lhn_no_pend(v), "lhn_conv_pw_fwd: extra source %d geometry", e);
-      ex.v[e] = *v;
-    }
-    for (int e = 0; e < 3; ++e) ex.coef[e] = opts->coef[e];
-    if (opts->sum_out) {
-      const lhn_view* so = opts->sum_out;
-      LHN_CHECK_ARG(so->data && so->C == Cin && so->N == x->N && so->H == x->H && so->W == x->W && so->cstride % 4 == 0 && so->coff % 4 == 0 &&
-                        so->coff + so->C <= so->cstride && Cout <= 128 && Cin % 4 == 0,
-                    "lhn_conv_pw_fwd: sum_out geometry (same pixels and channels as x, one output slice)");
-      ex.sum_out = so->data;
-      ex.so_cstride = so->cstride;
-      ex.so_coff = so->coff;
-    }
-  } else {
-    LHN_CHECK_ARG(!(opts && opts->sum_out), "lhn_conv_pw_fwd: sum_out without extra sources");
-  }
-  // Cin = 256 with full-width rows: the register-W kernel takes the whole K at once (LHN_PW_K256=0, or LHN_PW_LDSW=1 which has
-  // no register-W kernel to take it: two K slices, the second one accumulating into y)
-  static int k256 = -1;
-  if (k256 < 0) {
-    const char* e = getenv("LHN_PW_K256");
-    k256 = (e && e[0] == '0') ? 0 : 1;
-  }
-  const int kstep = (k256 && !pw_wr_off() && Cin == 256 && wcols == 256 && stride == 1 && !y_nchw && ex.n == 0 && Cout % 128 == 0 && wrows == Cout &&
-                     (reinterpret_cast<uintptr_t>(w) & 15) == 0 && !(fin && stats && single)) ? 256 : 128;
-  for (int co0 = 0; co0 < Cout; co0 += 128) {
-    const int cc = Cout - co0 < 128 ? Cout - co0 : 128;
-    for (int k0 = 0; k0 < Cin; k0 += kstep) {
-      const int kc = Cin - k0 < kstep ? Cin - k0 : kstep;
-      const bool last = k0 + kc >= Cin;
-      lhn_view xv = *x, yv = *y;
-      xv.coff += k0;
-      xv.C = kc;
-      if (!y_nchw) {
-        yv.coff += co0;
-        yv.C = cc;
-      }
-      PwGeom g;
-      g.wstride = wcols;
-      g.kvalid = wcols - k0 < kc ? wcols - k0 : kc;
-      g.wrows = wrows - co0 < cc ? (wrows - co0 < 0 ? 0 : wrows - co0) : cc;
-      g.yacc = k0 > 0;
-      g.statC = Cout;
-      g.nchw_bstride = bstride;
-      const int rc = pw_fwd_slice(&xv, w + (int64_t)co0 * wcols + k0, (last && bias) ? bias + co0 : nullptr, &yv,
-                                  (last && stats) ? stats + co0 : nullptr, stride, y_nchw ? y_nchw + (int64_t)co0 * HoWo : nullptr,
-                                  cc, single ? fin : nullptr, g, s, &ex);
-      LHN_CHECK_ARG(rc != -1, "lhn_conv_pw_fwd: unsupported channels Cin=%d Cout=%d (%d extra sources)", Cin, Cout, ex.n);
-      if (rc) return rc;
-    }
-  }
-  LHN_CHECK_LAUNCH("lhn_conv_pw_fwd");
-  if (!single && fin && stats) {   // fused finalize was requested: the sliced form runs it as its own launch
-    return lhn_bn_finalize(stats, fin->gamma, fin->beta, fin->running_mean, fin->running_var, fin->num_batches_tracked, fin->table,
-                           fin->cstride, fin->coff, fin->C, fin->save_mean_invstd, fin->count, fin->eps, fin->momentum, fin->slope,
-                           1, fin->conv_bias, stream);
-  }
-  return 0;
-}
-
-extern "C" int lhn_conv_pw_fwd(const lhn_view* x, const float* w, const float* bias, const lhn_view* y, double* stats,
-                               int stride, float* y_nchw, const lhn_bnfin* fin, void* stream) {
-  return lhn_conv_pw_fwd2(x, w, bias, y, stats, stride, y_nchw, fin, nullptr, stream);
-}
-
 // =====================================================================================================
 // Backward: fused dgrad + wgrad.  Per 64-pixel tile the block stages
 //     dYs[m][co] = dy  (formed on the fly from dz, the saved raw output y and the BN-backward coefficients)
@@ -1012,19 +820,6 @@ static int launch_pw_bwd_t(const lhn_view* x, const float* w, const lhn_view* y,
     hipLaunchKernelGGL(k_bias_grad_nchw, dim3(geo.wrows, lhn_deterministic_mode() ? 1 : (y->N < 16 ? y->N : 16)), dim3(256), 0, s, dy_nchw, dbias, y->N, cout,
                        y->H * y->W, geo.nchw_bstride);
   return 0;
-}
-
-template <int CIN, int NTO>
-static int launch_pw_bwd(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc,
-                         float* dw, float* dbias, int stride, const float* dy_nchw, int cout, int nrep, int64_t rep_stride,
-                         const PwGeom& geo, hipStream_t s, const lhn_bnsum& bs) {
-  if (dy_nchw) return launch_pw_bwd_t<CIN, NTO, true>(x, w, y, gy, dx, dx_acc, dw, dbias, stride, dy_nchw, cout, nrep, rep_stride, geo, s, bs);
-  if constexpr (CIN * NTO * 32 < 64 * 128) {           // reader-side BatchNorm sums: the shapes the fused kernel keeps for itself
-    if (bs.sums && dx && stride == 1)
-      return launch_pw_bwd_t<CIN, NTO, false, true>(x, w, y, gy, dx, dx_acc, dw, dbias, stride, dy_nchw, cout, nrep, rep_stride, geo, s, bs);
-  }
-  if (bs.sums) return -1;
-  return launch_pw_bwd_t<CIN, NTO, false>(x, w, y, gy, dx, dx_acc, dw, dbias, stride, dy_nchw, cout, nrep, rep_stride, geo, s, bs);
 }
 
 // =====================================================================================================
@@ -1383,86 +1178,325 @@ static int launch_pw_bwd_wr(const lhn_view* x, const float* w, const lhn_view* y
   return 0;
 }
 
-// LHN_PW_BWD_NARROW=0: 64 -> 64 and 32 -> 32 stay on k_pw_bwd as before the narrow instances existed (A/B comparisons)
-static bool pw_bwd_narrow_off() {
-  static int off = -1;
-  if (off < 0) {
-    const char* e = getenv("LHN_PW_BWD_NARROW");
-    off = (e && e[0] == '0') ? 1 : 0;
+// =====================================================================================================
+// Route: which kernels a 1x1 call launches.  pw_fwd_route() and pw_bwd_route() are pure and the only place that knows the rules; the
+// dispatchers below and lhn_conv_pw_route() (the host-only query, which the tests and profiles/pw_instances.md read) call them.
+struct PwShape {
+  int N, H, W, HoWo;             // of x; pixels of one output image
+  int Cin, Cout, stride;
+  int wcols, wrows;              // the weight tensor's real shape (<= Cin, <= Cout)
+  unsigned f;                    // LHN_PW_F_*: what the call carries
+};
+enum PwPath {
+  PW_NONE = 0,      // no instance
+  PW_HEAD,          // the streaming head kernels (k_conv_head.hip)
+  PW_SLICED,        // (<= 128 | 256) x (<= 128) channel slices on k_pw_fwd_wr / k_pw_fwd; backward: the fused k_pw_bwd
+  PWB_WIDE,         // backward, one register-W launch: 128 -> 128, 64 -> 128, 128 -> 64
+  PWB_NARROW,       // the same kernel's 64 -> 64 and 32 -> 32 instances
+  PWB_SPLIT         // k_dy_inplace, dgrad, wgrad (lhn_pw_bwd_split)
+};
+struct PwRoute {
+  PwPath path;
+  int kstep;                     // sliced forward: input channels per launch, 128 or 256 (the whole K = 256 on the register-W kernel)
+  int dgrad;                     // split: LHN_PW_DGRAD_*, the kernel every output slice's data gradient takes
+  bool dyst, bns;                // wide / narrow: DYST and BNS of the k_pw_bwd_wr instance
+  bool separate_finalize;        // forward: the sliced form's own lhn_bn_finalize launch behind; backward: lhn_bn_bwd_finalize2 in front
+  bool gate_reduce_after;        // gate sums asked for and the kernel does not add them: the lhn_gate_bwd_reduce3 launch behind
+};
+// One forward launch of the sliced path: k_pw_fwd_wr<ci, nt, ns> (wr; nt = NCOT) or k_pw_fwd<ci, nt, ns>.  ci = 0: no instance.
+struct PwInst {
+  int ci, nt, ns;
+  bool wr;
+};
+
+// LHN_PW_SW_*, read from the environment once.  LHN_PW_LDSW=1: no register-W kernel anywhere (the LDS-resident-W kernels, the split
+// backward, no streaming head).  LHN_PW_K256=0: Cin = 256 in two K slices, the second accumulating into y.  LHN_PW_BWD_NARROW=0:
+// 64 -> 64 and 32 -> 32 stay on k_pw_bwd.  LHN_PW_BWD_SPLIT=1: the wide shapes take lhn_pw_bwd_split.  LHN_HEAD_STREAM=0: the head
+// stays on k_pw_fwd / k_pw_bwd + k_bias_grad_nchw and the plan runs every gate-gradient pass as its own launch.  All for A/B runs.
+static unsigned pw_switches() {
+  static int v = -1;
+  if (v < 0) {
+    const char *ld = getenv("LHN_PW_LDSW"), *k2 = getenv("LHN_PW_K256"), *na = getenv("LHN_PW_BWD_NARROW"), *sp = getenv("LHN_PW_BWD_SPLIT"),
+               *hs = getenv("LHN_HEAD_STREAM");
+    v = ((ld && ld[0] == '1') ? LHN_PW_SW_LDSW : 0) | ((k2 && k2[0] == '0') ? 0 : LHN_PW_SW_K256) |
+        ((na && na[0] == '0') ? 0 : LHN_PW_SW_BWD_NARROW) | ((sp && sp[0] == '1') ? LHN_PW_SW_BWD_SPLIT : 0) |
+        ((hs && hs[0] == '0') ? 0 : LHN_PW_SW_HEAD_STREAM) | (lhn_deterministic_mode() ? LHN_PW_SW_DETERMINISTIC : 0);
   }
-  return off == 1;
+  return (unsigned)v;
+}
+bool lhn_head_stream_on() { return (pw_switches() & LHN_PW_SW_HEAD_STREAM) != 0; }
+
+// smallest tile width (16/32/64/128) that holds `c` input channels; 0 = none
+static inline int pw_cin_tile(int c) { return c <= 16 ? 16 : c <= 32 ? 32 : c <= 64 ? 64 : c <= 128 ? 128 : 0; }
+// 32-wide feature tiles per workgroup of the LDS-W kernels for `cc` features: 1, 2 or 4 (three run as four)
+static inline int pw_feature_tiles(int cc) { return (cc + 31) / 32 == 3 ? 4 : (cc + 31) / 32; }
+static inline bool pw_head_shape(const PwShape& s) { return lhn_head_shape(s.Cin, s.Cout, s.wcols, s.wrows); }
+// reader-side BatchNorm sums: the k_pw_bwd tiles that have a BNS instance (the shapes the fused kernel keeps for itself)
+constexpr bool pw_bwd_bns_tile(int ci, int nto) { return ci * nto * 32 < 64 * 128; }
+
+// The slice at (co0, k0) of the sliced paths: cc features, kc input channels (kstep per launch) and the geometry its launch sees
+struct PwSlice {
+  int cc, kc;
+  PwGeom g;
+};
+static PwSlice pw_slice(const PwShape& s, int kstep, int co0, int k0) {
+  PwSlice t;
+  t.cc = s.Cout - co0 < 128 ? s.Cout - co0 : 128;
+  t.kc = s.Cin - k0 < kstep ? s.Cin - k0 : kstep;
+  t.g = {s.wcols, s.wcols - k0 < t.kc ? s.wcols - k0 : t.kc, s.wrows - co0 < t.cc ? (s.wrows - co0 < 0 ? 0 : s.wrows - co0) : t.cc, 0, s.Cout, 0};
+  return t;
 }
 
-// LHN_PW_BWD_SPLIT=1: the wide shapes take lhn_pw_bwd_split as before k_pw_bwd_wr existed (A/B comparisons)
-static bool pw_bwd_split_forced() {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("LHN_PW_BWD_SPLIT");
-    on = (e && e[0] == '1') ? 1 : 0;
+// The register-W forward instances: `ci` input channels exactly, `cout` features, `ms` = summed-on-load sources.  K = 256
+// (hourglassnet.py: every 1x1 of the C = 256 residuals) in ONE pass needs 128 features per block (64 would need 64-pixel tiles: 256
+// VGPRs and spills).
+static PwInst pw_wr_instance(int ci, int cout, bool ms) {
+  const int ncot = cout <= 32 ? 1 : cout <= 64 ? 2 : 4;
+  const bool ok = ms ? ((ci == 128 && ncot == 4) || (ci == 64 && ncot == 2))
+                     : ci == 256 ? ncot == 4 : ci == 128 ? ncot >= 2 : (ci == 64 || ci == 32);
+  return {ok ? ci : 0, ncot, ms ? 3 : 1, true};
+}
+
+// the forward launch of the slice at (co0, k0)
+static PwInst pw_fwd_inst(const PwShape& s, unsigned sw, int kstep, int co0, int k0) {
+  const PwSlice t = pw_slice(s, kstep, co0, k0);
+  const int cc = t.cc, kc = t.kc, ci = kc == 256 ? 256 : pw_cin_tile(kc), nt = pw_feature_tiles(cc);
+  const bool ms = s.f & (LHN_PW_F_EXTRA1 | LHN_PW_F_EXTRA2);
+  // fast path: whole-K slice with full-width rows, plain NHWC store.  Slices of a C = 256 convolution qualify too: the kernel takes
+  // the whole weight's row stride, accumulates later K slices into y and addresses the statistics of the whole BatchNorm.
+  if (!(sw & LHN_PW_SW_LDSW) && s.stride == 1 && !(s.f & (LHN_PW_F_NCHW | LHN_PW_F_UNALIGNED)) && kc == ci && t.g.kvalid == ci && s.wcols % 4 == 0 &&
+      t.g.wrows == cc) {
+    const PwInst i = pw_wr_instance(ci, cc, ms);
+    if (i.ci) return i;
   }
-  return on == 1;
+  // summed-on-load sources: the square 1x1 of MSRB (litehourglass.py:30,49), C = 64 / 128
+  if (ms) return {((ci == 128 && nt == 4) || (ci == 64 && nt == 2)) ? ci : 0, nt, 3, false};
+  return {ci == 256 ? 0 : ci, nt, 1, false};
 }
 
-int lhn_pw_bwd_split(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate,
-                     float* dw, float* dbias, int nrep, int64_t rep_stride, hipStream_t s);
+static PwRoute pw_fwd_route(const PwShape& s, unsigned sw) {
+  PwRoute r = {PW_NONE, 128, LHN_PW_DGRAD_NONE, false, false, false, false};
+  const bool nchw = s.f & LHN_PW_F_NCHW, ms = s.f & (LHN_PW_F_EXTRA1 | LHN_PW_F_EXTRA2), regw = !(sw & LHN_PW_SW_LDSW);
+  const bool single = s.Cin <= 128 && s.Cout <= 128;
+  // the heatmap head (128 -> <= 32 features, NCHW, one source) on its streaming kernel; every other NCHW shape (H's stacked
+  // 256 -> 21, padded heads, K slices) keeps k_pw_fwd
+  if (nchw && (sw & LHN_PW_SW_HEAD_STREAM) && regw && s.stride == 1 && pw_head_shape(s) && !ms && !(s.f & (LHN_PW_F_SUM_OUT | LHN_PW_F_UNALIGNED)))
+    return r.path = PW_HEAD, r;
+  // (only summed-on-load sources can lack an instance, and they are one slice: every other slice has an LDS-W instance at least)
+  if (ms && (!single || !pw_fwd_inst(s, sw, 128, 0, 0).ci)) return r;
+  // Cin = 256 with full-width rows: the register-W kernel takes the whole K at once
+  if ((sw & LHN_PW_SW_K256) && regw && s.Cin == 256 && s.wcols == 256 && s.stride == 1 && !nchw && !ms && s.Cout % 128 == 0 && s.wrows == s.Cout &&
+      !(s.f & LHN_PW_F_UNALIGNED))
+    r.kstep = 256;
+  r.path = PW_SLICED;
+  // a fused finalize rides in the kernel only when one launch is the whole convolution
+  r.separate_finalize = !single && (s.f & LHN_PW_F_FUSE_FIN) && (s.f & LHN_PW_F_STATS);
+  return r;
+}
 
-extern "C" int lhn_conv_pw_bwd2(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
-                                int dx_accumulate, float* dw, float* dbias, int stride, const float* dy_nchw, int nrep,
-                                int64_t rep_stride, const lhn_pw_opts* opts, void* stream) {
-  return lhn_conv_pw_bwd3(x, w, y, gy, dx, dx_accumulate, dw, dbias, stride, dy_nchw, nrep, rep_stride, opts, nullptr, stream);
+// input tile of a backward slice of kc channels (no 16-wide backward tile)
+static inline int pw_bwd_cin_tile(int kc) { return kc <= 32 ? 32 : pw_cin_tile(kc); }
+
+// The split path's instances: every slice must have one BEFORE anything is launched (dy is formed in place: no way back afterwards).
+// Slices are all alike: channel counts above 128 must be multiples of 128.
+static bool pw_split_route(const PwShape& s, unsigned sw, int* dgrad) {
+  const int ntd = s.Cin >= 128 ? 4 : (s.Cin + 31) / 32, nto = s.Cout >= 128 ? 4 : (s.Cout + 31) / 32;
+  const int cc = s.Cout < 128 ? s.Cout : 128, kc = s.Cin < 128 ? s.Cin : 128;
+  const bool dx = !(s.f & LHN_PW_F_NO_DX), regw = !(sw & LHN_PW_SW_LDSW);
+  if ((s.Cin > 128 && s.Cin % 128 != 0) || (s.Cout > 128 && s.Cout % 128 != 0)) return false;
+  if ((dx && !lhn_pw_split_instance(cc, ntd)) || !lhn_pw_split_instance(kc, nto)) return false;
+  *dgrad = !dx ? LHN_PW_DGRAD_NONE
+           : (regw && s.Cout == 256 && pw_wr_instance(256, kc, false).ci) ? LHN_PW_DGRAD_WR256
+           : (regw && (cc == 32 || cc == 64 || cc == 128) && pw_wr_instance(cc, kc, false).ci) ? LHN_PW_DGRAD_WR
+                                                                                                : LHN_PW_DGRAD_KXK;
+  return true;
 }
-extern "C" int lhn_conv_pw_bwd3(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
-                                int dx_accumulate, float* dw, float* dbias, int stride, const float* dy_nchw, int nrep,
-                                int64_t rep_stride, const lhn_pw_opts* opts, const lhn_bnsum* bns, void* stream) {
-  return lhn_conv_pw_bwd4(x, w, y, gy, dx, dx_accumulate, dw, dbias, stride, dy_nchw, nrep, rep_stride, opts, bns, nullptr, stream);
+
+static PwRoute pw_bwd_route(const PwShape& s, unsigned sw) {
+  PwRoute r = {PW_NONE, 128, LHN_PW_DGRAD_NONE, false, false, false, false};
+  const bool nchw = s.f & LHN_PW_F_NCHW, bns = s.f & LHN_PW_F_BNSUM, fin = s.f & LHN_PW_F_FIN, gs = s.f & LHN_PW_F_GATESUM;
+  const bool regw = !(sw & LHN_PW_SW_LDSW);
+  // reader-side BatchNorm sums ride in the fused kernel's BNS instances and in the narrow register-W ones (both inside the tile rule);
+  // an NCHW gradient runs the NCHW instances, which take no sums: such a call is accepted by its channel product, as it always was
+  if (bns && (s.stride != 1 || s.Cin > 128 || s.Cout > 128 || (s.f & LHN_PW_F_NO_DX) ||
+              (nchw ? s.Cin * s.Cout >= 64 * 128 : !pw_bwd_bns_tile(pw_bwd_cin_tile(s.Cin), pw_feature_tiles(s.Cout)))))
+    return r;
+  // the heatmap head (128 -> <= 32 features from NCHW planes) on its streaming kernel: dx, dW, dbias and the gate sums of x's buffer
+  // in ONE launch.  Gate sums only where a tile stays inside an image, and not in deterministic mode: an image's sums have several
+  // writers there (dW and dbias have one writer per replica: at most 4 workgroups).
+  if (nchw && (sw & LHN_PW_SW_HEAD_STREAM) && regw && s.stride == 1 && !bns && !fin && pw_head_shape(s) && s.HoWo % 4 == 0 &&
+      !(s.f & LHN_PW_F_UNALIGNED) && (!gs || (s.HoWo % 64 == 0 && !(sw & LHN_PW_SW_DETERMINISTIC))))
+    return r.path = PW_HEAD, r;
+  const bool whole = s.stride == 1 && !nchw && s.wcols == s.Cin && s.wrows == s.Cout;
+  if (whole && !bns && regw && !(sw & LHN_PW_SW_BWD_SPLIT) &&
+      ((s.Cin == 128 && s.Cout == 128) || (s.Cin == 64 && s.Cout == 128) || (s.Cin == 128 && s.Cout == 64))) {
+    r.path = PWB_WIDE;
+    r.dyst = !(s.f & LHN_PW_F_DZ_DEAD);      // dz declared dead: dy stays in LDS
+  } else if (whole && regw && (sw & LHN_PW_SW_BWD_NARROW) && s.Cin == s.Cout && (s.Cin == 64 || s.Cin == 32)) {
+    // The BNS instances compile the gate on x out: they rely on the dispatcher's `!x->gate` condition for sums -- if that check is
+    // ever relaxed, gated sums calls must leave this branch
+    r.path = PWB_NARROW;
+    r.bns = bns;
+  } else if (whole && !bns && s.Cin * s.Cout >= 64 * 128 && s.Cout % 32 == 0 && s.Cin % 32 == 0 && s.Cout <= 256 && pw_split_route(s, sw, &r.dgrad)) {
+    r.path = PWB_SPLIT;
+  } else {
+    r.path = PW_SLICED;
+  }
+  // the register-W instances fold the finalize in their prologue; every other path gets the separate launch, before its own first
+  r.separate_finalize = fin && r.path != PWB_WIDE && r.path != PWB_NARROW;
+  r.gate_reduce_after = gs;
+  return r;
 }
-// fin: the BatchNorm-backward finalize of y (lhn_bnbwdsrc).  The register-W instances fold it in their prologue; every other path gets
-// the separate launch from here, before its own first launch.
-extern "C" int lhn_conv_pw_bwd4(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
-                                int dx_accumulate, float* dw, float* dbias, int stride, const float* dy_nchw, int nrep,
-                                int64_t rep_stride, const lhn_pw_opts* opts, const lhn_bnsum* bns, const lhn_bnbwdsrc* fin, void* stream) {
-  return lhn_conv_pw_bwd5(x, w, y, gy, dx, dx_accumulate, dw, dbias, stride, dy_nchw, nrep, rep_stride, opts, bns, fin, nullptr, stream);
+
+// =====================================================================================================
+// Launch switches: from the route's instance to the template.
+static int pw_fwd_launch(const PwInst& i, const lhn_view* x, const float* w, const float* bias, const lhn_view* y, double* stats, int stride,
+                         float* y_nchw, int cout, const lhn_bnfin* fin, const PwGeom& geo, hipStream_t s, const PwExtra* ex, int wt = 0) {
+#define PW_KEY(WRV, CI, NTV, NSV) ((((WRV) * 1000 + (CI)) * 10 + (NTV)) * 10 + (NSV))
+  switch (PW_KEY(i.wr, i.ci, i.nt, i.ns)) {
+#define WR(CI, NC, NSV) case PW_KEY(1, CI, NC, NSV): return launch_pw_fwd_wr<CI, NC, NSV>(x, w, bias, y, stats, cout, s, ex, geo, wt, stats ? fin : nullptr);
+    WR(256, 4, 1) WR(128, 4, 3) WR(64, 2, 3) WR(128, 4, 1) WR(128, 2, 1) WR(64, 4, 1) WR(64, 2, 1) WR(64, 1, 1) WR(32, 4, 1) WR(32, 2, 1) WR(32, 1, 1)
+#undef WR
+#define LW(CI, NTV, NSV) case PW_KEY(0, CI, NTV, NSV): return launch_pw_fwd<CI, NTV, NSV>(x, w, bias, y, stats, stride, y_nchw, cout, fin, geo, s, ex);
+    LW(128, 4, 3) LW(64, 2, 3) LW(32, 1, 1) LW(32, 2, 1) LW(32, 4, 1) LW(64, 1, 1) LW(64, 2, 1) LW(64, 4, 1) LW(128, 1, 1) LW(128, 2, 1)
+    LW(128, 4, 1) LW(16, 1, 1) LW(16, 2, 1) LW(16, 4, 1)
+#undef LW
+#undef PW_KEY
+    default: LHN_CHECK_ARG(false, "lhn_conv_pw_fwd: no kernel instance for %d channels x %d tiles", i.ci, i.nt);
+  }
 }
+
+int lhn_pw_dgrad_wr(const lhn_view* dyv, const float* w, const lhn_view* dxv, int wstride, int accumulate, hipStream_t s) {
+  const PwGeom g = {wstride, dyv->C, dxv->C, accumulate, dxv->C, 0};
+  return pw_fwd_launch(pw_wr_instance(dyv->C, dxv->C, false), dyv, w, nullptr, dxv, nullptr, 1, nullptr, dxv->C, nullptr, g, s, nullptr, 1);
+}
+
+// k_pw_bwd<CIN, NTO, NCHW, BNS>: the NCHW instances take no sums; the route has refused sums on a tile without a BNS instance
+template <int CIN, int NTO>
+static int launch_pw_bwd(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc,
+                         float* dw, float* dbias, int stride, const float* dy_nchw, int cout, int nrep, int64_t rep_stride,
+                         const PwGeom& geo, hipStream_t s, const lhn_bnsum& bs) {
+  if (dy_nchw) return launch_pw_bwd_t<CIN, NTO, true>(x, w, y, gy, dx, dx_acc, dw, dbias, stride, dy_nchw, cout, nrep, rep_stride, geo, s, bs);
+  if constexpr (pw_bwd_bns_tile(CIN, NTO)) {
+    if (bs.sums) return launch_pw_bwd_t<CIN, NTO, false, true>(x, w, y, gy, dx, dx_acc, dw, dbias, stride, dy_nchw, cout, nrep, rep_stride, geo, s, bs);
+  }
+  return launch_pw_bwd_t<CIN, NTO, false>(x, w, y, gy, dx, dx_acc, dw, dbias, stride, dy_nchw, cout, nrep, rep_stride, geo, s, bs);
+}
+
+// The k_pw_bwd_wr instances: Cin, Cout, PX, PF, DYST, BNS, OCC.  Wide ones with and without the dy store, narrow ones with and without sums.
+#define PW_BWD_WR_INSTANCES(X)                                                                                                  \
+  X(128, 128, 32, 1, true, false, 2) X(128, 128, 32, 1, false, false, 2) X(64, 128, 64, 1, true, false, 2) X(64, 128, 64, 1, false, false, 2) \
+  X(128, 64, 64, 2, true, false, 2) X(128, 64, 64, 2, false, false, 2) X(64, 64, 64, 2, false, false, 2) X(64, 64, 64, 2, false, true, 2)     \
+  X(32, 32, 128, 2, false, false, 3) X(32, 32, 128, 2, false, true, 2)
+#define PW_BWD_WR_KEY(CI, CO, DY, BN) ((((CI) * 1000 + (CO)) * 2 + ((DY) ? 1 : 0)) * 2 + ((BN) ? 1 : 0))
+
+// =====================================================================================================
+// Dispatchers: validate everything, ask the route, issue the separate finalize launch when the route says so, launch.
+static int pw_fwd_run(const lhn_view* x, const float* w, const float* bias, const lhn_view* y, double* stats, int stride, float* y_nchw,
+                      const lhn_bnfin* fin, const lhn_pw_opts* opts, void* stream) {
+  LHN_CHECK_ARG(lhn_view_ok(x) && w && y, "lhn_conv_pw_fwd: bad input view / null pointer");
+  LHN_CHECK_ARG(stride == 1 || stride == 2, "lhn_conv_pw_fwd: stride %d", stride);
+  LHN_CHECK_ARG(y->N == x->N && y->H == (x->H + stride - 1) / stride && y->W == (x->W + stride - 1) / stride,
+                "lhn_conv_pw_fwd: output geometry %dx%dx%d does not match input %dx%dx%d / stride %d", y->N, y->H, y->W,
+                x->N, x->H, x->W, stride);
+  const int Cout = y->C, Cin = x->C, HoWo = y->H * y->W;
+  if (y_nchw) {
+    LHN_CHECK_ARG(HoWo % 4 == 0 && Cout > 0, "lhn_conv_pw_fwd: NCHW output needs H*W %% 4 == 0");
+    LHN_CHECK_ARG(!stats, "lhn_conv_pw_fwd: no statistics on the NCHW head");
+  } else {
+    LHN_CHECK_ARG(lhn_view_ok(y), "lhn_conv_pw_fwd: bad output view");
+  }
+  LHN_CHECK_ARG((int64_t)y->N * y->H * y->W < (1ll << 31) - 256, "lhn_conv_pw_fwd: too many pixels");
+  // weight tensor: [w_rows][w_cols], w_cols real input channels (<= Cin, the view may be padded to a multiple of 4),
+  // w_rows real output features (<= Cout)
+  const int wcols = (opts && opts->w_cols > 0) ? opts->w_cols : Cin, wrows = (opts && opts->w_rows > 0) ? opts->w_rows : Cout;
+  LHN_CHECK_ARG(wcols <= Cin && wcols > Cin - 4 && wrows <= Cout, "lhn_conv_pw_fwd: weight [%d][%d] does not fit views %d -> %d",
+                wrows, wcols, Cin, Cout);
+  const int64_t bstride = (opts && opts->nchw_batch_stride > 0) ? opts->nchw_batch_stride : (int64_t)Cout * HoWo;
+  const bool single = Cin <= 128 && Cout <= 128;
+  PwExtra ex;
+  ex.n = 0;
+  ex.sum_out = nullptr;
+  ex.so_cstride = ex.so_coff = 0;
+  LHN_CHECK_ARG(lhn_no_pend(x), "lhn_conv_pw_fwd: lhn_view.pend is reserved (NULL)");
+  if (opts && opts->n_extra > 0) {
+    LHN_CHECK_ARG(opts->n_extra <= 2 && opts->extra && single && stride == 1, "lhn_conv_pw_fwd: extra sources need stride 1 and <= 128 channels");
+    ex.n = opts->n_extra;
+    for (int e = 0; e < ex.n; ++e) {
+      const lhn_view* v = &opts->extra[e];
+      LHN_CHECK_ARG(lhn_view_ok(v) && v->C == Cin && v->N == x->N && v->H == x->H && v->W == x->W && lhn_no_pend(v), "lhn_conv_pw_fwd: extra source %d geometry", e);
+      ex.v[e] = *v;
+    }
+    for (int e = 0; e < 3; ++e) ex.coef[e] = opts->coef[e];
+    if (opts->sum_out) {
+      const lhn_view* so = opts->sum_out;
+      LHN_CHECK_ARG(so->data && so->C == Cin && so->N == x->N && so->H == x->H && so->W == x->W && so->cstride % 4 == 0 && so->coff % 4 == 0 &&
+                        so->coff + so->C <= so->cstride && Cout <= 128 && Cin % 4 == 0,
+                    "lhn_conv_pw_fwd: sum_out geometry (same pixels and channels as x, one output slice)");
+      ex.sum_out = so->data;
+      ex.so_cstride = so->cstride;
+      ex.so_coff = so->coff;
+    }
+  } else {
+    LHN_CHECK_ARG(!(opts && opts->sum_out), "lhn_conv_pw_fwd: sum_out without extra sources");
+  }
+  const bool unaligned = (reinterpret_cast<uintptr_t>(w) & 15) != 0 || (y_nchw && ((reinterpret_cast<uintptr_t>(y_nchw) & 15) != 0 || bstride % 4 != 0));
+  const PwShape sh = {x->N, x->H, x->W, HoWo, Cin, Cout, stride, wcols, wrows,
+                      (y_nchw ? LHN_PW_F_NCHW : 0u) | (stats ? LHN_PW_F_STATS : 0u) | (fin ? LHN_PW_F_FUSE_FIN : 0u) |
+                          (ex.n == 1 ? LHN_PW_F_EXTRA1 : ex.n == 2 ? LHN_PW_F_EXTRA2 : 0u) | (ex.sum_out ? LHN_PW_F_SUM_OUT : 0u) |
+                          (unaligned ? LHN_PW_F_UNALIGNED : 0u)};
+  const unsigned sw = pw_switches();
+  const PwRoute r = pw_fwd_route(sh, sw);
+  LHN_CHECK_ARG(r.path != PW_NONE, "lhn_conv_pw_fwd: unsupported channels Cin=%d Cout=%d (%d extra sources)", Cin, Cout, ex.n);
+  hipStream_t s = (hipStream_t)stream;
+  int rc = r.path == PW_HEAD ? lhn_head_fwd(x, w, bias, y_nchw, Cout, HoWo, bstride, s) : 0;
+  for (int co0 = 0; r.path == PW_SLICED && co0 < Cout && !rc; co0 += 128) {
+    for (int k0 = 0; k0 < Cin && !rc; k0 += r.kstep) {
+      PwSlice t = pw_slice(sh, r.kstep, co0, k0);
+      const bool last = k0 + t.kc >= Cin;
+      lhn_view xv = *x, yv = *y;
+      xv.coff += k0;
+      xv.C = t.kc;
+      if (!y_nchw) {
+        yv.coff += co0;
+        yv.C = t.cc;
+      }
+      t.g.yacc = k0 > 0;
+      t.g.nchw_bstride = bstride;
+      rc = pw_fwd_launch(pw_fwd_inst(sh, sw, r.kstep, co0, k0), &xv, w + (int64_t)co0 * wcols + k0, (last && bias) ? bias + co0 : nullptr,
+                         &yv, (last && stats) ? stats + co0 : nullptr, stride, y_nchw ? y_nchw + (int64_t)co0 * HoWo : nullptr, t.cc,
+                         single ? fin : nullptr, t.g, s, &ex);
+    }
+  }
+  if (rc) return rc;
+  LHN_CHECK_LAUNCH("lhn_conv_pw_fwd");
+  if (r.separate_finalize)
+    return lhn_bn_finalize(stats, fin->gamma, fin->beta, fin->running_mean, fin->running_var, fin->num_batches_tracked, fin->table,
+                           fin->cstride, fin->coff, fin->C, fin->save_mean_invstd, fin->count, fin->eps, fin->momentum, fin->slope,
+                           1, fin->conv_bias, stream);
+  return 0;
+}
+
+// fin: the BatchNorm-backward finalize of y (lhn_bnbwdsrc).  gs: gate-gradient sums of x's buffer (lhn_gatesum): the caller finds the
+// same sums whichever kernel ran.  flags: LHN_PW_BWD_DZ_DEAD.
 static int pw_bwd_run(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate, float* dw,
                       float* dbias, int stride, const float* dy_nchw, int nrep, int64_t rep_stride, const lhn_pw_opts* opts,
-                      const lhn_bnsum* bns, const lhn_bnbwdsrc* fin, const lhn_gatesum* gs, bool* gs_done, int flags, void* stream);
-// gs: gate-gradient sums of x's buffer (lhn_gatesum).  The streaming head kernel adds them in its launch; any other kernel is
-// followed by the lhn_gate_bwd_reduce3 launch over (x, dx) from here, so the caller finds the same sums whichever kernel ran.
-extern "C" int lhn_conv_pw_bwd5(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
-                                int dx_accumulate, float* dw, float* dbias, int stride, const float* dy_nchw, int nrep,
-                                int64_t rep_stride, const lhn_pw_opts* opts, const lhn_bnsum* bns, const lhn_bnbwdsrc* fin,
-                                const lhn_gatesum* gs, void* stream) {
-  return lhn_conv_pw_bwd6(x, w, y, gy, dx, dx_accumulate, dw, dbias, stride, dy_nchw, nrep, rep_stride, opts, bns, fin, gs, 0, stream);
-}
-// flags: LHN_PW_BWD_DZ_DEAD -- the wide register-W instances then run without their dy store (every other path forms dy where it
-// always did: the split path and k_dy_inplace need it in memory, k_pw_bwd and the narrow instances never stored it)
-extern "C" int lhn_conv_pw_bwd6(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
-                                int dx_accumulate, float* dw, float* dbias, int stride, const float* dy_nchw, int nrep,
-                                int64_t rep_stride, const lhn_pw_opts* opts, const lhn_bnsum* bns, const lhn_bnbwdsrc* fin,
-                                const lhn_gatesum* gs, int flags, void* stream) {
+                      const lhn_bnsum* bns, const lhn_bnbwdsrc* fin, const lhn_gatesum* gs, int flags, void* stream) {
+  static const char* const sums_text =
+      "lhn_conv_pw_bwd3: BatchNorm sums ride in the fused kernel only (stride 1, a stored dx, Cin and Cout <= 128 in tiles below 64 x 128, ungated input inside the producer's channels)";
   if (gs && !gs->dgate) gs = nullptr;
   // (dx accumulated: the head kernel would sum this call's part of dx, the reduce launch the whole buffer -- refused, so the
   // result cannot depend on the route; the executor only ever passes the stored mode)
   if (gs) LHN_CHECK_ARG(lhn_view_ok(x) && dx && !dx_accumulate && stride == 1 && (!gs->slices || (gs->slices->n >= 0 && gs->slices->n <= 2)),
                         "lhn_conv_pw_bwd5: gate sums need a stored dx (no accumulate), stride 1 and 0..2 BatchNorm slices");
-  bool gs_done = false;
-  const int rc = pw_bwd_run(x, w, y, gy, dx, dx_accumulate, dw, dbias, stride, dy_nchw, nrep, rep_stride, opts, bns, fin, gs, &gs_done, flags, stream);
-  if (rc || !gs || gs_done) return rc;
-  lhn_view xv = *x;
-  xv.gate = nullptr;
-  return lhn_gate_bwd_reduce3(&xv, dx, gs->dgate, gs->dgate + (size_t)x->N * x->cstride, gs->slices, 1, stream);
-}
-static int pw_bwd_run(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate, float* dw,
-                      float* dbias, int stride, const float* dy_nchw, int nrep, int64_t rep_stride, const lhn_pw_opts* opts,
-                      const lhn_bnsum* bns, const lhn_bnbwdsrc* fin, const lhn_gatesum* gs, bool* gs_done, int flags, void* stream) {
   if (nrep < 1) nrep = 1;
   if (fin && !fin->sums) fin = nullptr;
   lhn_bnsum bs;
   memset(&bs, 0, sizeof(bs));
   if (bns && bns->sums) {
-    LHN_CHECK_ARG(x && y && bns->save && dx && stride == 1 && x->C <= 128 && y->C <= 128 && x->C * y->C < 64 * 128 && !x->gate && x->table &&
-                      bns->coff >= 0 && bns->coff + x->C <= bns->C,
-                  "lhn_conv_pw_bwd3: BatchNorm sums ride in the fused kernel only (stride 1, Cin * Cout < 8192, ungated input inside the producer's channels)");
+    LHN_CHECK_ARG(x && y && bns->save && dx && stride == 1 && x->C <= 128 && y->C <= 128 && !x->gate && x->table && bns->coff >= 0 &&
+                      bns->coff + x->C <= bns->C,
+                  "%s", sums_text);
     bs = *bns;
   }
   LHN_CHECK_ARG(lhn_view_ok(x) && w && y && gy && dw && lhn_no_pend(x) && lhn_no_pend(y), "lhn_conv_pw_bwd: bad view / null pointer");
@@ -1474,111 +1508,190 @@ static int pw_bwd_run(const lhn_view* x, const float* w, const lhn_view* y, cons
   LHN_CHECK_ARG(wcols <= Cin && wcols > Cin - 4 && wrows <= Cout, "lhn_conv_pw_bwd: weight [%d][%d] does not fit views %d -> %d",
                 wrows, wcols, Cin, Cout);
   const int64_t bstride = (opts && opts->nchw_batch_stride > 0) ? opts->nchw_batch_stride : (int64_t)Cout * HoWo;
-  hipStream_t s = (hipStream_t)stream;
-  const bool wr_wide = !bs.sums && stride == 1 && !dy_nchw && wcols == Cin && wrows == Cout && !pw_bwd_split_forced() && !pw_wr_off() &&
-                       ((Cin == 128 && Cout == 128) || (Cin == 64 && Cout == 128) || (Cin == 128 && Cout == 64));
-  const bool wr_narrow = stride == 1 && !dy_nchw && wcols == Cin && wrows == Cout && Cin == Cout && (Cin == 64 || Cin == 32) &&
-                         !pw_bwd_narrow_off() && !pw_wr_off();
-  // the heatmap head (128 -> <= 32 features from NCHW planes) on its streaming kernel: dx, dW, dbias and the gate sums of x's buffer
-  // in ONE launch (k_conv_head.hip).  Not under LHN_HEAD_STREAM=0 or LHN_PW_LDSW=1.  Gate sums only where a tile stays inside an image, and not in
-  // deterministic mode: an image's sums have several writers there (dW and dbias have one writer per replica: at most 4 workgroups).
-  if (dy_nchw && lhn_head_stream_on() && !pw_wr_off() && stride == 1 && !bs.sums && !fin && Cin == HEAD_CIN && wcols == Cin && Cout <= 32 && wrows == Cout &&
-      HoWo % 4 == 0 && bstride % 4 == 0 && (!gs || (HoWo % 64 == 0 && !lhn_deterministic_mode())) &&
-      ((reinterpret_cast<uintptr_t>(dy_nchw) | reinterpret_cast<uintptr_t>(x->data)) & 15) == 0) {
-    const int rc = lhn_head_bwd(x, w, dy_nchw, dx, dx_accumulate, dw, dbias, Cout, HoWo, bstride, nrep, rep_stride, gs, s);
-    if (rc) return rc;
-    LHN_CHECK_LAUNCH("lhn_conv_pw_bwd");
-    *gs_done = gs != nullptr;
-    return 0;
-  }
-  if (fin) {
+  if (fin)
     LHN_CHECK_ARG(!dy_nchw && gy->coef && fin->save_mean_invstd && fin->count > 0 && fin->stat_channels >= Cout,
                   "lhn_conv_pw_bwd4: finalize source needs gy->coef, saved statistics and stat_channels >= Cout");
-    if (!wr_wide && !wr_narrow) {      // no in-prologue fold on this path: the separate launch, then as ever
-      const int rc = lhn_bn_bwd_finalize2(fin->sums, fin->gamma, fin->save_mean_invstd, const_cast<float*>(gy->coef), y->cstride, y->coff,
-                                          Cout, fin->stat_channels, fin->count, fin->dgamma, fin->dbeta, fin->pgrad_scale, stream);
-      if (rc) return rc;
-      fin = nullptr;
-    }
-  }
-  // wide shapes with both sides <= 128: one register-W launch (decided here, before any launch; LHN_PW_BWD_SPLIT=1 and
-  // LHN_PW_LDSW=1, which means "no register-W kernel", keep the split path)
-  if (wr_wide) {
-    int rc = -1;
-#define PWB_WIDE(CI, CO, PXV, PFV) \
-  if (Cin == CI && Cout == CO)     \
-    rc = dz_dead ? launch_pw_bwd_wr<CI, CO, PXV, PFV, false>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs, fin) \
-                 : launch_pw_bwd_wr<CI, CO, PXV, PFV, true>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs, fin);
-    const bool dz_dead = (flags & LHN_PW_BWD_DZ_DEAD) != 0;      // dy stays in LDS: dz is only read
-    PWB_WIDE(128, 128, 32, 1) PWB_WIDE(64, 128, 64, 1) PWB_WIDE(128, 64, 64, 2)
-#undef PWB_WIDE
-    if (rc == 0) {
-      LHN_CHECK_LAUNCH("lhn_conv_pw_bwd");
-      return 0;
-    }
-    if (rc > 0) return rc;
-  }
-  // 64 -> 64 and 32 -> 32, with or without reader-side sums: the narrow register-W instances (LHN_PW_BWD_NARROW=0 and
-  // LHN_PW_LDSW=1 keep k_pw_bwd; so do stride 2, the NCHW head and partial channel counts).  The BNS instances compile the
-  // gate on x out: they rely on the `!x->gate` condition for sums checked at the top of this function -- if that check is
-  // ever relaxed, gated sums calls must leave this branch
-  if (wr_narrow) {
-    int rc;
-    if (Cin == 64) rc = bs.sums ? launch_pw_bwd_wr<64, 64, 64, 2, false, true>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs, fin)
-                                : launch_pw_bwd_wr<64, 64, 64, 2, false, false>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs, fin);
-    else rc = bs.sums ? launch_pw_bwd_wr<32, 32, 128, 2, false, true>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs, fin)
-                      : launch_pw_bwd_wr<32, 32, 128, 2, false, false, 3>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs, fin);
+  const bool unaligned = dy_nchw && (bstride % 4 != 0 || ((reinterpret_cast<uintptr_t>(dy_nchw) | reinterpret_cast<uintptr_t>(x->data)) & 15) != 0);
+  const PwShape sh = {x->N, x->H, x->W, HoWo, Cin, Cout, stride, wcols, wrows,
+                      (dy_nchw ? LHN_PW_F_NCHW : 0u) | (bs.sums ? LHN_PW_F_BNSUM : 0u) | (fin ? LHN_PW_F_FIN : 0u) | (gs ? LHN_PW_F_GATESUM : 0u) |
+                          (dx ? 0u : LHN_PW_F_NO_DX) | (dx_accumulate ? LHN_PW_F_DX_ACC : 0u) | ((flags & LHN_PW_BWD_DZ_DEAD) ? LHN_PW_F_DZ_DEAD : 0u) |
+                          (dbias ? LHN_PW_F_DBIAS : 0u) | (unaligned ? LHN_PW_F_UNALIGNED : 0u)};
+  const PwRoute r = pw_bwd_route(sh, pw_switches());
+  LHN_CHECK_ARG(r.path != PW_NONE, "%s", sums_text);      // (the sums are what has no instance everywhere)
+  if (r.separate_finalize) {
+    const int rc = lhn_bn_bwd_finalize2(fin->sums, fin->gamma, fin->save_mean_invstd, const_cast<float*>(gy->coef), y->cstride, y->coff,
+                                        Cout, fin->stat_channels, fin->count, fin->dgamma, fin->dbeta, fin->pgrad_scale, stream);
     if (rc) return rc;
-    LHN_CHECK_LAUNCH("lhn_conv_pw_bwd");
-    return 0;
+    fin = nullptr;
   }
-  if (!bs.sums && stride == 1 && !dy_nchw && Cin * Cout >= 64 * 128 && Cout % 32 == 0 && Cin % 32 == 0 && Cout <= 256 && wcols == Cin && wrows == Cout) {
-    const int rc = lhn_pw_bwd_split(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s);
-    if (rc == 0) {
-      LHN_CHECK_LAUNCH("lhn_conv_pw_bwd");
-      return 0;
-    }
-    if (rc > 0) return rc;
-  }
-  for (int co0 = 0; co0 < Cout; co0 += 128) {
-    const int cc = Cout - co0 < 128 ? Cout - co0 : 128, nto = (cc + 31) / 32 == 3 ? 4 : (cc + 31) / 32;
-    for (int k0 = 0; k0 < Cin; k0 += 128) {
-      const int kc = Cin - k0 < 128 ? Cin - k0 : 128, ci = kc <= 32 ? 32 : pw_cin_tile(kc);   // (no 16-wide backward tile)
-      lhn_view xv = *x, yv = *y;
-      xv.coff += k0;
-      xv.C = kc;
-      if (!dy_nchw) {
-        yv.coff += co0;
-        yv.C = cc;
+  hipStream_t s = (hipStream_t)stream;
+  int rc = 0;
+  switch (r.path) {
+    case PW_HEAD: rc = lhn_head_bwd(x, w, dy_nchw, dx, dx_accumulate, dw, dbias, Cout, HoWo, bstride, nrep, rep_stride, gs, s); break;
+    case PWB_WIDE:
+    case PWB_NARROW:
+      switch (PW_BWD_WR_KEY(Cin, Cout, r.dyst, r.bns)) {
+#define X(CI, CO, PXV, PFV, DY, BN, OC) \
+  case PW_BWD_WR_KEY(CI, CO, DY, BN): rc = launch_pw_bwd_wr<CI, CO, PXV, PFV, DY, BN, OC>(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, s, bs, fin); break;
+        PW_BWD_WR_INSTANCES(X)
+#undef X
       }
-      PwGeom g;
-      g.wstride = wcols;
-      g.kvalid = wcols - k0 < kc ? wcols - k0 : kc;
-      g.wrows = wrows - co0 < cc ? (wrows - co0 < 0 ? 0 : wrows - co0) : cc;
-      g.yacc = 0;
-      g.statC = Cout;
-      g.nchw_bstride = bstride;
-      const float* wv = w + (int64_t)co0 * wcols + k0;
-      float* dwv = dw + (int64_t)co0 * wcols + k0;
-      float* dbv = (dbias && k0 == 0) ? dbias + co0 : nullptr;
-      const float* dyv = dy_nchw ? dy_nchw + (int64_t)co0 * HoWo : nullptr;
-      const int acc = dx_accumulate || co0 > 0;
-      int rc = -1;
+      break;
+    case PWB_SPLIT: rc = lhn_pw_bwd_split(x, w, y, gy, dx, dx_accumulate, dw, dbias, nrep, rep_stride, r.dgrad, s); break;
+    default:
+      for (int co0 = 0; co0 < Cout && !rc; co0 += 128) {
+        for (int k0 = 0; k0 < Cin && !rc; k0 += 128) {
+          PwSlice t = pw_slice(sh, 128, co0, k0);
+          lhn_view xv = *x, yv = *y;
+          xv.coff += k0;
+          xv.C = t.kc;
+          if (!dy_nchw) {
+            yv.coff += co0;
+            yv.C = t.cc;
+          }
+          t.g.nchw_bstride = bstride;
+          const float* wv = w + (int64_t)co0 * wcols + k0;
+          float* dwv = dw + (int64_t)co0 * wcols + k0;
+          float* dbv = (dbias && k0 == 0) ? dbias + co0 : nullptr;
+          const float* dyv = dy_nchw ? dy_nchw + (int64_t)co0 * HoWo : nullptr;
+          const int acc = dx_accumulate || co0 > 0;
+          switch (pw_bwd_cin_tile(t.kc) * 10 + pw_feature_tiles(t.cc)) {
 #define PWB_CASE(CI, NTV) \
-  if (ci == CI && nto == NTV) rc = launch_pw_bwd<CI, NTV>(&xv, wv, &yv, gy, dx, acc, dwv, dbv, stride, dyv, cc, nrep, rep_stride, g, s, bs);
-      PWB_CASE(32, 1) PWB_CASE(32, 2) PWB_CASE(32, 4) PWB_CASE(64, 1) PWB_CASE(64, 2) PWB_CASE(64, 4) PWB_CASE(128, 1)
-      PWB_CASE(128, 2) PWB_CASE(128, 4)
+  case CI * 10 + NTV: rc = launch_pw_bwd<CI, NTV>(&xv, wv, &yv, gy, dx, acc, dwv, dbv, stride, dyv, t.cc, nrep, rep_stride, t.g, s, bs); break;
+            PWB_CASE(32, 1) PWB_CASE(32, 2) PWB_CASE(32, 4) PWB_CASE(64, 1) PWB_CASE(64, 2) PWB_CASE(64, 4) PWB_CASE(128, 1)
+            PWB_CASE(128, 2) PWB_CASE(128, 4)
 #undef PWB_CASE
-      LHN_CHECK_ARG(rc != -1, "lhn_conv_pw_bwd: unsupported channels Cin=%d Cout=%d", Cin, Cout);
-      if (rc) return rc;
-    }
+          }
+        }
+      }
   }
+  if (rc) return rc;
   LHN_CHECK_LAUNCH("lhn_conv_pw_bwd");
-  return 0;
+  if (!r.gate_reduce_after) return 0;
+  lhn_view xv = *x;
+  xv.gate = nullptr;
+  return lhn_gate_bwd_reduce3(&xv, dx, gs->dgate, gs->dgate + (size_t)x->N * x->cstride, gs->slices, 1, stream);
 }
 
+// =====================================================================================================
+// Entry points.  The numbered forms differ in what a call may carry; each forwards to the widest.
+extern "C" int lhn_conv_pw_fwd(const lhn_view* x, const float* w, const float* bias, const lhn_view* y, double* stats,
+                               int stride, float* y_nchw, const lhn_bnfin* fin, void* stream) {
+  return lhn_conv_pw_fwd2(x, w, bias, y, stats, stride, y_nchw, fin, nullptr, stream);
+}
+extern "C" int lhn_conv_pw_fwd2(const lhn_view* x, const float* w, const float* bias, const lhn_view* y, double* stats,
+                                int stride, float* y_nchw, const lhn_bnfin* fin, const lhn_pw_opts* opts, void* stream) {
+  return pw_fwd_run(x, w, bias, y, stats, stride, y_nchw, fin, opts, stream);
+}
 extern "C" int lhn_conv_pw_bwd(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
                                int dx_accumulate, float* dw, float* dbias, int stride, const float* dy_nchw, int nrep,
                                int64_t rep_stride, void* stream) {
-  return lhn_conv_pw_bwd2(x, w, y, gy, dx, dx_accumulate, dw, dbias, stride, dy_nchw, nrep, rep_stride, nullptr, stream);
+  return lhn_conv_pw_bwd6(x, w, y, gy, dx, dx_accumulate, dw, dbias, stride, dy_nchw, nrep, rep_stride, nullptr, nullptr, nullptr, nullptr, 0, stream);
+}
+extern "C" int lhn_conv_pw_bwd2(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
+                                int dx_accumulate, float* dw, float* dbias, int stride, const float* dy_nchw, int nrep,
+                                int64_t rep_stride, const lhn_pw_opts* opts, void* stream) {
+  return lhn_conv_pw_bwd6(x, w, y, gy, dx, dx_accumulate, dw, dbias, stride, dy_nchw, nrep, rep_stride, opts, nullptr, nullptr, nullptr, 0, stream);
+}
+extern "C" int lhn_conv_pw_bwd3(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
+                                int dx_accumulate, float* dw, float* dbias, int stride, const float* dy_nchw, int nrep,
+                                int64_t rep_stride, const lhn_pw_opts* opts, const lhn_bnsum* bns, void* stream) {
+  return lhn_conv_pw_bwd6(x, w, y, gy, dx, dx_accumulate, dw, dbias, stride, dy_nchw, nrep, rep_stride, opts, bns, nullptr, nullptr, 0, stream);
+}
+extern "C" int lhn_conv_pw_bwd4(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
+                                int dx_accumulate, float* dw, float* dbias, int stride, const float* dy_nchw, int nrep,
+                                int64_t rep_stride, const lhn_pw_opts* opts, const lhn_bnsum* bns, const lhn_bnbwdsrc* fin, void* stream) {
+  return lhn_conv_pw_bwd6(x, w, y, gy, dx, dx_accumulate, dw, dbias, stride, dy_nchw, nrep, rep_stride, opts, bns, fin, nullptr, 0, stream);
+}
+extern "C" int lhn_conv_pw_bwd5(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
+                                int dx_accumulate, float* dw, float* dbias, int stride, const float* dy_nchw, int nrep,
+                                int64_t rep_stride, const lhn_pw_opts* opts, const lhn_bnsum* bns, const lhn_bnbwdsrc* fin,
+                                const lhn_gatesum* gs, void* stream) {
+  return lhn_conv_pw_bwd6(x, w, y, gy, dx, dx_accumulate, dw, dbias, stride, dy_nchw, nrep, rep_stride, opts, bns, fin, gs, 0, stream);
+}
+extern "C" int lhn_conv_pw_bwd6(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
+                                int dx_accumulate, float* dw, float* dbias, int stride, const float* dy_nchw, int nrep,
+                                int64_t rep_stride, const lhn_pw_opts* opts, const lhn_bnsum* bns, const lhn_bnbwdsrc* fin,
+                                const lhn_gatesum* gs, int flags, void* stream) {
+  return pw_bwd_run(x, w, y, gy, dx, dx_accumulate, dw, dbias, stride, dy_nchw, nrep, rep_stride, opts, bns, fin, gs, flags, stream);
+}
+
+// Host only: the names of what pw_fwd_run / pw_bwd_run would launch, in order (include/lhn.h).
+extern "C" const char* lhn_conv_pw_route(int backward, int N, int H, int W, int Cin, int Cout, int stride, int w_rows, int w_cols,
+                                         int features, int switches) {
+  if (stride != 1 && stride != 2) return nullptr;
+  const PwShape sh = {N, H, W, ((H + stride - 1) / stride) * ((W + stride - 1) / stride), Cin, Cout, stride, w_cols > 0 ? w_cols : Cin,
+                      w_rows > 0 ? w_rows : Cout, (unsigned)features};
+  const unsigned sw = switches < 0 ? pw_switches() : (unsigned)switches;
+  const PwRoute r = (backward ? pw_bwd_route : pw_fwd_route)(sh, sw);
+  if (r.path == PW_NONE) return nullptr;
+  static thread_local char buf[768];
+  size_t len = 0;
+  char run[96] = "", cur[96];
+  int reps = 0;
+  auto flush = [&] {      // the pending name, " x n" for a repeated launch
+    if (!reps) return;
+    len += snprintf(buf + len, sizeof(buf) - len, reps > 1 ? "%s%s x %d" : "%s%s", len ? " + " : "", run, reps);
+    if (len >= sizeof(buf)) len = sizeof(buf) - 1;
+    reps = 0;
+  };
+  auto emit = [&](const char* name) {
+    if (reps && strcmp(run, name) != 0) flush();
+    snprintf(run, sizeof(run), "%s", name);
+    ++reps;
+  };
+  auto fwd_name = [&](const PwInst& i) {
+    snprintf(cur, sizeof(cur), "%s<%d, %d, %d>", i.wr ? "k_pw_fwd_wr" : "k_pw_fwd", i.ci, i.nt, i.ns);
+    emit(cur);
+  };
+  const char* const tf[] = {"false", "true"};
+  buf[0] = 0;
+  if (r.separate_finalize && backward) emit("lhn_bn_bwd_finalize2");
+  switch (r.path) {
+    case PW_HEAD:
+      snprintf(cur, sizeof(cur), "k_head_bwd<%s>", tf[(features & LHN_PW_F_GATESUM) != 0]);
+      emit(backward ? cur : "k_head_fwd");
+      break;
+    case PWB_WIDE:
+    case PWB_NARROW:
+      switch (PW_BWD_WR_KEY(Cin, Cout, r.dyst, r.bns)) {
+#define X(CI, CO, PXV, PFV, DY, BN, OC) case PW_BWD_WR_KEY(CI, CO, DY, BN): emit("k_pw_bwd_wr<" #CI ", " #CO ", " #PXV ", " #PFV ", " #DY ", " #BN ", " #OC ">"); break;
+        PW_BWD_WR_INSTANCES(X)
+#undef X
+      }
+      break;
+    case PWB_SPLIT: {
+      emit("k_dy_inplace");
+      const int ntd = Cin >= 128 ? 4 : (Cin + 31) / 32, nto = Cout >= 128 ? 4 : (Cout + 31) / 32, cc = Cout < 128 ? Cout : 128, kc = Cin < 128 ? Cin : 128;
+      const int nco = r.dgrad == LHN_PW_DGRAD_WR256 ? 1 : (Cout + 127) / 128, nk = (Cin + 127) / 128;
+      for (int j = 0; r.dgrad != LHN_PW_DGRAD_NONE && j < nco * (r.dgrad == LHN_PW_DGRAD_KXK ? 1 : nk); ++j) {
+        if (r.dgrad == LHN_PW_DGRAD_KXK) {
+          snprintf(cur, sizeof(cur), "k_kxk<%d, %d, 1, 1, true>", cc, ntd);
+          emit(cur);
+        } else {
+          fwd_name(pw_wr_instance(r.dgrad == LHN_PW_DGRAD_WR256 ? 256 : cc, kc, false));
+        }
+      }
+      snprintf(cur, sizeof(cur), "k_kxk_wgrad<%d, %d, 1, true>", kc, nto);
+      for (int j = 0; j < nk; ++j) emit(cur);
+      break;
+    }
+    default:
+      for (int co0 = 0; co0 < Cout; co0 += 128)
+        for (int k0 = 0; k0 < Cin; k0 += r.kstep) {
+          if (!backward) {
+            fwd_name(pw_fwd_inst(sh, sw, r.kstep, co0, k0));
+            continue;
+          }
+          const PwSlice t = pw_slice(sh, 128, co0, k0);
+          const bool nchw = features & LHN_PW_F_NCHW;
+          snprintf(cur, sizeof(cur), "k_pw_bwd<%d, %d, %s, %s>", pw_bwd_cin_tile(t.kc), pw_feature_tiles(t.cc), tf[nchw], tf[!nchw && (features & LHN_PW_F_BNSUM)]);
+          emit(cur);
+          if (nchw && k0 == 0 && (features & LHN_PW_F_DBIAS)) emit("k_bias_grad_nchw");
+        }
+  }
+  if (r.separate_finalize && !backward) emit("lhn_bn_finalize");
+  if (r.gate_reduce_after) emit("lhn_gate_bwd_reduce3");
+  flush();
+  return buf;
 }

@@ -73,6 +73,26 @@ static inline bool lhn_dw_force_gather() {
   }
   return v == 1;
 }
+// The 1x1 convolution's cross-file functions.  pw_fwd_route / pw_bwd_route (k_conv_pw.hip) alone decide which a call reaches.
+bool lhn_head_stream_on();      // LHN_HEAD_STREAM, as pw_switches() read it
+// the shapes of the heatmap head's streaming kernels (k_conv_head.hip): 128 input channels, at most 32 features, whole weight
+constexpr int HEAD_CIN = 128;
+static inline bool lhn_head_shape(int Cin, int Cout, int wcols, int wrows) { return Cin == HEAD_CIN && Cout <= 32 && wcols == Cin && wrows == Cout; }
+int lhn_head_fwd(const lhn_view* x, const float* w, const float* bias, float* y_nchw, int cout, int HoWo, int64_t bstride, hipStream_t s);
+int lhn_head_bwd(const lhn_view* x, const float* w, const float* dy, float* dx, int dx_acc, float* dw, float* dbias, int cout, int HoWo,
+                 int64_t bstride, int nrep, int64_t rep_stride, const lhn_gatesum* gs, hipStream_t s);
+// Data gradient on the register-W forward kernel: dx[.., ci0 + n] (+)= sum_k dy[.., k] * W[co0 + k][ci0 + n].  dyv: the plain dy as a view
+// of 32/64/128/256 output features, dxv: <= 128 input channels of the gradient buffer, w = &W[co0][ci0], wstride = the weight's Cin.
+int lhn_pw_dgrad_wr(const lhn_view* dyv, const float* w, const lhn_view* dxv, int wstride, int accumulate, hipStream_t s);
+// The three-launch backward (k_conv_kxk.hip).  dgrad: the kernel every output slice's data gradient takes
+enum { LHN_PW_DGRAD_NONE = 0,      // dx is NULL
+       LHN_PW_DGRAD_WR256,         // lhn_pw_dgrad_wr over all K = 256 output features at once
+       LHN_PW_DGRAD_WR,            // lhn_pw_dgrad_wr per slice of <= 128 output features, later slices accumulating
+       LHN_PW_DGRAD_KXK };         // k_kxk with one tap
+int lhn_pw_bwd_split(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate,
+                     float* dw, float* dbias, int nrep, int64_t rep_stride, int dgrad, hipStream_t s);
+// its one-tap instances of k_kxk and k_kxk_wgrad: k = the slice's K (output features / input channels), nt = 32-wide tiles per block
+static inline bool lhn_pw_split_instance(int k, int nt) { return (k == 64 && (nt == 4 || nt == 2)) || (k == 128 && (nt == 4 || nt == 2 || nt == 1)) || (k == 32 && nt == 4); }
 // k_bottleneck.hip: lhn_bottleneck_fwd with the choice of skipping the tap-major copy of w2 (relayout = 0: wt_scratch holds it already)
 int lhn_bottleneck_fwd_impl(const lhn_view* x, int Cm, const float* w1, const float* b1, const float* t1, const float* w2, const float* t2,
                             const float* w3, const float* b3, const float* t3, float out_slope, const lhn_view* y, float* wt_scratch,

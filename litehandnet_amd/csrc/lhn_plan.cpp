@@ -143,12 +143,12 @@ static bool bwd_fin_consumer() {
 // else by the same lhn_gate_bwd_reduce3 launch) and the GATE_REDUCE op is not launched.  CA_MLP_BWD reads the same arena.  Like the
 // consumer-side finalize above this is decided here and not in the plan compiler: the op lists do not change.  Whole-plan runs only.
 // Variant B: the pass over neck[1]'s buffer, 8 -> 7 k_gate_bwd_reduce launches per step.
-bool lhn_head_stream_on();
 static bool head_gate_fold_at(const Plan* P, const std::vector<lhn_op>& ops, size_t oi) {
   if (!lhn_head_stream_on() || lhn_deterministic_mode() || oi + 1 >= ops.size()) return false;
   const lhn_op &o = ops[oi], &nx = ops[oi + 1];
   if (o.kind != OP_PW_BWD || !o.i[1] || o.i[0] != 1 || o.i[2] != 1 || o.in_buf[0] < 0) return false;
-  if (o.in_C[0] != 128 || o.out_C > 32 || o.i[3] || o.i[4]) return false;      // the shapes k_head_bwd serves: every other head keeps its GATE_REDUCE op
+  // the shapes k_head_bwd serves (no w_cols / w_rows given: the whole weight): every other head keeps its GATE_REDUCE op
+  if (o.i[3] || o.i[4] || !lhn_head_shape(o.in_C[0], o.out_C, o.in_C[0], o.out_C)) return false;
   const lhn_buf& b = P->bufs[o.in_buf[0]];
   return o.in_coff[0] == 0 && o.in_C[0] == b.C && b.gate_off >= 0 && nx.kind == OP_GATE_REDUCE && nx.out_buf == o.in_buf[0] &&
          nx.out_coff == 0 && nx.out_C == b.C && nx.ws[3] >= 0 && nx.ws[4] >= 0;

@@ -1723,13 +1723,11 @@ class PlanBuilder:
                 not any(a[0] == id(q) for a in pending_add.get(t.buf, ())) and \
                 q["out"].H % t.H == 0 and q["out"].W % t.W == 0
         if q["op"] == PW:
-            # (the fused 1x1 backward kernel keeps the shapes whose TILES stay below 64 x 128: csrc/k_conv_pw.hip)
-            ci_t = 32 if t.C <= 32 else 64 if t.C <= 64 else 128
-            nto = (q["out"].C + 31) // 32
-            nto = 4 if nto == 3 else nto
-            return q["stride"] == 1 and not q.get("nchw") and q.get("xs") is None and t.C <= 128 and \
-                q["out"].C <= 128 and ci_t * nto * 32 < 64 * 128 and not q["wrc"][1] and not q["wrc"][0] and \
-                (t.coff, t.C) == (q["x"].coff, q["x"].C)
+            # (which shapes have a backward kernel that takes the sums is the library's answer: lhn_conv_pw_route, feature 64 =
+            # LHN_PW_F_BNSUM, the switches as the process read them -- the answer does not depend on them)
+            return not q.get("nchw") and q.get("xs") is None and not q["wrc"][1] and not q["wrc"][0] and \
+                (t.coff, t.C) == (q["x"].coff, q["x"].C) and \
+                _lib.lib().lhn_conv_pw_route(1, 1, t.H, t.W, t.C, q["out"].C, q["stride"], 0, 0, 64, -1) is not None
         return q["op"] in (MAXPOOL, AVGPOOL)
 
     def _reader_bn_sums(self, uses, aliased, pending_add):

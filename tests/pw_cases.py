@@ -3,7 +3,9 @@ CPU (float64, or float32 to measure what the same operation loses in the kernels
 tests/test_pw_gpu.py; run as a script (a child process with its own environment, e.g. LHN_PW_LDSW=1, LHN_PW_K256=0 or
 LHN_DETERMINISTIC=1) it writes the kernel outputs of the named cases to an .npz file:
     python tests/pw_cases.py OUT.npz REPEATS fwd:NAME bwd:NAME ...
-    python tests/pw_cases.py --check-reference        (CPU only: every case's inputs and both references)"""
+    python tests/pw_cases.py --check-reference        (CPU only: every case's inputs and both references)
+    python tests/pw_cases.py --instances              (CPU only: prints profiles/pw_instances.md)
+kernel_of(kind, name) asks the library which kernels a case launches (lhn_conv_pw_route: host only)."""
 import ctypes as C
 import os
 import sys
@@ -107,6 +109,36 @@ BWD_REFUSE = {
 }
 TABLES = {"fwd": FWD, "bwd": BWD}
 _ALL = {"fwd": dict(FWD, **FWD_REFUSE), "bwd": dict(BWD, **BWD_REFUSE)}
+
+
+# LHN_PW_F_* / LHN_PW_SW_* (include/lhn.h)
+F_NCHW, F_STATS, F_EXTRA1, F_EXTRA2, F_SUM_OUT, F_BNSUM, F_FIN, F_GATESUM, F_NO_DX, F_DX_ACC, F_DZ_DEAD, F_UNALIGNED, F_DBIAS = \
+    1, 2, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192
+SW_LDSW, SW_K256, SW_BWD_NARROW, SW_BWD_SPLIT, SW_HEAD_STREAM, SW_DETERMINISTIC = 1, 2, 4, 8, 16, 32
+# the settings a table of profiles/pw_instances.md is printed for: title, kernel_of keywords
+SETTINGS = (("default dispatch", {}), ("`LHN_PW_LDSW=1`", {"ldsw": True}), ("`LHN_PW_K256=0`", {"k256": False}),
+            ("`LHN_PW_BWD_NARROW=0`", {"narrow": False}), ("`LHN_PW_BWD_SPLIT=1`", {"split": True}),
+            ("`LHN_HEAD_STREAM=0`", {"head_stream": False}), ("`LHN_DETERMINISTIC=1`", {"deterministic": True}))
+
+
+def kernel_of(kind, name, extra=0, ldsw=False, k256=True, narrow=True, split=False, head_stream=True, deterministic=False):
+    """The launches of lhn_conv_pw_fwd2 / lhn_conv_pw_bwd3 for a case, in order, asked of the library (lhn_conv_pw_route: host only).
+    extra: further LHN_PW_F_* bits (F_FIN, F_DZ_DEAD).  The keywords are the switches: ldsw: LHN_PW_LDSW=1, k256=False: LHN_PW_K256=0,
+    narrow=False: LHN_PW_BWD_NARROW=0, split: LHN_PW_BWD_SPLIT=1, head_stream=False: LHN_HEAD_STREAM=0, deterministic:
+    LHN_DETERMINISTIC=1.  None: no kernel for the case."""
+    c = _ALL[kind][name]
+    f, (n, h, w) = c["flags"], c["nhw"]
+    if kind == "fwd":       # the LHN_PW_F_* bits of the call run_fwd / run_bwd make
+        feat = (F_NCHW * ("nchw" in f) | F_STATS * ("nostats" not in f) | F_EXTRA1 * ("extras1" in f) | F_EXTRA2 * ("extras2" in f) |
+                F_SUM_OUT * ("extras1" in f or "extras2" in f or "sumonly" in f) | F_UNALIGNED * ("wmis" in f))
+    else:
+        acc = "nodx" not in f and ("acc" in f or (c["stride"] == 2 and "s2store" not in f))
+        feat = (F_NCHW * ("nchw" in f) | F_BNSUM * ("bns" in f) | F_NO_DX * ("nodx" in f) | F_DX_ACC * acc | F_DBIAS * ("dbias" in f) |
+                F_GATESUM * ("slices" in c))
+    sw = (SW_LDSW * ldsw | SW_K256 * k256 | SW_BWD_NARROW * narrow | SW_BWD_SPLIT * split | SW_HEAD_STREAM * head_stream |
+          SW_DETERMINISTIC * deterministic)
+    r = _lib.lib().lhn_conv_pw_route(int(kind == "bwd"), n, h, w, c["cin"], c["cout"], c["stride"], c.get("w_rows", 0), c.get("w_cols", 0), feat | extra, sw)
+    return r.decode() if r is not None else None
 
 
 def _rand(shape, seed, scale=1.0):
@@ -456,9 +488,36 @@ def _check_reference():
     print(f"{sum(len(t) for t in TABLES.values())} cases, no activation kinks at seed 7, worst float32 error {worst:.2e}, {time.time() - t0:.1f} s")
 
 
+def _instances():
+    """profiles/pw_instances.md: one table per direction and switch setting; under a switch only the cases that change their launches."""
+    print("# 1x1 convolution kernels: which test case launches what\n")
+    print("The answers of `lhn_conv_pw_route` (`include/lhn.h`: host only, the route functions every `lhn_conv_pw_*` entry asks) for `FWD` / `BWD` of\n"
+          "`tests/pw_cases.py`, printed by `python tests/pw_cases.py --instances`; `tests/test_pw_route_cpu.py` holds them as a literal table.\n"
+          "Names as a kernel trace prints the template instances, launches in order; ` x n`: a launch that repeats (channel slices).")
+    for kind, title in (("fwd", "Forward"), ("bwd", "Backward")):
+        base = {nm: kernel_of(kind, nm) for nm in TABLES[kind]}
+        for setting, kw in SETTINGS:
+            got = {nm: kernel_of(kind, nm, **kw) for nm in TABLES[kind]}
+            rows = {}
+            for nm, k in got.items():
+                if not kw or k != base[nm]:
+                    rows.setdefault(k, []).append(nm)
+            if not rows:
+                continue
+            print(f"\n## {title}, {setting}" + (": the cases that change their launches" if kw else "") + "\n\n| launches | cases |\n|---|---|")
+            for k, names in rows.items():
+                print(f"| `{k}` | {', '.join(names)} |")
+    print("\n## Refused for lack of a kernel (the query answers NULL)\n")
+    none = [f"{kind}:{nm}" for kind, tab in (("fwd", FWD_REFUSE), ("bwd", BWD_REFUSE)) for nm in tab if kernel_of(kind, nm) is None]
+    print(", ".join(none))
+
+
 if __name__ == "__main__":
     if sys.argv[1] == "--check-reference":
         _check_reference()
+        sys.exit(0)
+    if sys.argv[1] == "--instances":
+        _instances()
         sys.exit(0)
     dst, reps, names = sys.argv[1], int(sys.argv[2]), sys.argv[3:]
     dev = torch.device("cuda:0")
