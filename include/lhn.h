@@ -651,7 +651,11 @@ int lhn_conv_pw_bwd4(const lhn_view* x, const float* w, const lhn_view* y, const
 #define LHN_PW_F_FIN       128   /* backward: a finalize source (lhn_bnbwdsrc) */
 #define LHN_PW_F_GATESUM   256   /* backward: gate sums (lhn_gatesum) */
 #define LHN_PW_F_NO_DX     512   /* backward: dx NULL */
-#define LHN_PW_F_DX_ACC    1024  /* backward: dx accumulated (part of the call's description; no rule of the route reads it today) */
+#define LHN_PW_F_DX_ACC    1024  /* backward: dx accumulated (part of the call's description; no rule of the route reads it.  Behind the
+                                    route, the launcher of the 32 -> 32 instances k_pw_bwd_wr<32, 32, 128, 2, false, BNS, *> sends an
+                                    accumulating call to k_pw_bwd_wr<32, 32, 128, 3, false, BNS, 2>: the prior dx rides in the tile
+                                    prefetch, same bits of dx.  The route's answer names the PF = 2 instance either way.
+                                    LHN_PW_BWD_ACC_PREFETCH=0: the PF = 2 instance itself, dx re-read at the store) */
 #define LHN_PW_F_DZ_DEAD   2048  /* backward: LHN_PW_BWD_DZ_DEAD */
 #define LHN_PW_F_UNALIGNED 4096  /* a pointer the vector paths need at 16 bytes is not (forward: w, y_nchw; backward: dy_nchw, x's data),
                                     or the NCHW batch stride is no multiple of 4 floats */

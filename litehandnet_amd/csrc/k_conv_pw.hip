@@ -853,6 +853,11 @@ static int launch_pw_bwd_t(const lhn_view* x, const float* w, const lhn_view* y,
 //       registers; raw x comes from an LDS copy of the staged tile (Xr, written at commit in these instances only) where k_pw_bwd
 //       re-read it from global memory.  Rows beyond M are zero rows of dYs: their dX is exactly 0 and adds nothing.
 // OCC: workgroups per CU the register budget is cut for (waves per SIMD of __launch_bounds__).
+// PF = 3 (32 -> 32 only, launched for dx_acc != 0 only): the prior dx rides in the prefetch as well, one more tensor of the tile.  It is
+//   loaded in issue() with x's loader geometry, parked by commit() in the LDS tile Pr and read in the C/D layout at the store,
+//   dx = prior + dX: the same fp32 add of the same two values as the read-modify-write `dx += dX` of the other instances, so the bits
+//   of dx are the same.  That read-modify-write's sixteen loads per lane are issued behind issue(next tile), and vmcnt counts in
+//   order: waiting for them waits for the whole prefetch, which then no longer runs under the MFMA phase and the stores.
 template <int CIN, int COUT, int PX, int PF, bool DYST, bool BNS, int OCC>
 __global__ void __launch_bounds__(256, OCC) k_pw_bwd_wr(lhn_view x, const float* __restrict__ w, lhn_view y, lhn_gradview gy,
                                                         float* __restrict__ dx, int dx_acc, float* __restrict__ dw, float* __restrict__ dbias,
@@ -873,6 +878,9 @@ __global__ void __launch_bounds__(256, OCC) k_pw_bwd_wr(lhn_view x, const float*
   float* yt = xt + 3 * CIN;           // [3][COUT]  the same of y
   float* cf = yt + 3 * COUT;          // [3][COUT]  A | B | C
   float* Xr = cf + 3 * COUT;          // [PX][CIN]  raw x of the staged tile (BNS only)
+  float* Pr = Xr + (BNS ? PX * CIN : 0);      // [PX][CIN]  prior dx of the staged tile (PF = 3 only)
+  constexpr bool ACCPF = PF == 3;
+  static_assert(!ACCPF || (ONE && !DYST), "the prior dx in the prefetch: 32 -> 32");
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, lh = lane >> 5;
   const int HoWo = y.H * y.W;
   float* dzw = const_cast<float*>(gy.dz);
@@ -883,12 +891,13 @@ __global__ void __launch_bounds__(256, OCC) k_pw_bwd_wr(lhn_view x, const float*
   const int xc4 = tid % XC4, xr0 = tid / XC4, xabs = x.coff + 4 * xc4;
   const int yc4 = tid % YC4, yr0 = tid / YC4, yabs = y.coff + 4 * yc4;
 
-  f4 xraw[XPF], yraw[YPF], ydz[YPF];
+  f4 xraw[XPF], yraw[YPF], ydz[YPF], praw[ACCPF ? XPF : 1];
   auto issue = [&](int tile) __attribute__((always_inline)) {
 #pragma unroll
     for (int p = 0; p < XPF; ++p) {
       const int m = min(tile * PX + xr0 + p * XRP, M - 1);      // clamped (branch-free); commit() zeroes rows >= M
       xraw[p] = *reinterpret_cast<const f4*>(x.data + (int64_t)m * x.cstride + xabs);
+      if (ACCPF) praw[p] = *reinterpret_cast<const f4*>(dx + (int64_t)m * x.cstride + xabs);      // (rows >= M: never stored)
     }
 #pragma unroll
     for (int p = 0; p < YPF; ++p) {
@@ -913,6 +922,7 @@ __global__ void __launch_bounds__(256, OCC) k_pw_bwd_wr(lhn_view x, const float*
       }
       *reinterpret_cast<f4*>(Xs + row * LDX + 4 * xc4) = v;
       if (BNS) *reinterpret_cast<f4*>(Xr + row * CIN + 4 * xc4) = m < M ? xraw[p] : (f4){0.f, 0.f, 0.f, 0.f};
+      if (ACCPF) *reinterpret_cast<f4*>(Pr + row * CIN + 4 * xc4) = praw[p];
     }
     Xf4 yxf;
     Gr4 ygr;
@@ -1063,7 +1073,19 @@ __global__ void __launch_bounds__(256, OCC) k_pw_bwd_wr(lhn_view x, const float*
             b_q += du * ((raw - b_mean) * b_inv);
           }
         }
-        if (tile * PX + PX <= M) {        // whole tile inside the tensor: stores off one base pointer, no row predicate
+        if constexpr (ACCPF) {            // the prior of this lane's sixteen elements from the LDS tile: no load behind issue(next)
+          const float* pr = Pr + ((mt0 + hh) * 32 + 4 * lh) * CIN + 32 * jt + l31;
+          if (tile * PX + PX <= M) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[((r & 3) + 8 * (r >> 2)) * cs] = pr[((r & 3) + 8 * (r >> 2)) * CIN] + accx[hh][r];
+          } else {                        // the tail tile: rows predicated per lane
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              const int ro = (r & 3) + 8 * (r >> 2);
+              if (mbase + ro < M) o[(int64_t)ro * cs] = pr[ro * CIN] + accx[hh][r];
+            }
+          }
+        } else if (tile * PX + PX <= M) {        // whole tile inside the tensor: stores off one base pointer, no row predicate
           if (dx_acc) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) o[((r & 3) + 8 * (r >> 2)) * cs] += accx[hh][r];
@@ -1158,20 +1180,38 @@ __global__ void __launch_bounds__(256, OCC) k_pw_bwd_wr(lhn_view x, const float*
 // Narrow instances (no dy store; plain and with reader-side sums):
 //   64 -> 64:   PX = 64, x, y and dz prefetched, two workgroups per CU (a third costs spills).
 //   32 -> 32:   PX = 128, x, y and dz prefetched.
+//               An accumulating launch (dx_acc != 0; the stem's b1 -> b3, whose input also feeds the max pool) runs PF = 3, the
+//               prior dx in the prefetch too (LDS + 16 KB), at two workgroups per CU also where the plain instance has three: its
+//               16 more registers do not fit the budget of three.  lhn_conv_pw_route answers with the PF = 2 instance either way.
+//   64 -> 64 keeps the read-modify-write: no plan of the project launches it accumulating, and with sums it has 6 registers left.
+// LHN_PW_BWD_ACC_PREFETCH (default 1), read once.  0: an accumulating 32 -> 32 launch re-reads dx at its store, as before PF = 3.
+static bool pw_bwd_acc_prefetch_on() {
+  static int v = -1;
+  if (v < 0) {
+    const char* e = getenv("LHN_PW_BWD_ACC_PREFETCH");
+    v = (e && e[0] == '0') ? 0 : 1;
+  }
+  return v != 0;
+}
 template <int CIN, int COUT, int PX, int PF, bool DYST = true, bool BNS = false, int OCC = 2>
 static int launch_pw_bwd_wr(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc, float* dw,
-                            float* dbias, int nrep, int64_t rep_stride, hipStream_t s, const lhn_bnsum& bs, const lhn_bnbwdsrc* fsp = nullptr) {
+                            float* dbias, int nrep, int64_t rep_stride, hipStream_t s, const lhn_bnsum& bs, const lhn_bnbwdsrc* fsp = nullptr,
+                            int det_per_cu = 0) {
+  if constexpr (CIN == 32 && COUT == 32 && PF == 2) {      // (deterministic mode: the grid of THIS instance, so that every sum keeps its order)
+    if (dx && dx_acc && pw_bwd_acc_prefetch_on())
+      return launch_pw_bwd_wr<CIN, COUT, PX, 3, DYST, BNS, 2>(x, w, y, gy, dx, dx_acc, dw, dbias, nrep, rep_stride, s, bs, fsp, OCC);
+  }
   const int M = y->N * y->H * y->W, ntiles = (M + PX - 1) / PX;
   lhn_bnbwdsrc fs;
   if (fsp) fs = *fsp; else memset(&fs, 0, sizeof(fs));
-  const size_t lds = (size_t)(PX * (COUT + 4) + PX * (CIN + 4) + 3 * CIN + 6 * COUT + (BNS ? PX * CIN : 0)) * sizeof(float);
+  const size_t lds = (size_t)(PX * (COUT + 4) + PX * (CIN + 4) + 3 * CIN + 6 * COUT + (BNS ? PX * CIN : 0) + (PF == 3 ? PX * CIN : 0)) * sizeof(float);
   static LhnKernelCfg cfg;
   int per_cu = 1;
   if (!lhn_kernel_cfg(cfg, &k_pw_bwd_wr<CIN, COUT, PX, PF, DYST, BNS, OCC>, lds, OCC, &per_cu)) {
     lhn_set_error("lhn_conv_pw_bwd: cannot reserve %zu B of LDS", lds);
     return 2;
   }
-  int grid = lhn_num_cus() * per_cu;
+  int grid = lhn_num_cus() * ((det_per_cu && lhn_deterministic_mode()) ? det_per_cu : per_cu);
   if (grid > ntiles) grid = ntiles;
   hipLaunchKernelGGL((k_pw_bwd_wr<CIN, COUT, PX, PF, DYST, BNS, OCC>), dim3(grid), dim3(256), lds, s, *x, w, *y, *gy, dx, dx_acc, dw, dbias,
                      M, ntiles, nrep, rep_stride, bs, fs);
