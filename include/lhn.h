@@ -313,7 +313,7 @@ int lhn_conv_dw3_pw_fwd(const lhn_view* x, const float* w_dw /*[Cin,1,3,3]*/, in
  * wt_scratch: optional 9*Cm*Cm floats of caller-owned scratch; the call re-lays w2 tap-major into it with one small launch of its own
  * (16-byte weight loads per tap), as lhn_conv_kxk_fwd does.  NULL = the kernel reads the OIHW tensor directly and the call is ONE
  * launch.  (The plan executor skips the re-lay when the parameters have not changed since the run that wrote the scratch.)
- * Built for C == 128 and Cm in {32, 64}, any N, H, W.  Any other channel pair, an out_slope outside [0, 1] (LHN_SLOPE_SILU /
+ * Built for C == 128 with Cm in {32, 64} and C == 256 with Cm in {64, 128}, any N, H, W.  Any other channel pair, an out_slope outside [0, 1] (LHN_SLOPE_SILU /
  * LHN_SLOPE_RELU_SIGMOID) or a y view that overlaps x's channels in the same buffer returns the invalid-argument status
  * ("unsupported shape") before any launch and writes nothing. */
 int lhn_bottleneck_fwd(const lhn_view* x, int Cm, const float* w1 /*[Cm,C]*/, const float* b1 /*[Cm] or NULL*/, const float* t1 /*[3][Cm] or NULL*/,

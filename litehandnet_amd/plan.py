@@ -1065,7 +1065,7 @@ class PlanBuilder:
         return n
 
     # Channel pairs (C, Cm) lhn_bottleneck_fwd is built for (csrc/k_bottleneck.hip: bottleneck_supported); any map size.
-    FUSE_BNECK_CHANNELS = ((128, 32), (128, 64))
+    FUSE_BNECK_CHANNELS = ((128, 32), (128, 64), (256, 64), (256, 128))
 
     def _fusable_bottleneck(self, r1, uses):
         """(r2, r3, ew) when the 1x1 record r1 starts a BottleNeck pattern, else None: 1x1 C -> Cm, 3x3 Cm -> Cm, 1x1 Cm -> C (slope 1),

@@ -3,13 +3,17 @@
 dense 3x3 convolutions on the split-bf16 MFMA (plan.set_infer_bf16x3), and Lite-HRNet with its channel-weighting blocks as grouped
 launches (plan.set_infer_fuse_ccw); LHN_INFER_FUSE / LHN_INFER_FUSE_DWPW / LHN_INFER_FUSE_MSRB / LHN_INFER_FUSE_BNECK / LHN_INFER_FUSE_STEM /
 LHN_INFER_BF16X3 / LHN_INFER_FUSE_CCW in the environment are overridden here.
-python scripts/bench_infer.py [A|B|M|H|L] [bs] [every|off|on|dwpw|both|msrb|all|bneck|full|bf16x3|full+bf16x3|stem|full+stem|ccw|full+ccw] [reduction]
+python scripts/bench_infer.py [A|B|M|H|L] [bs] [every|off|on|dwpw|both|msrb|all|bneck|full|bf16x3|bneck+bf16x3|full+bf16x3|stem|full+stem|ccw|full+ccw] [reduction] [channels]
   off / on / dwpw / both / msrb / all / bneck / full: only the lines of that setting (no fusion / 1x1 -> depthwise / depthwise -> 1x1 /
   those two passes / MSRB rounds / those three passes / BottleNecks / all four passes), for alternating runs in fresh processes; every
   (the default): off and on, dwpw and both where the depthwise -> 1x1 pass finds pairs, msrb and all where the MSRB pass finds rounds,
   bneck and full where the BottleNeck pass finds blocks, bf16x3 and full+bf16x3 (the 3x3 pass alone / on top of the four fusion passes)
   where the model has eligible 3x3 convolutions, stem and full+stem (the stem pass alone / on top of the four fusion passes; `full` keeps
   its meaning) where the stem pass finds its pattern (A, M).  A model without a deployed form (H) runs its eval form only.  reduction: the `reduction` of variant A's Residual blocks (config default 4).
+  channels: the model width (`input_channel`, config default 128; the reference's width-256 configs run 256).  Variant B runs at 256; variant A
+  does not (its Residuals' 256 -> 256 dense 3x3 has no kernel: lhn_conv_kxk_fwd refuses it) -- scripts/bench_bottleneck256.py times A's BottleNecks at
+  that width on their own.  bneck+bf16x3 (only when asked for): the BottleNeck pass and the 3x3 pass together -- the inner 3x3s belong to the
+  BottleNeck launches and stay fp32.  LHN_BENCH_BNECK_CHANNELS="128:32,128:64" restricts the BottleNeck pass to those (C, Cm) classes.
 Launches: kernel launches of one steady-state forward (tables current), and the table-only launches a first forward adds."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -23,13 +27,17 @@ SETTINGS = {"ccw": (False, False, False, False, False, False, True), "full+ccw":
             "dwpw": (False, True, False, False, False, False), "both": (True, True, False, False, False, False),
             "msrb": (False, False, True, False, False, False), "all": (True, True, True, False, False, False),
             "bneck": (False, False, False, True, False, False), "full": (True, True, True, True, False, False),
-            "bf16x3": (False, False, False, False, True, False), "full+bf16x3": (True, True, True, True, True, False),
+            "bf16x3": (False, False, False, False, True, False), "bneck+bf16x3": (False, False, False, True, True, False), "full+bf16x3": (True, True, True, True, True, False),
             "stem": (False, False, False, False, False, True), "full+stem": (True, True, True, True, False, True)}
 variant = sys.argv[1] if len(sys.argv) > 1 else "B"
 bs = int(sys.argv[2]) if len(sys.argv) > 2 else 64
 which = sys.argv[3] if len(sys.argv) > 3 else "every"
 assert which == "every" or which in SETTINGS, which
 cfg_kw = {"reduction": int(sys.argv[4])} if len(sys.argv) > 4 else {}
+if len(sys.argv) > 5:
+    cfg_kw["channels"] = int(sys.argv[5])
+if os.environ.get("LHN_BENCH_BNECK_CHANNELS"):
+    plan.PlanBuilder.FUSE_BNECK_CHANNELS = tuple(tuple(int(v) for v in pair.split(":")) for pair in os.environ["LHN_BENCH_BNECK_CHANNELS"].split(","))
 if os.environ.get("LHN_BENCH_CCW_BRANCHES"):
     plan.PlanBuilder.FUSE_CCW_BRANCHES = tuple(int(v) for v in os.environ["LHN_BENCH_CCW_BRANCHES"].split(","))
 m = get_model(litehandnet_cfg(variant, **cfg_kw)).cuda().eval()
@@ -78,7 +86,7 @@ def timeit(form, setting):
         torch.cuda.synchronize()
         steady, tables, fused, fused_dwpw, fused_msrb, fused_bneck, mb, n_bf16x3, fused_stem, fused_ccw = launches(fuse, dwpw, msrb, bneck, bf16x3, stem, ccw)
         ms = e0.elapsed_time(e1) / 20
-        print(f"{variant}{'' if not cfg_kw else ' r' + str(cfg_kw['reduction'])} bs{bs} {form} [{setting}]: {ms:.3f} ms/fwd (wall {(time.perf_counter() - t0) * 50:.3f}) "
+        print(f"{variant}{''.join(f' {k[0]}{v}' for k, v in cfg_kw.items())} bs{bs} {form} [{setting}]: {ms:.3f} ms/fwd (wall {(time.perf_counter() - t0) * 50:.3f}) "
               f"-> {bs / ms * 1e3:.0f} img/s; {steady} launches (+{tables} table launches on a first run), "
               f"{fused} 1x1->dw + {fused_dwpw} dw->1x1 fused pairs, {fused_msrb} MSRB rounds, {fused_bneck} BottleNecks, {fused_stem} stems, {fused_ccw} channel-weighting blocks (n_fused_ccw), {n_bf16x3} 3x3 on bf16x3; {mb:.2f} MB/image of convolution traffic = {mb * bs / ms / 1e3:.3f} TB/s = "
               f"{mb * bs / ms / 1e3 / 8:.3f} of 8 TB/s", flush=True)
