@@ -91,7 +91,31 @@ typedef struct lhn_bnbwdsrc {
   int32_t       stat_channels;     /* channel stride of sums / save, >= y->C                                                  */
 } lhn_bnbwdsrc;
 
-/* BatchNorm-backward sums contributed by a READER.  du = dz * act'(u) is linear in dz, and dz of a convolution output is the sum
+/* BatchNorm FORWARD finalize on the consumer side.  The table (scale | shift | slope) of a convolution + BatchNorm output is read
+ * first by the next kernel; when that kernel is a depthwise or 1x1 convolution over exactly the BatchNorm's channels,
+ * lhn_conv_dw_fwd4 / lhn_conv_pw_fwd3 take the finished statistics instead of a finalized x->table: every workgroup folds the
+ * replicas of its own input channels in its prologue, while its first tile's loads are in flight (replica order and double arithmetic of
+ * lhn_bn_finalize: same sums, same bits), and one workgroup per channel also stores the table slice, mean | invstd, one momentum
+ * step of the running statistics and num_batches_tracked + 1 -- memory holds what the separate launch leaves, for every later
+ * reader.  The slice must be x's: table == x->table, cstride / coff / C equal to the view's.  Where the launcher picks a kernel
+ * without the in-prologue fold it calls lhn_bn_finalize itself first: the result never depends on the kernel chosen.  NULL pointer
+ * to the struct (or stats == NULL): x->table is read as it is. */
+typedef struct lhn_bnfinsrc {
+  const double* stats;              /* [LHN_STAT_REPLICAS][2][C]: sum | sum of squares, complete before the call               */
+  const float*  gamma;              /* [C] or NULL (= 1)                                                                       */
+  const float*  beta;               /* [C] or NULL (= 0)                                                                       */
+  const float*  conv_bias;          /* bias of the convolution in front of the BatchNorm, or NULL (see lhn_bn_finalize)        */
+  float*        running_mean;       /* [C] or NULL (then running_var is not touched either)                                    */
+  float*        running_var;
+  int64_t*      num_batches_tracked;/* or NULL                                                                                 */
+  float*        table;              /* base of the [3][cstride] table: the slice [coff, coff + C) of each row is written       */
+  float*        save_mean_invstd;   /* [2][C] or NULL                                                                          */
+  double        count;              /* N*H*W of the BatchNorm (times the world size under SyncBatchNorm)                       */
+  int32_t       cstride, coff, C;
+  float         eps, momentum, slope;
+} lhn_bnfinsrc;
+
+/* BatchNorm-backward sums contributed by a READER. du = dz * act'(u) is linear in dz, and dz of a convolution output is the sum
  * of what its readers' backward kernels hand back -- so every reader that has its own part of dz in registers can add that
  * part's  sum du  and  sum du * xhat  into the PRODUCER's replicated sums (the reader holds the raw value and the table of its
  * input anyway, or re-reads a tile that is still in L2).  When all readers of a convolution + BatchNorm output do, its
@@ -612,7 +636,17 @@ int lhn_conv_pw_bwd3(const lhn_view* x, const float* w, const lhn_view* y, const
 int lhn_conv_dw_bwd4(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate,
                      float* dw, int k, int stride, int pad, int dil, int nrep, int64_t rep_stride, const lhn_bnsum* bns,
                      const float* dx_add0, const float* dx_add1, const lhn_bnbwdsrc* fin, void* stream);
-/* Which kernel lhn_conv_dw_fwd3 (backward = 0) / lhn_conv_dw_bwd4 (backward = 1) launches for this shape and feature set: host-only
+/* lhn_conv_dw_fwd3 / lhn_conv_pw_fwd2 with the BatchNorm finalize of x taken in the kernel's prologue (lhn_bnfinsrc; fin NULL = the
+ * calls above).  One source only (no extra, no summed-on-load sources).  In-prologue fold: k_dwk_fwd_lds<3,1,1,true> (3x3, stride 1,
+ * dilation 1, "same" padding, W >= 8), k_dws2_fwd_lds<true> (3x3, stride 2, pad 1), k_pw_fwd_wr<64, 2, 1, true> and
+ * k_pw_fwd_wr<32, 1, 1, true> (the whole 1x1 in one register-W launch, Cin = 64 with 33..64 features or Cin = 32 with <= 32); every
+ * other kernel gets a lhn_bn_finalize launch in front, from this call (lhn_conv_dw_route / lhn_conv_pw_route name it). */
+int lhn_conv_dw_fwd4(const lhn_view* x, const float* w, const lhn_view* y, double* stats, int k, int stride, int pad, int dil,
+                     const lhn_bnfin* fin, const lhn_view* extra, const float* coef2, const lhn_view* sum_out, const lhn_bnfinsrc* finsrc,
+                     void* stream);
+int lhn_conv_pw_fwd3(const lhn_view* x, const float* w, const float* bias, const lhn_view* y, double* stats, int stride,
+                     float* y_nchw, const lhn_bnfin* fin, const lhn_pw_opts* opts, const lhn_bnfinsrc* finsrc, void* stream);
+/* Which kernel lhn_conv_dw_fwd4 (backward = 0) / lhn_conv_dw_bwd4 (backward = 1) launches for this shape and feature set: host-only
  * (no device needed, nothing is launched), answered by the function the two calls themselves ask.  H, W, C are x's.
  * features: what the call carries.  switches: -1 = as this process read them from the environment, else a set of LHN_DW_SW_* bits.
  * Returns a static string (per thread, valid until the next call) in the spelling of profiles/dw_instances.md ("k_dw3_bwd_rows<1,BNS>
@@ -625,6 +659,7 @@ int lhn_conv_dw_bwd4(const lhn_view* x, const float* w, const lhn_view* y, const
 #define LHN_DW_F_FIN       16  /* backward: a finalize source (lhn_bnbwdsrc) */
 #define LHN_DW_F_NO_DX     32  /* backward: dx NULL */
 #define LHN_DW_F_DX_ACC    64  /* backward: dx accumulated */
+#define LHN_DW_F_FINSRC    128 /* forward: a finalize source (lhn_bnfinsrc); "lhn_bn_finalize + " in front where the kernel does not fold */
 #define LHN_DW_SW_GATHER    1  /* LHN_DW_GATHER=1 */
 #define LHN_DW_SW_BWD_V1    2  /* LHN_DW_BWD_V1=1 */
 #define LHN_DW_SW_BWD_SMALL 4  /* the small-map route: set unless LHN_DW_BWD_SMALL=0 */
@@ -660,6 +695,7 @@ int lhn_conv_pw_bwd4(const lhn_view* x, const float* w, const lhn_view* y, const
 #define LHN_PW_F_UNALIGNED 4096  /* a pointer the vector paths need at 16 bytes is not (forward: w, y_nchw; backward: dy_nchw, x's data),
                                     or the NCHW batch stride is no multiple of 4 floats */
 #define LHN_PW_F_DBIAS     8192  /* backward: dbias given (an NCHW gradient's bias sums are a launch of their own on k_pw_bwd) */
+#define LHN_PW_F_FINSRC    16384 /* forward: a finalize source (lhn_bnfinsrc); "lhn_bn_finalize + " in front where the kernel does not fold */
 #define LHN_PW_SW_LDSW          1   /* LHN_PW_LDSW=1 */
 #define LHN_PW_SW_K256          2   /* K = 256 in one pass: set unless LHN_PW_K256=0 */
 #define LHN_PW_SW_BWD_NARROW    4   /* the narrow register-W backward: set unless LHN_PW_BWD_NARROW=0 */
@@ -796,6 +832,11 @@ int   lhn_plan_head_gate_fold(void* plan);
  * LHN_PW_BWD_DZ_DEAD to lhn_conv_pw_bwd6 unless LHN_PW_BWD_DY_STORE=1; 0 otherwise; -1: index out of range.  The answer does not
  * depend on the switch, and the op lists are the same either way. */
 int   lhn_plan_pw_dz_dead(void* plan, int bwd_index);
+/* 1 when forward op fwd_index is a convolution + BatchNorm that hands its finalize to the next op of the list (a single-source NHWC
+ * depthwise or 1x1 convolution over exactly the BatchNorm's output view, on a kernel that folds the statistics in its prologue:
+ * lhn_bnfinsrc): a whole-plan training run then launches no lhn_bn_finalize for it.  0 otherwise, also with LHN_FWD_FIN_CONSUMER=0
+ * or LHN_FUSE_FINALIZE=1; -1: index out of range.  The op lists are the same either way. */
+int   lhn_plan_fwd_fin_consumer(void* plan, int fwd_index);
 /* io: phase 0 {image NCHW, heatmap NCHW out}; phase 1 {image NCHW, d(heatmap) NCHW}.
  * training: a bit set -- bit 0 = train-mode BatchNorm (batch statistics, running statistics updated); bit 1 (LHN_RUN_TABLES_CURRENT,
  * eval only) = the workspace's per-buffer BatchNorm tables were built by an earlier eval run of THIS plan and no parameter

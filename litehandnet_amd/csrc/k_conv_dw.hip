@@ -258,10 +258,15 @@ struct DwTile {
   static constexpr int P = DIL * (K - 1) / 2, HH = TH + 2 * P, WW = TW + 2 * P, PIX = HH * WW;
 };
 
-template <int K, int DIL, int NS = 1>
+// FIN: x is the output of a convolution + BatchNorm whose statistics are complete and whose table is not written yet (lhn_bnfinsrc):
+// the workgroup folds the replicas of its own 32 channels while its first tile's loads are in flight (the statistics' own loads go
+// out in front of them), in LDS the first commit has not touched yet
+// (16 KB of the halo tile for the pairs, 384 B of `red` for the table entries), and the first workgroup of each channel group also
+// stores what lhn_bn_finalize leaves in memory.  A template flag: the instances that do not fold keep their registers.
+template <int K, int DIL, int NS = 1, bool FIN = false>
 __global__ void __launch_bounds__(256) k_dwk_fwd_lds(lhn_view x, const float* __restrict__ w, lhn_view y,
                                                      double* __restrict__ stats, int tiles_h, int tiles_w, int cgroups,
-                                                     lhn_bnfin fin, int ps, DwExtra ex, int xchunk) {
+                                                     lhn_bnfin fin, int ps, DwExtra ex, int xchunk, lhn_bnfinsrc fs) {
   constexpr int TH = 8, TW = 32, KK = K * K;
   // XCD-aware tile order: blocks are dealt round-robin over the 8 XCDs, so logical block (b % 8) * xchunk + b / 8 gives each
   // XCD a CONTIGUOUS run of tiles -- neighbouring tiles (which share their halo rows / columns) then meet in one L2
@@ -334,9 +339,32 @@ __global__ void __launch_bounds__(256) k_dwk_fwd_lds(lhn_view x, const float* __
     }
   };
   int t = bid;
+  double fa[FIN ? 4 : 1], fb[FIN ? 4 : 1];      // FIN: this thread's share of the statistics, loaded in front of the tile (lhn_common.h)
+  LhnFinPre pre;
+  if constexpr (FIN) {
+    pre = lhn_bn_fin_pre(fs, cg * 32, 4 * cvalid, bid < cgroups);
+    lhn_bn_fin_load<4>(fs.stats, fs.C, cg * 32, 4 * cvalid, fa, fb);
+  }
   if (t < ntile) issue(t);
   // (the tile region is free until the first commit, which follows a barrier)
-  xf = lhn_load_xf(x, cin);
+  if constexpr (FIN) {
+    static_assert(NS == 1 && T::PIX * 8 * 16 >= LHN_STAT_REPLICAS * 32 * 16, "the halo tile holds the replica pairs of one channel group");
+    double* rawd = reinterpret_cast<double*>(tile);
+    float* tab = reinterpret_cast<float*>(red);
+    const int nc = 4 * cvalid;
+    const bool lead = bid < cgroups;
+    lhn_bn_fin_put<4>(fa, fb, nc, rawd);
+    __syncthreads();
+    if (tid < nc) {
+      double s1, s2;
+      lhn_bn_fin_sum_any(rawd, nc, tid, fs.C, s1, s2);
+      lhn_bn_fin_channel(fs, pre, s1, s2, cg * 32, tid, lead, tab, 32);
+    }
+    __syncthreads();
+    xf = lhn_bn_fin_xf(tab, 32, 4 * c4e);
+  } else {
+    xf = lhn_load_xf(x, cin);
+  }
   if (NS > 1) xf2 = lhn_load_xf(ex.v, cin2);
   for (; t < ntile; t += gridDim.x) {
     int r = t / cgroups;
@@ -938,8 +966,10 @@ struct DwS2 {
   static constexpr int TH = 4, TW = 16, XH = 2 * TH + 1, XW = 2 * TW + 1, XPIX = XH * XW, DH = TH + 1, DW = TW + 1, DPIX = DH * DW;
 };
 
+// FIN: as in k_dwk_fwd_lds (the pairs in the input tile, the table entries in `red`, both free before the first commit)
+template <bool FIN = false>
 __global__ void __launch_bounds__(256) k_dws2_fwd_lds(lhn_view x, const float* __restrict__ w, lhn_view y, double* __restrict__ stats,
-                                                      int tiles_h, int tiles_w, int cgroups, lhn_bnfin fin) {
+                                                      int tiles_h, int tiles_w, int cgroups, lhn_bnfin fin, lhn_bnfinsrc fs) {
   using T = DwS2;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   f4* tx = reinterpret_cast<f4*>(smem);          // [XPIX][8]
@@ -956,7 +986,28 @@ __global__ void __launch_bounds__(256) k_dws2_fwd_lds(lhn_view x, const float* _
     const int k = i >> 3, cc = cg * 32 + 4 * min(i & 7, cvalid - 1);
     wl[i] = (f4){w[(cc + 0) * 9 + k], w[(cc + 1) * 9 + k], w[(cc + 2) * 9 + k], w[(cc + 3) * 9 + k]};
   }
-  const Xf4 xf = lhn_load_xf(x, cin);
+  Xf4 xf;
+  if constexpr (FIN) {
+    static_assert(T::XPIX * 8 * 16 >= LHN_STAT_REPLICAS * 32 * 16, "the input tile holds the replica pairs of one channel group");
+    double* rawd = reinterpret_cast<double*>(tx);
+    float* tab = reinterpret_cast<float*>(red);
+    const int nc = 4 * cvalid;
+    const bool lead = (int)blockIdx.x < cgroups;
+    const LhnFinPre pre = lhn_bn_fin_pre(fs, cg * 32, nc, lead);
+    double fa[4], fb[4];
+    lhn_bn_fin_load<4>(fs.stats, fs.C, cg * 32, nc, fa, fb);
+    lhn_bn_fin_put<4>(fa, fb, nc, rawd);
+    __syncthreads();
+    if (tid < nc) {
+      double s1, s2;
+      lhn_bn_fin_sum_any(rawd, nc, tid, fs.C, s1, s2);
+      lhn_bn_fin_channel(fs, pre, s1, s2, cg * 32, tid, lead, tab, 32);
+    }
+    __syncthreads();
+    xf = lhn_bn_fin_xf(tab, 32, 4 * c4e);
+  } else {
+    xf = lhn_load_xf(x, cin);
+  }
   double sd[4] = {0, 0, 0, 0}, qd[4] = {0, 0, 0, 0};
   constexpr int NIT = (T::XPIX + 31) / 32;
   for (int t = blockIdx.x; t < ntile; t += gridDim.x) {
@@ -1189,11 +1240,13 @@ static int dw3_grid(int ntile, int cgroups, int per_cu) {
   return g;
 }
 
-template <int K, int DIL, int NS = 1>
+template <int K, int DIL, int NS = 1, bool FIN = false>
 static void launch_dwk_fwd(const lhn_view* x, const float* w, const lhn_view* y, double* stats, lhn_bnfin fin, hipStream_t s, int ps = 1,
-                           const DwExtra* exp = nullptr) {
+                           const DwExtra* exp = nullptr, const lhn_bnfinsrc* fsp = nullptr) {
   DwExtra ex;
   if (exp) ex = *exp; else { ex.n = 0; ex.sum_out = nullptr; }
+  lhn_bnfinsrc fs;
+  if (FIN && fsp) fs = *fsp; else memset(&fs, 0, sizeof(fs));
   constexpr int TH = 8, TW = 32, P = DIL * (K - 1) / 2;
   const int cg = (x->C + 31) / 32;
   const int sh = (y->H + ps - 1) / ps, sw = (y->W + ps - 1) / ps;       // largest parity sub-lattice
@@ -1201,9 +1254,14 @@ static void launch_dwk_fwd(const lhn_view* x, const float* w, const lhn_view* y,
   const size_t lds = (size_t)((TH + 2 * P) * (TW + 2 * P) * 8 + 512 + K * K * 8) * 16;
   const int per_cu = lds > 80 * 1024 ? 1 : (lds > 52 * 1024 ? 2 : 3);
   static LhnKernelCfg cfg;
-  (void)lhn_kernel_cfg(cfg, &k_dwk_fwd_lds<K, DIL, NS>, lds, 4, nullptr);
-  const int grid = dw3_grid(ntile, cg, per_cu * 2);      // (2 / 3 / 4 / 8 / 16 blocks per CU measured in round 3: forward 2.65 / 2.68 / 2.66 / 2.71 / 2.71 ms)
-  hipLaunchKernelGGL((k_dwk_fwd_lds<K, DIL, NS>), dim3(grid), dim3(256), lds, s, *x, w, *y, stats, th, tw, cg, fin, ps, ex, dw3_xchunk(grid, cg));
+  int resident = 2;
+  (void)lhn_kernel_cfg(cfg, &k_dwk_fwd_lds<K, DIL, NS, FIN>, lds, 4, &resident);
+  // (2 / 3 / 4 / 8 / 16 blocks per CU measured in round 3: forward 2.65 / 2.68 / 2.66 / 2.71 / 2.71 ms).  FIN: one round of resident
+  // workgroups -- every workgroup pays the prologue fold once, and six per CU with two resident paid it three times in a row
+  // (64 x 64 x 64 channels at batch 64: 33.6 -> 48 us, against 39 us with the separate launch)
+  const int grid = dw3_grid(ntile, cg, FIN ? resident : per_cu * 2);
+  hipLaunchKernelGGL((k_dwk_fwd_lds<K, DIL, NS, FIN>), dim3(grid), dim3(256), lds, s, *x, w, *y, stats, th, tw, cg, fin, ps, ex,
+                     dw3_xchunk(grid, cg), fs);
 }
 template <int K, int DIL, bool BNS = false, bool FOLD = false>
 static void launch_dwk_bwd(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc,
@@ -1253,14 +1311,20 @@ static void launch_dw3_bwd_rows(const lhn_view* x, const float* w, const lhn_vie
                      nrep, rep_stride, ps, bs, fs);
 }
 // returns 1 if the stride-2 tiled kernel was launched
-static int dws2_fwd(const lhn_view* x, const float* w, const lhn_view* y, double* stats, lhn_bnfin fin, hipStream_t s) {
+template <bool FIN = false>
+static int dws2_fwd(const lhn_view* x, const float* w, const lhn_view* y, double* stats, lhn_bnfin fin, hipStream_t s,
+                    const lhn_bnfinsrc* fsp = nullptr) {
   using T = DwS2;
+  lhn_bnfinsrc fs;
+  if (FIN && fsp) fs = *fsp; else memset(&fs, 0, sizeof(fs));
   const int cg = (x->C + 31) / 32;
   const int th = (y->H + T::TH - 1) / T::TH, tw = (y->W + T::TW - 1) / T::TW, ntile = y->N * th * tw * cg;
   size_t lds = (size_t)(T::XPIX * 8 + 512 + 72) * 16;
   static LhnKernelCfg cfg;
-  if (!lhn_kernel_cfg(cfg, &k_dws2_fwd_lds, lds, 4, nullptr)) return 0;
-  hipLaunchKernelGGL(k_dws2_fwd_lds, dim3(dw3_grid(ntile, cg, 6)), dim3(256), lds, s, *x, w, *y, stats, th, tw, cg, fin);
+  int resident = 3;
+  if (!lhn_kernel_cfg(cfg, &k_dws2_fwd_lds<FIN>, lds, 4, &resident)) return 0;
+  // (FIN: one round of resident workgroups, see launch_dwk_fwd)
+  hipLaunchKernelGGL(k_dws2_fwd_lds<FIN>, dim3(dw3_grid(ntile, cg, FIN ? resident : 6)), dim3(256), lds, s, *x, w, *y, stats, th, tw, cg, fin, fs);
   return 1;
 }
 static int dws2_bwd(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_acc, float* dw,
@@ -1308,14 +1372,15 @@ struct DwShape {
 enum DwKern {
   DW_NONE = 0,      // no kernel for this k / dilation with these features
   DW_NARROW,        // none either: the features live in the tiled stride-1 kernels, which this geometry does not reach
-  DWF_LDS31, DWF_LDS32, DWF_LDS71, DWF_LDS31_NS2, DWF_S2, DWF_GATHER1, DWF_GATHER3, DWF_GATHER5, DWF_GATHER7,
+  DWF_LDS31, DWF_LDS32, DWF_LDS71, DWF_LDS31_NS2, DWF_S2, DWF_LDS31_FIN, DWF_S2_FIN, DWF_GATHER1, DWF_GATHER3, DWF_GATHER5, DWF_GATHER7,
   DWB_ROWS1, DWB_ROWS1_BNS, DWB_ROWS2, DWB_LDS31, DWB_LDS31_BNS, DWB_LDS31_FOLD, DWB_LDS31_BNS_FOLD, DWB_LDS32, DWB_LDS71, DWB_S2,
   DWB_GATHER1, DWB_GATHER3, DWB_GATHER7
 };
 struct DwRoute {
   DwKern kern;
   int ps;                       // 2: a dilation-2 convolution run as four dilation-1 convolutions on the parity sub-lattices
-  bool separate_finalize;       // a finalize source is present and the kernel does not take it in its prologue
+  bool separate_finalize;       // a finalize source is present and the kernel does not take it in its prologue (forward: lhn_bnfinsrc
+                                // and lhn_bn_finalize in front; backward: lhn_bnbwdsrc and lhn_bn_bwd_finalize2)
 };
 
 // LHN_DW_SW_*, read from the environment once.  LHN_DW_GATHER=1: the row-gather kernels.  LHN_DW_BWD_V1=1: the 3x3 backward runs the
@@ -1335,18 +1400,21 @@ static unsigned dw_switches() {
 static bool dw_tiled_geometry(const DwShape& s) { return s.stride == 1 && s.pad == s.dil * (s.k - 1) / 2 && s.W >= 8; }
 static int dw_parity_split(const DwShape& s) { return (s.k == 3 && s.dil == 2 && s.W >= 16) ? 2 : 1; }
 
+// A finalize source (LHN_DW_F_FINSRC) rides in the 3x3 / dilation 1 / stride 1 tile kernel and in the stride-2 one; every other
+// kernel gets the lhn_bn_finalize launch in front.
 static DwRoute dw_fwd_route(const DwShape& s, unsigned sw) {
-  const bool tiled = dw_tiled_geometry(s);
+  const bool tiled = dw_tiled_geometry(s), fs = s.f & LHN_DW_F_FINSRC;
   const int ps = dw_parity_split(s);
   if (s.f & LHN_DW_F_EXTRA)      // two summed sources (MSRB's second round): 3x3 on the dilation-1 kernel only; ignores LHN_DW_GATHER
-    return {(tiled && s.k == 3 && (s.dil == 1 || ps == 2)) ? DWF_LDS31_NS2 : DW_NONE, ps, false};
+    return {(tiled && s.k == 3 && (s.dil == 1 || ps == 2)) ? DWF_LDS31_NS2 : DW_NONE, ps, fs};
   if (!(s.f & LHN_DW_F_NO_WEIGHT) && !(sw & LHN_DW_SW_GATHER)) {
-    if (tiled && s.k == 3 && (s.dil == 1 || ps == 2)) return {DWF_LDS31, ps, false};
-    if (tiled && s.k == 3 && s.dil == 2) return {DWF_LDS32, 1, false};
-    if (tiled && s.k == 7 && s.dil == 1) return {DWF_LDS71, 1, false};
-    if (s.k == 3 && s.stride == 2 && s.pad == 1 && s.dil == 1) return {DWF_S2, 1, false};
+    if (tiled && s.k == 3 && s.dil == 1 && fs) return {DWF_LDS31_FIN, 1, false};
+    if (tiled && s.k == 3 && (s.dil == 1 || ps == 2)) return {DWF_LDS31, ps, fs};
+    if (tiled && s.k == 3 && s.dil == 2) return {DWF_LDS32, 1, fs};
+    if (tiled && s.k == 7 && s.dil == 1) return {DWF_LDS71, 1, fs};
+    if (s.k == 3 && s.stride == 2 && s.pad == 1 && s.dil == 1) return {fs ? DWF_S2_FIN : DWF_S2, 1, false};
   }
-  return {s.k == 1 ? DWF_GATHER1 : s.k == 3 ? DWF_GATHER3 : s.k == 5 ? DWF_GATHER5 : s.k == 7 ? DWF_GATHER7 : DW_NONE, 1, false};
+  return {s.k == 1 ? DWF_GATHER1 : s.k == 3 ? DWF_GATHER3 : s.k == 5 ? DWF_GATHER5 : s.k == 7 ? DWF_GATHER7 : DW_NONE, 1, fs};
 }
 
 // The small-map rule (3x3, dilation 1): H * W <= 256 pixels run the 8 x 16 tile kernel, whose whole halo tile is ONE batch of loads,
@@ -1388,10 +1456,20 @@ static DwRoute dw_bwd_route(const DwShape& s, unsigned sw) {
 
 // =====================================================================================================
 // Dispatchers: validate once, ask the route, issue the separate finalize launch when the route says so, launch.
+static int dw_fwd_finalize(const lhn_bnfinsrc* f, void* stream) {
+  return lhn_bn_finalize(f->stats, f->gamma, f->beta, f->running_mean, f->running_var, f->num_batches_tracked, f->table, f->cstride, f->coff,
+                         f->C, f->save_mean_invstd, f->count, f->eps, f->momentum, f->slope, 1, f->conv_bias, stream);
+}
 static int dw_fwd_run(const lhn_view* x, const float* w, const lhn_view* y, double* stats, int k, int stride, int pad, int dil,
-                      const lhn_bnfin* finp, const lhn_view* extra, const float* coef2, const lhn_view* sum_out, void* stream) {
+                      const lhn_bnfin* finp, const lhn_view* extra, const float* coef2, const lhn_view* sum_out, const lhn_bnfinsrc* fsrc,
+                      void* stream) {
   lhn_bnfin fin;
   if (finp && stats) fin = *finp; else fin.counter = nullptr;
+  if (fsrc && !fsrc->stats) fsrc = nullptr;
+  if (fsrc)
+    LHN_CHECK_ARG(lhn_view_ok(x) && !extra && fsrc->table && fsrc->table == x->table && fsrc->cstride == x->cstride && fsrc->coff == x->coff &&
+                      fsrc->C == x->C && fsrc->count >= 1 && (!fsrc->running_mean || fsrc->running_var),
+                  "lhn_conv_dw_fwd: the finalize source must be the BatchNorm of x (its table and channel slice), one source");
   if (!extra) {
     LHN_CHECK_ARG(!sum_out, "lhn_conv_dw_fwd: sum_out without a second source");
     LHN_CHECK_ARG(lhn_view_ok(x) && lhn_view_ok(y) && (w || k == 1), "lhn_conv_dw_fwd: bad view / null pointer (w may be NULL = ones only for k=1)");
@@ -1408,7 +1486,8 @@ static int dw_fwd_run(const lhn_view* x, const float* w, const lhn_view* y, doub
                                sum_out->cstride % 4 == 0 && sum_out->coff % 4 == 0 && sum_out->coff + sum_out->C <= sum_out->cstride),
                   "lhn_conv_dw_fwd: sum_out geometry (same pixels and channels as x)");
   }
-  const DwShape sh = {x->H, x->W, x->C, k, stride, pad, dil, (w ? 0u : LHN_DW_F_NO_WEIGHT) | (extra ? LHN_DW_F_EXTRA : 0u)};
+  const DwShape sh = {x->H, x->W, x->C, k, stride, pad, dil,
+                      (w ? 0u : LHN_DW_F_NO_WEIGHT) | (extra ? LHN_DW_F_EXTRA : 0u) | (fsrc ? LHN_DW_F_FINSRC : 0u)};
   const DwRoute r = dw_fwd_route(sh, dw_switches());
   LHN_CHECK_ARG(!extra || (r.kern != DW_NONE && lhn_no_pend(x) && lhn_no_pend(extra)),
                 "lhn_conv_dw_fwd: a second source needs k=3, stride 1, 'same' padding, W >= 8 (got k=%d s=%d C=%d W=%d)", k, stride, x->C, y->W);
@@ -1424,7 +1503,19 @@ static int dw_fwd_run(const lhn_view* x, const float* w, const lhn_view* y, doub
     ex.so_coff = sum_out ? sum_out->coff : 0;
   }
   hipStream_t s = (hipStream_t)stream;
+  if (r.separate_finalize && r.kern != DW_NONE) {
+    const int rc = dw_fwd_finalize(fsrc, stream);
+    if (rc) return rc;
+  }
   switch (r.kern) {
+    case DWF_LDS31_FIN: launch_dwk_fwd<3, 1, 1, true>(x, w, y, stats, fin, s, 1, &ex, fsrc); break;
+    case DWF_S2_FIN: {
+      if (dws2_fwd<true>(x, w, y, stats, fin, s, fsrc)) break;
+      const int rc = dw_fwd_finalize(fsrc, stream);      // (its LDS reservation was refused: the launch in front, then the gather kernel)
+      if (rc) return rc;
+      launch_dw_fwd_gather<3>(x, w, y, stats, stride, pad, dil, fin, s);
+      break;
+    }
     case DWF_LDS31: launch_dwk_fwd<3, 1>(x, w, y, stats, fin, s, r.ps, &ex); break;
     case DWF_LDS32: launch_dwk_fwd<3, 2>(x, w, y, stats, fin, s, 1, &ex); break;
     case DWF_LDS71: launch_dwk_fwd<7, 1>(x, w, y, stats, fin, s, 1, &ex); break;
@@ -1529,7 +1620,12 @@ extern "C" int lhn_conv_dw_fwd2(const lhn_view* x, const float* w, const lhn_vie
 extern "C" int lhn_conv_dw_fwd3(const lhn_view* x, const float* w, const lhn_view* y, double* stats, int k, int stride,
                                 int pad, int dil, const lhn_bnfin* finp, const lhn_view* extra, const float* coef2,
                                 const lhn_view* sum_out, void* stream) {
-  return dw_fwd_run(x, w, y, stats, k, stride, pad, dil, finp, extra, coef2, sum_out, stream);
+  return dw_fwd_run(x, w, y, stats, k, stride, pad, dil, finp, extra, coef2, sum_out, nullptr, stream);
+}
+extern "C" int lhn_conv_dw_fwd4(const lhn_view* x, const float* w, const lhn_view* y, double* stats, int k, int stride,
+                                int pad, int dil, const lhn_bnfin* finp, const lhn_view* extra, const float* coef2,
+                                const lhn_view* sum_out, const lhn_bnfinsrc* finsrc, void* stream) {
+  return dw_fwd_run(x, w, y, stats, k, stride, pad, dil, finp, extra, coef2, sum_out, finsrc, stream);
 }
 
 extern "C" int lhn_conv_dw_bwd(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
@@ -1560,7 +1656,7 @@ extern "C" const char* lhn_conv_dw_route(int backward, int H, int W, int C, int 
                                          int switches) {
   static const char* const name[] = {
       nullptr, nullptr, "k_dwk_fwd_lds<3,1>", "k_dwk_fwd_lds<3,2>", "k_dwk_fwd_lds<7,1>", "k_dwk_fwd_lds<3,1,2>", "k_dws2_fwd_lds",
-      "k_dw_fwd<1>", "k_dw_fwd<3>", "k_dw_fwd<5>", "k_dw_fwd<7>",
+      "k_dwk_fwd_lds<3,1,1,true>", "k_dws2_fwd_lds<true>", "k_dw_fwd<1>", "k_dw_fwd<3>", "k_dw_fwd<5>", "k_dw_fwd<7>",
       "k_dw3_bwd_rows<1>", "k_dw3_bwd_rows<1,BNS>", "k_dw3_bwd_rows<2>", "k_dwk_bwd_lds<3,1>", "k_dwk_bwd_lds<3,1,BNS>",
       "k_dwk_bwd_lds<3,1,false,true>", "k_dwk_bwd_lds<3,1,BNS,true>", "k_dwk_bwd_lds<3,2>", "k_dwk_bwd_lds<7,1>", "k_dws2_bwd_lds"};
   static const char* const gdata[] = {"k_dw_bwd_data<1>", "k_dw_bwd_data<3>", "k_dw_bwd_data<7>"};
@@ -1569,7 +1665,7 @@ extern "C" const char* lhn_conv_dw_route(int backward, int H, int W, int C, int 
   const DwRoute r = (backward ? dw_bwd_route : dw_fwd_route)(sh, switches < 0 ? dw_switches() : (unsigned)switches);
   if (r.kern == DW_NONE || r.kern == DW_NARROW) return nullptr;
   static thread_local char buf[128];
-  const char* fin = r.separate_finalize ? "lhn_bn_bwd_finalize2 + " : "";
+  const char* fin = r.separate_finalize ? (backward ? "lhn_bn_bwd_finalize2 + " : "lhn_bn_finalize + ") : "";
   if (r.kern >= DWB_GATHER1) {
     const bool d = !(features & LHN_DW_F_NO_DX), wg = !(features & LHN_DW_F_NO_WEIGHT);
     snprintf(buf, sizeof(buf), "%s%s%s%s", fin, d ? gdata[r.kern - DWB_GATHER1] : "", d && wg ? " + " : "", wg ? gweight[r.kern - DWB_GATHER1] : "");

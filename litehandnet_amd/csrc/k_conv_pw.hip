@@ -280,10 +280,16 @@ static int launch_pw_fwd(const lhn_view* x, const float* w, const float* bias, c
 // run under another block's MFMA phase (the LDS-resident-W kernel above sits at ONE block per CU for 128 -> 128 and adds its
 // phases up: 126 us against a 55 us MFMA bound).  Waves: NCOT feature tiles x (4 / NCOT) pixel sub-tiles of 32.
 // Statistics need no cross-wave reduction: each wave owns its features.
-template <int CIN, int NCOT, int NS>
+// FIN: x is the output of a convolution + BatchNorm of CIN channels whose statistics are complete and whose table is not written yet
+// (lhn_bnfinsrc): every workgroup folds the 32 replicas while its first tile's loads are in flight (the statistics' own loads go
+// out in front of them), in the two pixel buffers, which nobody has
+// committed to yet (CIN * 512 B of pairs from the front, the 3 * CIN table entries at the very end, in the second buffer, which
+// the first commit does not reach), and workgroup 0 also stores what lhn_bn_finalize leaves in memory.  A template flag: the
+// instances that do not fold keep their registers.
+template <int CIN, int NCOT, int NS, bool FIN = false>
 __global__ void __launch_bounds__(256, (NS > 1 || CIN >= 128) ? 2 : 3)
 k_pw_fwd_wr(lhn_view x, const float* __restrict__ w, const float* __restrict__ bias, lhn_view y, double* __restrict__ stats,
-            int cout, int M, int ntiles, PwExtra ex, int wstride, int yacc, int statC, int wt, lhn_bnfin fin) {
+            int cout, int M, int ntiles, PwExtra ex, int wstride, int yacc, int statC, int wt, lhn_bnfin fin, lhn_bnfinsrc fs) {
   constexpr int LDA = CIN + 4, PXW = 4 / NCOT, BM = 32 * PXW;
   constexpr int C4 = CIN / 4, RP = 256 / C4, PF = BM / RP;      // float4 loads per thread, tile and source
   static_assert(PF >= 1, "tile too small for the loader");
@@ -377,8 +383,33 @@ k_pw_fwd_wr(lhn_view x, const float* __restrict__ w, const float* __restrict__ b
 
   double ssum = 0.0, ssq = 0.0;       // fp32 partials per tile, promoted per tile (see k_pw_fwd)
   int tile = blockIdx.x, buf = 0;
+  double fa[FIN ? CIN / 8 : 1], fb[FIN ? CIN / 8 : 1];      // FIN: this thread's share of the statistics, loaded in front of the tile
+  LhnFinPre fpre;
+  if constexpr (FIN) {
+    fpre = lhn_bn_fin_pre(fs, 0, CIN, blockIdx.x == 0);
+    lhn_bn_fin_load<CIN / 8>(fs.stats, CIN, 0, CIN, fa, fb);
+  }
   if (tile < ntiles) issue(tile);     // the first tile's loads are in flight while pending BatchNorms are finalized
-  xf = lhn_load_xf(x, cabs);
+  if constexpr (FIN) {
+    static_assert(NS == 1 && CIN % 8 == 0 && LHN_STAT_REPLICAS * CIN * 16 <= (2 * BM * LDA - 3 * CIN) * 4 && 3 * CIN <= BM * LDA &&
+                      (2 * BM * LDA - 3 * CIN) % 4 == 0,
+                  "the pixel buffers hold the replica pairs in front of the table entries, which sit in the second one");
+    double* rawd = reinterpret_cast<double*>(smem);
+    float* tab = smem + 2 * BM * LDA - 3 * CIN;
+    const bool lead = blockIdx.x == 0;
+    lhn_bn_fin_put<CIN / 8>(fa, fb, CIN, rawd);
+    __syncthreads();
+    if (tid < CIN) {
+      constexpr int GC = LHN_FIN_THREADS / CIN > LHN_STAT_REPLICAS ? LHN_STAT_REPLICAS : LHN_FIN_THREADS / CIN;      // lhn_fin_groups(CIN)
+      double s1, s2;
+      lhn_bn_fin_sum<GC>(rawd, CIN, tid, GC, s1, s2);
+      lhn_bn_fin_channel(fs, fpre, s1, s2, 0, tid, lead, tab, CIN);
+    }
+    __syncthreads();
+    xf = lhn_bn_fin_xf(tab, CIN, 4 * c4);
+  } else {
+    xf = lhn_load_xf(x, cabs);
+  }
   if (NS > 1) {
 #pragma unroll
     for (int e = 0; e < NS - 1; ++e)
@@ -463,9 +494,10 @@ k_pw_fwd_wr(lhn_view x, const float* __restrict__ w, const float* __restrict__ b
   if (stats && fin.counter && lhn_last_block(fin.counter)) lhn_bn_finalize_block_par(fin, stats, reinterpret_cast<double*>(smem));
 }
 
-template <int CIN, int NCOT, int NS>
+template <int CIN, int NCOT, int NS, bool FIN = false>
 static int launch_pw_fwd_wr(const lhn_view* x, const float* w, const float* bias, const lhn_view* y, double* stats, int cout,
-                            hipStream_t s, const PwExtra* exp, const PwGeom& geo, int wt = 0, const lhn_bnfin* finp = nullptr) {
+                            hipStream_t s, const PwExtra* exp, const PwGeom& geo, int wt = 0, const lhn_bnfin* finp = nullptr,
+                            const lhn_bnfinsrc* fsp = nullptr) {
   PwExtra ex;
   if (exp) ex = *exp; else { ex.n = 0; ex.sum_out = nullptr; }
   constexpr int BM = 32 * (4 / NCOT);
@@ -473,7 +505,7 @@ static int launch_pw_fwd_wr(const lhn_view* x, const float* w, const float* bias
   const size_t lds = (size_t)2 * BM * (CIN + 4) * sizeof(float);
   static LhnKernelCfg cfg;
   int per_cu = 1;
-  if (!lhn_kernel_cfg(cfg, &k_pw_fwd_wr<CIN, NCOT, NS>, lds, 4, &per_cu)) {
+  if (!lhn_kernel_cfg(cfg, &k_pw_fwd_wr<CIN, NCOT, NS, FIN>, lds, 4, &per_cu)) {
     lhn_set_error("lhn_conv_pw_fwd: cannot reserve %zu B of LDS", lds);
     return 2;
   }
@@ -481,8 +513,10 @@ static int launch_pw_fwd_wr(const lhn_view* x, const float* w, const float* bias
   if (grid > ntiles) grid = ntiles;
   lhn_bnfin fin;
   if (finp) fin = *finp; else fin.counter = nullptr;
-  hipLaunchKernelGGL((k_pw_fwd_wr<CIN, NCOT, NS>), dim3(grid), dim3(256), lds, s, *x, w, bias, *y, stats, cout, M, ntiles, ex, geo.wstride,
-                     geo.yacc, geo.statC, wt, fin);
+  lhn_bnfinsrc fs;
+  if (FIN && fsp) fs = *fsp; else memset(&fs, 0, sizeof(fs));
+  hipLaunchKernelGGL((k_pw_fwd_wr<CIN, NCOT, NS, FIN>), dim3(grid), dim3(256), lds, s, *x, w, bias, *y, stats, cout, M, ntiles, ex, geo.wstride,
+                     geo.yacc, geo.statC, wt, fin, fs);
   return 0;
 }
 
@@ -1242,11 +1276,13 @@ struct PwRoute {
   bool dyst, bns;                // wide / narrow: DYST and BNS of the k_pw_bwd_wr instance
   bool separate_finalize;        // forward: the sliced form's own lhn_bn_finalize launch behind; backward: lhn_bn_bwd_finalize2 in front
   bool gate_reduce_after;        // gate sums asked for and the kernel does not add them: the lhn_gate_bwd_reduce3 launch behind
+  bool finalize_in_front;        // forward: a finalize source (lhn_bnfinsrc) that no kernel folds: the lhn_bn_finalize launch of x's BatchNorm
 };
 // One forward launch of the sliced path: k_pw_fwd_wr<ci, nt, ns> (wr; nt = NCOT) or k_pw_fwd<ci, nt, ns>.  ci = 0: no instance.
 struct PwInst {
   int ci, nt, ns;
   bool wr;
+  bool fin;                      // the register-W instance that folds a finalize source in its prologue (FIN)
 };
 
 // LHN_PW_SW_*, read from the environment once.  LHN_PW_LDSW=1: no register-W kernel anywhere (the LDS-resident-W kernels, the split
@@ -1294,7 +1330,7 @@ static PwInst pw_wr_instance(int ci, int cout, bool ms) {
   const int ncot = cout <= 32 ? 1 : cout <= 64 ? 2 : 4;
   const bool ok = ms ? ((ci == 128 && ncot == 4) || (ci == 64 && ncot == 2))
                      : ci == 256 ? ncot == 4 : ci == 128 ? ncot >= 2 : (ci == 64 || ci == 32);
-  return {ok ? ci : 0, ncot, ms ? 3 : 1, true};
+  return {ok ? ci : 0, ncot, ms ? 3 : 1, true, false};
 }
 
 // the forward launch of the slice at (co0, k0)
@@ -1306,18 +1342,21 @@ static PwInst pw_fwd_inst(const PwShape& s, unsigned sw, int kstep, int co0, int
   // the whole weight's row stride, accumulates later K slices into y and addresses the statistics of the whole BatchNorm.
   if (!(sw & LHN_PW_SW_LDSW) && s.stride == 1 && !(s.f & (LHN_PW_F_NCHW | LHN_PW_F_UNALIGNED)) && kc == ci && t.g.kvalid == ci && s.wcols % 4 == 0 &&
       t.g.wrows == cc) {
-    const PwInst i = pw_wr_instance(ci, cc, ms);
+    PwInst i = pw_wr_instance(ci, cc, ms);
+    // a finalize source rides in the two instances the narrow 1x1 -> depthwise chains reach, when one launch is the whole convolution
+    i.fin = (s.f & LHN_PW_F_FINSRC) && !ms && s.Cin == ci && s.Cout <= 128 && ((ci == 64 && i.nt == 2) || (ci == 32 && i.nt == 1));
     if (i.ci) return i;
   }
   // summed-on-load sources: the square 1x1 of MSRB (litehourglass.py:30,49), C = 64 / 128
-  if (ms) return {((ci == 128 && nt == 4) || (ci == 64 && nt == 2)) ? ci : 0, nt, 3, false};
-  return {ci == 256 ? 0 : ci, nt, 1, false};
+  if (ms) return {((ci == 128 && nt == 4) || (ci == 64 && nt == 2)) ? ci : 0, nt, 3, false, false};
+  return {ci == 256 ? 0 : ci, nt, 1, false, false};
 }
 
 static PwRoute pw_fwd_route(const PwShape& s, unsigned sw) {
-  PwRoute r = {PW_NONE, 128, LHN_PW_DGRAD_NONE, false, false, false, false};
+  PwRoute r = {PW_NONE, 128, LHN_PW_DGRAD_NONE, false, false, false, false, false};
   const bool nchw = s.f & LHN_PW_F_NCHW, ms = s.f & (LHN_PW_F_EXTRA1 | LHN_PW_F_EXTRA2), regw = !(sw & LHN_PW_SW_LDSW);
   const bool single = s.Cin <= 128 && s.Cout <= 128;
+  r.finalize_in_front = s.f & LHN_PW_F_FINSRC;
   // the heatmap head (128 -> <= 32 features, NCHW, one source) on its streaming kernel; every other NCHW shape (H's stacked
   // 256 -> 21, padded heads, K slices) keeps k_pw_fwd
   if (nchw && (sw & LHN_PW_SW_HEAD_STREAM) && regw && s.stride == 1 && pw_head_shape(s) && !ms && !(s.f & (LHN_PW_F_SUM_OUT | LHN_PW_F_UNALIGNED)))
@@ -1331,6 +1370,7 @@ static PwRoute pw_fwd_route(const PwShape& s, unsigned sw) {
   r.path = PW_SLICED;
   // a fused finalize rides in the kernel only when one launch is the whole convolution
   r.separate_finalize = !single && (s.f & LHN_PW_F_FUSE_FIN) && (s.f & LHN_PW_F_STATS);
+  if (r.finalize_in_front && single && pw_fwd_inst(s, sw, r.kstep, 0, 0).fin) r.finalize_in_front = false;
   return r;
 }
 
@@ -1353,7 +1393,7 @@ static bool pw_split_route(const PwShape& s, unsigned sw, int* dgrad) {
 }
 
 static PwRoute pw_bwd_route(const PwShape& s, unsigned sw) {
-  PwRoute r = {PW_NONE, 128, LHN_PW_DGRAD_NONE, false, false, false, false};
+  PwRoute r = {PW_NONE, 128, LHN_PW_DGRAD_NONE, false, false, false, false, false};
   const bool nchw = s.f & LHN_PW_F_NCHW, bns = s.f & LHN_PW_F_BNSUM, fin = s.f & LHN_PW_F_FIN, gs = s.f & LHN_PW_F_GATESUM;
   const bool regw = !(sw & LHN_PW_SW_LDSW);
   // reader-side BatchNorm sums ride in the fused kernel's BNS instances and in the narrow register-W ones (both inside the tile rule);
@@ -1391,7 +1431,13 @@ static PwRoute pw_bwd_route(const PwShape& s, unsigned sw) {
 // =====================================================================================================
 // Launch switches: from the route's instance to the template.
 static int pw_fwd_launch(const PwInst& i, const lhn_view* x, const float* w, const float* bias, const lhn_view* y, double* stats, int stride,
-                         float* y_nchw, int cout, const lhn_bnfin* fin, const PwGeom& geo, hipStream_t s, const PwExtra* ex, int wt = 0) {
+                         float* y_nchw, int cout, const lhn_bnfin* fin, const PwGeom& geo, hipStream_t s, const PwExtra* ex, int wt = 0,
+                         const lhn_bnfinsrc* fs = nullptr) {
+  if (i.fin && fs) {
+    if (i.ci == 64 && i.nt == 2) return launch_pw_fwd_wr<64, 2, 1, true>(x, w, bias, y, stats, cout, s, ex, geo, wt, stats ? fin : nullptr, fs);
+    if (i.ci == 32 && i.nt == 1) return launch_pw_fwd_wr<32, 1, 1, true>(x, w, bias, y, stats, cout, s, ex, geo, wt, stats ? fin : nullptr, fs);
+    LHN_CHECK_ARG(false, "lhn_conv_pw_fwd: no folding instance for %d channels x %d tiles", i.ci, i.nt);
+  }
 #define PW_KEY(WRV, CI, NTV, NSV) ((((WRV) * 1000 + (CI)) * 10 + (NTV)) * 10 + (NSV))
   switch (PW_KEY(i.wr, i.ci, i.nt, i.ns)) {
 #define WR(CI, NC, NSV) case PW_KEY(1, CI, NC, NSV): return launch_pw_fwd_wr<CI, NC, NSV>(x, w, bias, y, stats, cout, s, ex, geo, wt, stats ? fin : nullptr);
@@ -1433,7 +1479,12 @@ static int launch_pw_bwd(const lhn_view* x, const float* w, const lhn_view* y, c
 // =====================================================================================================
 // Dispatchers: validate everything, ask the route, issue the separate finalize launch when the route says so, launch.
 static int pw_fwd_run(const lhn_view* x, const float* w, const float* bias, const lhn_view* y, double* stats, int stride, float* y_nchw,
-                      const lhn_bnfin* fin, const lhn_pw_opts* opts, void* stream) {
+                      const lhn_bnfin* fin, const lhn_pw_opts* opts, const lhn_bnfinsrc* fsrc, void* stream) {
+  if (fsrc && !fsrc->stats) fsrc = nullptr;
+  if (fsrc)
+    LHN_CHECK_ARG(lhn_view_ok(x) && !(opts && opts->n_extra > 0) && fsrc->table && fsrc->table == x->table && fsrc->cstride == x->cstride &&
+                      fsrc->coff == x->coff && fsrc->C == x->C && fsrc->count >= 1 && (!fsrc->running_mean || fsrc->running_var),
+                  "lhn_conv_pw_fwd: the finalize source must be the BatchNorm of x (its table and channel slice), one source");
   LHN_CHECK_ARG(lhn_view_ok(x) && w && y, "lhn_conv_pw_fwd: bad input view / null pointer");
   LHN_CHECK_ARG(stride == 1 || stride == 2, "lhn_conv_pw_fwd: stride %d", stride);
   LHN_CHECK_ARG(y->N == x->N && y->H == (x->H + stride - 1) / stride && y->W == (x->W + stride - 1) / stride,
@@ -1484,12 +1535,18 @@ static int pw_fwd_run(const lhn_view* x, const float* w, const float* bias, cons
   const PwShape sh = {x->N, x->H, x->W, HoWo, Cin, Cout, stride, wcols, wrows,
                       (y_nchw ? LHN_PW_F_NCHW : 0u) | (stats ? LHN_PW_F_STATS : 0u) | (fin ? LHN_PW_F_FUSE_FIN : 0u) |
                           (ex.n == 1 ? LHN_PW_F_EXTRA1 : ex.n == 2 ? LHN_PW_F_EXTRA2 : 0u) | (ex.sum_out ? LHN_PW_F_SUM_OUT : 0u) |
-                          (unaligned ? LHN_PW_F_UNALIGNED : 0u)};
+                          (unaligned ? LHN_PW_F_UNALIGNED : 0u) | (fsrc ? LHN_PW_F_FINSRC : 0u)};
   const unsigned sw = pw_switches();
   const PwRoute r = pw_fwd_route(sh, sw);
   LHN_CHECK_ARG(r.path != PW_NONE, "lhn_conv_pw_fwd: unsupported channels Cin=%d Cout=%d (%d extra sources)", Cin, Cout, ex.n);
   hipStream_t s = (hipStream_t)stream;
-  int rc = r.path == PW_HEAD ? lhn_head_fwd(x, w, bias, y_nchw, Cout, HoWo, bstride, s) : 0;
+  int rc = 0;
+  if (r.finalize_in_front)
+    rc = lhn_bn_finalize(fsrc->stats, fsrc->gamma, fsrc->beta, fsrc->running_mean, fsrc->running_var, fsrc->num_batches_tracked, fsrc->table,
+                         fsrc->cstride, fsrc->coff, fsrc->C, fsrc->save_mean_invstd, fsrc->count, fsrc->eps, fsrc->momentum, fsrc->slope, 1,
+                         fsrc->conv_bias, stream);
+  if (rc) return rc;
+  rc = r.path == PW_HEAD ? lhn_head_fwd(x, w, bias, y_nchw, Cout, HoWo, bstride, s) : 0;
   for (int co0 = 0; r.path == PW_SLICED && co0 < Cout && !rc; co0 += 128) {
     for (int k0 = 0; k0 < Cin && !rc; k0 += r.kstep) {
       PwSlice t = pw_slice(sh, r.kstep, co0, k0);
@@ -1505,7 +1562,7 @@ static int pw_fwd_run(const lhn_view* x, const float* w, const float* bias, cons
       t.g.nchw_bstride = bstride;
       rc = pw_fwd_launch(pw_fwd_inst(sh, sw, r.kstep, co0, k0), &xv, w + (int64_t)co0 * wcols + k0, (last && bias) ? bias + co0 : nullptr,
                          &yv, (last && stats) ? stats + co0 : nullptr, stride, y_nchw ? y_nchw + (int64_t)co0 * HoWo : nullptr, t.cc,
-                         single ? fin : nullptr, t.g, s, &ex);
+                         single ? fin : nullptr, t.g, s, &ex, 0, r.finalize_in_front ? nullptr : fsrc);
     }
   }
   if (rc) return rc;
@@ -1621,7 +1678,12 @@ extern "C" int lhn_conv_pw_fwd(const lhn_view* x, const float* w, const float* b
 }
 extern "C" int lhn_conv_pw_fwd2(const lhn_view* x, const float* w, const float* bias, const lhn_view* y, double* stats,
                                 int stride, float* y_nchw, const lhn_bnfin* fin, const lhn_pw_opts* opts, void* stream) {
-  return pw_fwd_run(x, w, bias, y, stats, stride, y_nchw, fin, opts, stream);
+  return pw_fwd_run(x, w, bias, y, stats, stride, y_nchw, fin, opts, nullptr, stream);
+}
+extern "C" int lhn_conv_pw_fwd3(const lhn_view* x, const float* w, const float* bias, const lhn_view* y, double* stats,
+                                int stride, float* y_nchw, const lhn_bnfin* fin, const lhn_pw_opts* opts, const lhn_bnfinsrc* finsrc,
+                                void* stream) {
+  return pw_fwd_run(x, w, bias, y, stats, stride, y_nchw, fin, opts, finsrc, stream);
 }
 extern "C" int lhn_conv_pw_bwd(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
                                int dx_accumulate, float* dw, float* dbias, int stride, const float* dy_nchw, int nrep,
@@ -1681,12 +1743,13 @@ extern "C" const char* lhn_conv_pw_route(int backward, int N, int H, int W, int 
     ++reps;
   };
   auto fwd_name = [&](const PwInst& i) {
-    snprintf(cur, sizeof(cur), "%s<%d, %d, %d>", i.wr ? "k_pw_fwd_wr" : "k_pw_fwd", i.ci, i.nt, i.ns);
+    snprintf(cur, sizeof(cur), i.fin ? "%s<%d, %d, %d, true>" : "%s<%d, %d, %d>", i.wr ? "k_pw_fwd_wr" : "k_pw_fwd", i.ci, i.nt, i.ns);
     emit(cur);
   };
   const char* const tf[] = {"false", "true"};
   buf[0] = 0;
   if (r.separate_finalize && backward) emit("lhn_bn_bwd_finalize2");
+  if (r.finalize_in_front && !backward) emit("lhn_bn_finalize");
   switch (r.path) {
     case PW_HEAD:
       snprintf(cur, sizeof(cur), "k_head_bwd<%s>", tf[(features & LHN_PW_F_GATESUM) != 0]);

@@ -51,27 +51,20 @@ __global__ void __launch_bounds__(LHN_FIN_THREADS) k_bn_finalize(const double* _
         s1 += part[2 * (k * C + threadIdx.x)];
         s2 += part[2 * (k * C + threadIdx.x) + 1];
       }
-      mean = s1 / count;
-      var = s2 / count - mean * mean;
-      if (var < 0) var = 0;
-      if (rmean) {
-        rmean[c] = (float)((1.0 - (double)momentum) * (double)rmean[c] + (double)momentum * (mean + cb));
-        const double unb = count > 1 ? var * count / (count - 1.0) : var;
-        rvar[c] = (float)((1.0 - (double)momentum) * (double)rvar[c] + (double)momentum * unb);
-      }
+      // (the arithmetic of lhn_common.h, which the forward kernels that fold their own input channels share: lhn_bnfinsrc)
+      lhn_bn_fin_moments(s1, s2, count, mean, var);
+      if (rmean) lhn_bn_fin_running(rmean, rvar, c, rmean[c], rvar[c], mean, var, cb, count, momentum);
     } else {
       mean = (double)rmean[c] - cb;
       var = rvar[c];
     }
-    const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float gm = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
-    const float sc = gm * invstd;
-    table[coff + c] = sc;
-    table[cs + coff + c] = b - (float)mean * sc;
+    const LhnFinTab ft = lhn_bn_fin_tab(mean, var, eps, gamma ? gamma[c] : 1.f, beta ? beta[c] : 0.f);
+    table[coff + c] = ft.sc;
+    table[cs + coff + c] = ft.sh;
     table[2 * cs + coff + c] = slope;
     if (save && training) {      // eval: no batch statistics to save (torch's batch_norm returns none either); save keeps its bytes
       save[c] = (float)mean;
-      save[SC + c] = invstd;
+      save[SC + c] = ft.invstd;
     }
   }
   if (training && nbt && threadIdx.x == 0) nbt[0] += 1;

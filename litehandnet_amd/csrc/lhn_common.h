@@ -537,6 +537,144 @@ __device__ __forceinline__ void lhn_bn_bwd_coef_put(const LhnBwdCoef& r, const l
   cfA[2 * ld + cl] = r.C;
   if (lead) lhn_bn_bwd_coef_store(r, coef, cs, coff, c, f.dgamma, f.dbeta, f.pgrad_scale);
 }
+// ---- BatchNorm FORWARD finalize, shared by k_bn_finalize and the prologues of the forward kernels that fold their own input
+// channels (lhn_bnfinsrc).  Replica order of the separate launch: G = lhn_fin_groups(C_bn) groups, group g adds replicas g, g + G, ...
+// in turn, the groups are then added in the order 0 .. G-1.  Same sums in memory, same bits out, whoever calls.
+// the arithmetic of one channel: batch moments from the folded sums ...
+__device__ __forceinline__ void lhn_bn_fin_moments(double s1, double s2, double count, double& mean, double& var) {
+  mean = s1 / count;
+  var = s2 / count - mean * mean;
+  if (var < 0) var = 0;
+}
+// ... one momentum step of the running statistics (cb: bias of the convolution in front, which the stored output excludes) ...
+__device__ __forceinline__ void lhn_bn_fin_running(float* __restrict__ rmean, float* __restrict__ rvar, int c, float rm, float rv,
+                                                   double mean, double var, double cb, double count, float momentum) {
+  rmean[c] = (float)((1.0 - (double)momentum) * (double)rm + (double)momentum * (mean + cb));
+  const double unb = count > 1 ? var * count / (count - 1.0) : var;
+  rvar[c] = (float)((1.0 - (double)momentum) * (double)rv + (double)momentum * unb);
+}
+// ... and the table entry
+struct LhnFinTab {
+  float sc, sh, invstd;
+};
+__device__ __forceinline__ LhnFinTab lhn_bn_fin_tab(double mean, double var, float eps, float gm, float b) {
+  LhnFinTab r;
+  r.invstd = (float)(1.0 / sqrt(var + (double)eps));
+  r.sc = gm * r.invstd;
+  r.sh = b - (float)mean * r.sc;
+  return r;
+}
+// Prologue form (256 threads, channels [c0, c0 + nc) of the BatchNorm of x, nc * 32 <= 256 * Q).  As in the backward prologues each
+// thread issues ALL of its loads -- its share of the statistics, and the parameters of the channel it finishes -- before the first
+// add, and IN FRONT of the first tile's loads: loads return in order, so a fold whose loads stand behind the tile's would wait for
+// the whole tile and run after it instead of under it (measured: 4 us per launch against 5.3 us for the launch it replaces).
+// lead (block-uniform): this workgroup also writes memory.
+struct LhnFinPre {
+  float gamma, beta, cb, rm, rv;
+};
+__device__ __forceinline__ LhnFinPre lhn_bn_fin_pre(const lhn_bnfinsrc& f, int c0, int nc, bool lead) {
+  LhnFinPre p;
+  const int c = c0 + min((int)threadIdx.x, nc - 1);
+  p.gamma = f.gamma ? f.gamma[c] : 1.f;
+  p.beta = f.beta ? f.beta[c] : 0.f;
+  p.cb = (lead && f.conv_bias) ? f.conv_bias[c] : 0.f;
+  p.rm = (lead && f.running_mean) ? f.running_mean[c] : 0.f;
+  p.rv = (lead && f.running_mean) ? f.running_var[c] : 0.f;
+  return p;
+}
+// first half: the 32 * nc (sum, sum of squares) pairs, Q per thread, into registers (in front of the tile's loads) ...
+template <int Q>
+__device__ __forceinline__ void lhn_bn_fin_load(const double* __restrict__ stats, int SC, int c0, int nc, double (&a)[Q], double (&b)[Q]) {
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const int p = min((int)threadIdx.x + 256 * q, LHN_STAT_REPLICAS * nc - 1), r = p / nc, cl = p - r * nc;
+    a[q] = stats[(size_t)r * 2 * SC + c0 + cl];
+    b[q] = stats[(size_t)r * 2 * SC + SC + c0 + cl];
+  }
+}
+// ... and to LDS as they are (behind them), raw[2 * (r * nc + cl)] (512 * nc bytes)
+template <int Q>
+__device__ __forceinline__ void lhn_bn_fin_put(const double (&a)[Q], const double (&b)[Q], int nc, double* raw) {
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const int p = threadIdx.x + 256 * q;
+    if (p < LHN_STAT_REPLICAS * nc) {
+      raw[2 * p] = a[q];
+      raw[2 * p + 1] = b[q];
+    }
+  }
+}
+// second half (behind a barrier), thread cl < nc: the replicas of its channel added in the finalize's order (groups of G, then the
+// groups).  GC = G at compile time (a divisor of 32), 0 = any G: with GC the 32 LDS reads are one batch in flight, where the loop
+// over a run-time G pays one LDS latency per replica (a microsecond of the prologue at G = 32)
+template <int GC>
+__device__ __forceinline__ void lhn_bn_fin_sum(const double* raw, int nc, int cl, int G, double& s1, double& s2) {
+  s1 = 0;
+  s2 = 0;
+  if constexpr (GC > 0) {
+    static_assert(LHN_STAT_REPLICAS % GC == 0, "whole groups");
+    const double* rc = raw + 2 * cl;
+#pragma unroll
+    for (int g = 0; g < GC; ++g) {
+      double t1 = 0, t2 = 0;
+#pragma unroll
+      for (int r = g; r < LHN_STAT_REPLICAS; r += GC) {
+        t1 += rc[2 * r * nc];
+        t2 += rc[2 * r * nc + 1];
+      }
+      s1 += t1;
+      s2 += t2;
+    }
+  } else {
+    for (int g = 0; g < G; ++g) {
+      double t1 = 0, t2 = 0;
+      for (int r = g; r < LHN_STAT_REPLICAS; r += G) {
+        t1 += raw[2 * (r * nc + cl)];
+        t2 += raw[2 * (r * nc + cl) + 1];
+      }
+      s1 += t1;
+      s2 += t2;
+    }
+  }
+}
+// the G of a workgroup's BatchNorm at run time: the two values the models' depthwise chains have (C = 32: 32, C = 64: 16) take the
+// compile-time form
+__device__ __forceinline__ void lhn_bn_fin_sum_any(const double* raw, int nc, int cl, int C_bn, double& s1, double& s2) {
+  const int G = lhn_fin_groups(C_bn);
+  if (G == 32) lhn_bn_fin_sum<32>(raw, nc, cl, G, s1, s2);
+  else if (G == 16) lhn_bn_fin_sum<16>(raw, nc, cl, G, s1, s2);
+  else lhn_bn_fin_sum<0>(raw, nc, cl, G, s1, s2);
+}
+// ... and the channel's table entry into the LDS slots tab[cl] | tab[ld + cl] | tab[2 * ld + cl] (scale | shift | slope); the lead
+// workgroup stores what lhn_bn_finalize leaves in memory.  No barrier here: the caller's next one publishes the slots and frees raw.
+__device__ __forceinline__ void lhn_bn_fin_channel(const lhn_bnfinsrc& f, const LhnFinPre& p, double s1, double s2, int c0, int cl,
+                                                   bool lead, float* tab, int ld) {
+  const int c = c0 + cl;
+  double mean, var;
+  lhn_bn_fin_moments(s1, s2, f.count, mean, var);
+  const LhnFinTab t = lhn_bn_fin_tab(mean, var, f.eps, p.gamma, p.beta);
+  tab[cl] = t.sc;
+  tab[ld + cl] = t.sh;
+  tab[2 * ld + cl] = f.slope;
+  if (lead) {
+    if (f.running_mean) lhn_bn_fin_running(f.running_mean, f.running_var, c, p.rm, p.rv, mean, var, (double)p.cb, f.count, f.momentum);
+    f.table[f.coff + c] = t.sc;
+    f.table[f.cstride + f.coff + c] = t.sh;
+    f.table[2 * f.cstride + f.coff + c] = f.slope;
+    if (f.save_mean_invstd) {
+      f.save_mean_invstd[c] = (float)mean;
+      f.save_mean_invstd[f.C + c] = t.invstd;
+    }
+    if (c == 0 && f.num_batches_tracked) f.num_batches_tracked[0] += 1;
+  }
+}
+__device__ __forceinline__ Xf4 lhn_bn_fin_xf(const float* tab, int ld, int cl4) {
+  Xf4 t;
+  t.sc = *reinterpret_cast<const f4*>(tab + cl4);
+  t.sh = *reinterpret_cast<const f4*>(tab + ld + cl4);
+  t.sl = *reinterpret_cast<const f4*>(tab + 2 * ld + cl4);
+  return t;
+}
 static __device__ __forceinline__ lhn_bnfin lhn_nofin() {
   lhn_bnfin f;
   f.counter = nullptr;

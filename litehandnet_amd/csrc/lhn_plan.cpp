@@ -44,6 +44,7 @@ struct Plan {
   std::vector<lhn_buf> bufs;
   std::vector<lhn_op> fwd, bwd;
   std::vector<uint8_t> pw_dz_dead;     // per backward op: an NHWC PW_BWD whose dz no later op touches (pw_dz_dead_at)
+  std::vector<uint8_t> fwd_fin;        // per forward op: a convolution + BatchNorm whose finalize the next op takes (fwd_fin_consumer_at)
   std::vector<GraphEntry> graphs;     // LHN_GRAPH=1: replayed instead of ~150-400 individual launches
   uint64_t tick = 0;
   int graph_misses = 0;
@@ -135,6 +136,41 @@ static bool bwd_fin_consumer() {
     v = (e && e[0] == '0') ? 0 : 1;
   }
   return v == 1;
+}
+// LHN_FWD_FIN_CONSUMER (default 1, read once; 0 = the separate launches, for A/B runs): the same on the forward side.  A convolution +
+// BatchNorm whose next op is a single-source NHWC depthwise or 1x1 convolution over exactly the BatchNorm's output view does not
+// launch k_bn_finalize; the finished statistics go to that convolution's entry point (lhn_bnfinsrc: lhn_conv_dw_fwd4 /
+// lhn_conv_pw_fwd3), whose kernel folds them in its prologue, under its first tile's loads, and leaves the table, mean | invstd and the
+// running statistics in memory for every later reader.  Only where the route functions name a kernel with the fold: a consumer that
+// would issue the launch itself gains nothing.  Decided once per plan (lhn_plan_fwd_fin_consumer); training whole-plan runs only
+// (SyncBatchNorm ranges split the op at its second half and keep the launch), not with LHN_FUSE_FINALIZE, no padded channels, no unit
+// the reference evaluates twice; the op lists do not change.  Variant B: 30 of 52 BatchNorms.
+static bool fwd_fin_consumer() {
+  static int v = -1;
+  if (v < 0) {
+    const char* e = getenv("LHN_FWD_FIN_CONSUMER");
+    v = (e && e[0] == '0') ? 0 : 1;
+  }
+  return v == 1;
+}
+static bool fwd_fin_consumer_at(const Plan* P, const std::vector<lhn_op>& ops, size_t oi) {
+  if (!fwd_fin_consumer() || fuse_finalize() || oi + 1 >= ops.size()) return false;
+  const lhn_op &o = ops[oi], &nx = ops[oi + 1];
+  const bool conv = o.kind == OP_STEM || o.kind == OP_PW || o.kind == OP_DW || (o.kind == OP_KXK && o.i[1] != 1);
+  if (!conv || !conv_has_bn(o) || o.ws[0] < 0 || o.out_buf < 0 || (o.kind == OP_PW && (o.i[1] || o.i[2] > 0))) return false;
+  if ((o.kind == OP_PW || o.kind == OP_DW) && (int)o.f[3] > 1) return false;
+  if ((nx.kind != OP_DW && nx.kind != OP_PW) || nx.i[6] > 1) return false;
+  if (nx.in_buf[0] != o.out_buf || nx.in_coff[0] != o.out_coff || nx.in_C[0] != o.out_C) return false;
+  const lhn_buf& b = P->bufs[o.out_buf];
+  if (b.table_off < 0) return false;
+  const char* name;
+  if (nx.kind == OP_DW)
+    name = lhn_conv_dw_route(0, b.H, b.W, nx.in_C[0], nx.i[0], nx.i[1], nx.i[2], nx.i[3], LHN_DW_F_FINSRC | (nx.p[0] < 0 ? LHN_DW_F_NO_WEIGHT : 0), -1);
+  else
+    name = nx.i[1] ? nullptr
+                   : lhn_conv_pw_route(0, b.N, b.H, b.W, nx.in_C[0], nx.out_C, nx.i[0], nx.i[2], nx.i[3],
+                                       LHN_PW_F_FINSRC | (nx.ws[0] >= 0 ? LHN_PW_F_STATS : 0), -1);
+  return name && strncmp(name, "lhn_bn_finalize", 15) != 0;
 }
 // Gate-gradient sums in the head's backward (lhn_gatesum, LHN_HEAD_STREAM, default on; not in deterministic mode): when the backward
 // of an NCHW 1x1 (stride 1) STORES the gradient of its whole input buffer and the next op is the GATE_REDUCE of that buffer with
@@ -239,6 +275,8 @@ void* lhn_plan_create(const lhn_buf* bufs, int nbufs, const lhn_op* fwd, int nfw
         return nullptr;
       }
     }
+  p->fwd_fin.resize(p->fwd.size());
+  for (size_t oi = 0; oi < p->fwd.size(); ++oi) p->fwd_fin[oi] = fwd_fin_consumer_at(p, p->fwd, oi) ? 1 : 0;
   p->pw_dz_dead.resize(p->bwd.size());
   for (size_t oi = 0; oi < p->bwd.size(); ++oi) p->pw_dz_dead[oi] = pw_dz_dead_at(p, p->bwd, oi) ? 1 : 0;
   return p;
@@ -256,6 +294,12 @@ int lhn_plan_pw_dz_dead(void* plan, int bwd_index) {
   const Plan* p = static_cast<const Plan*>(plan);
   if (!p || bwd_index < 0 || (size_t)bwd_index >= p->pw_dz_dead.size()) return -1;
   return p->pw_dz_dead[bwd_index];
+}
+
+int lhn_plan_fwd_fin_consumer(void* plan, int fwd_index) {
+  const Plan* p = static_cast<const Plan*>(plan);
+  if (!p || fwd_index < 0 || (size_t)fwd_index >= p->fwd_fin.size()) return -1;
+  return p->fwd_fin[fwd_index];
 }
 
 void lhn_plan_destroy(void* plan) {
@@ -284,6 +328,21 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
   const bool whole = (sb == 0 && se >= 2 * ops.size());
   lhn_bnbwdsrc cfin;                    // finalize source of the BN_BWD op in front of op cfin_for (consumer-side finalize)
   size_t cfin_for = (size_t)-1;
+  lhn_bnfinsrc ffin;                    // finalize source of the forward convolution in front of op ffin_for (fwd_fin_consumer_at)
+  size_t ffin_for = (size_t)-1;
+  // the BatchNorm of forward op oi is finalized by op oi + 1: no launch here, the statistics travel with `fin`
+  auto hand_over = [&](size_t oi, const lhn_bnfin& fin, const double* stats) {
+    if (phase != 0 || !training || !whole || skip_tables || !P->fwd_fin[oi]) return false;
+    ffin.stats = stats;
+    ffin.gamma = fin.gamma; ffin.beta = fin.beta; ffin.conv_bias = fin.conv_bias;
+    ffin.running_mean = fin.running_mean; ffin.running_var = fin.running_var; ffin.num_batches_tracked = fin.num_batches_tracked;
+    ffin.table = fin.table; ffin.save_mean_invstd = fin.save_mean_invstd;
+    ffin.count = fin.count;
+    ffin.cstride = fin.cstride; ffin.coff = fin.coff; ffin.C = fin.C;
+    ffin.eps = fin.eps; ffin.momentum = fin.momentum; ffin.slope = fin.slope;
+    ffin_for = oi + 1;
+    return true;
+  };
   size_t gfold_at = (size_t)-1;         // the GATE_REDUCE op whose sums the head's backward in front of it added (head_gate_fold_at)
   for (size_t oi = 0; oi < ops.size() && rc == 0; ++oi) {
     const lhn_op& o = ops[oi];
@@ -327,7 +386,8 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
         if (h0) rc = lhn_conv_stem_fwd(static_cast<const float*>(io[0]), prm<const float>(params, o.p[0]), &y,
                                (training && o.ws[0] >= 0) ? reinterpret_cast<double*>(at(ws, o.ws[0])) : nullptr, o.i[3], o.i[4], o.i[0], o.i[1],
                                o.i[2], (bn && fz) ? &fin : nullptr, stream);
-        if (!rc && bn && h1 && !skip_tables && !deferred && !fz) rc = sep_finalize(fin, reinterpret_cast<const double*>(at(ws, o.ws[0])), training, stream);
+        if (!rc && bn && h1 && !skip_tables && !deferred && !fz && !hand_over(oi, fin, reinterpret_cast<const double*>(at(ws, o.ws[0]))))
+          rc = sep_finalize(fin, reinterpret_cast<const double*>(at(ws, o.ws[0])), training, stream);
         break;
       }
       case OP_PW: {
@@ -377,10 +437,10 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
           nchw += (int64_t)o.i[4] * khw;
           po.nchw_batch_stride = (int64_t)o.i[5] * khw;
         }
-        if (h0) rc = lhn_conv_pw_fwd2(&x, prm<const float>(params, o.p[0]), bn ? nullptr : prm<const float>(params, o.p[1]), &y,
+        if (h0) rc = lhn_conv_pw_fwd3(&x, prm<const float>(params, o.p[0]), bn ? nullptr : prm<const float>(params, o.p[1]), &y,
                               (training && o.ws[0] >= 0) ? reinterpret_cast<double*>(at(ws, o.ws[0])) : nullptr, o.i[0], nchw,
-                              (bn && fz) ? &fin : nullptr, &po, stream);
-        if (!rc && bn && h1 && !skip_tables && !deferred && !fz)
+                              (bn && fz) ? &fin : nullptr, &po, ffin_for == oi ? &ffin : nullptr, stream);
+        if (!rc && bn && h1 && !skip_tables && !deferred && !fz && !hand_over(oi, fin, reinterpret_cast<const double*>(at(ws, o.ws[0]))))
           rc = sep_finalize(fin, reinterpret_cast<const double*>(at(ws, o.ws[0])), training, stream, o.i[2], (int)o.f[3]);
         break;
       }
@@ -406,11 +466,11 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
           sumv.table = nullptr; sumv.gate = nullptr; sumv.pend = nullptr;
           sumv.cstride = (int)(o.ws[5] >> 16); sumv.coff = (int)(o.ws[5] & 0xffff);
         }
-        if (h0) rc = lhn_conv_dw_fwd3(&x, prm<const float>(params, o.p[0]), &y,
+        if (h0) rc = lhn_conv_dw_fwd4(&x, prm<const float>(params, o.p[0]), &y,
                               (training && o.ws[0] >= 0) ? reinterpret_cast<double*>(at(ws, o.ws[0])) : nullptr, o.i[0], o.i[1], o.i[2], o.i[3],
                               (bn && fz) ? &fin : nullptr, o.i[6] > 1 ? &extra : nullptr, coef2,
-                              so ? &sumv : nullptr, stream);
-        if (!rc && bn && h1 && !skip_tables && !deferred && !fz)
+                              so ? &sumv : nullptr, ffin_for == oi ? &ffin : nullptr, stream);
+        if (!rc && bn && h1 && !skip_tables && !deferred && !fz && !hand_over(oi, fin, reinterpret_cast<const double*>(at(ws, o.ws[0]))))
           rc = sep_finalize(fin, reinterpret_cast<const double*>(at(ws, o.ws[0])), training, stream, 0, (int)o.f[3]);
         break;
       }
@@ -439,7 +499,8 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
                               (training && o.ws[0] >= 0) ? reinterpret_cast<double*>(at(ws, o.ws[0])) : nullptr, o.i[0],
                               (bn && fz) ? &fin : nullptr,
                               o.ws[3] >= 0 ? reinterpret_cast<float*>(at(ws, o.ws[3])) : nullptr, stream);
-        if (!rc && bn && h1 && !skip_tables && !deferred && !fz) rc = sep_finalize(fin, reinterpret_cast<const double*>(at(ws, o.ws[0])), training, stream);
+        if (!rc && bn && h1 && !skip_tables && !deferred && !fz && !hand_over(oi, fin, reinterpret_cast<const double*>(at(ws, o.ws[0]))))
+          rc = sep_finalize(fin, reinterpret_cast<const double*>(at(ws, o.ws[0])), training, stream);
         break;
       }
       case OP_PWDW: {  // in: x, the intermediate buffer (only its table exists); p: w1, w2.  Inference plans only.
