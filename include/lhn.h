@@ -801,6 +801,57 @@ int lhn_cbam_bwd(const lhn_view* p, const lhn_view* r, const float* w1, const fl
 int lhn_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, double lr, double beta1,
                   double beta2, double eps, double weight_decay, int64_t step, void* stream);
 
+/* ---------------------------------------------------------------- pair launches
+ * Two independent calls of one pool / combine / finalize entry in ONE launch (blockIdx.y selects the job; each job keeps the grid,
+ * the replicas and the arithmetic of its single launch: every output is bit-identical to the two single calls, BatchNorm-backward
+ * sums included wherever the single calls are run-to-run reproducible).  A job struct holds the arguments of the single entry named
+ * in its comment, with the same meaning.  A pair entry refuses, before anything is launched and with the reason in
+ * lhn_last_error(): whatever the single entry refuses for either job; jobs whose geometry differs (N, H, W, C, source count and
+ * resolutions, pooled size); jobs whose outputs overlap (one base pointer and pixel stride: the channel ranges decide; otherwise
+ * the address ranges); and the forms without a two-job kernel -- product / bilinear combines, SiLU / ReLU-sigmoid combine backward,
+ * average pools with statistics or a copy source or on the small-bin kernel. */
+typedef struct lhn_maxpool_job {          /* lhn_maxpool2_fwd (x, y) / lhn_maxpool2_bwd3 (all) */
+  const lhn_view*      x;
+  const lhn_view*      y;
+  const float*         dy;
+  float*               dx;
+  int32_t              dx_accumulate;
+  const lhn_bnsum*     bns;              /* or NULL */
+  const lhn_grad_adds* adds;             /* or NULL */
+} lhn_maxpool_job;
+typedef struct lhn_ew_job {               /* lhn_ew_fwd3 (srcs .. mode) / lhn_ew_bwd3 (nsrc = 1) / lhn_ew_bwd_multi */
+  const lhn_view*         srcs;
+  int32_t                 nsrc;
+  const float*            coef;          /* forward, or NULL */
+  const lhn_view*         dst;
+  float                   out_slope;
+  int32_t                 mode;          /* forward */
+  const float*            ddst;          /* backward from here on */
+  const float*            dst_dpool;
+  float* const*           dsrcs;         /* [nsrc] */
+  const int*              accumulate;    /* [nsrc] */
+  const lhn_bnsum* const* bns;           /* [nsrc] or NULL */
+} lhn_ew_job;
+typedef struct lhn_avgpool_job {          /* lhn_avgpool_fwd2; pstat / copy_src (lhn_avgpool_fwd4) are refused */
+  const lhn_view*      x;
+  float*               out;
+  int32_t              OH, OW, out_cstride, out_coff;
+  float*               pstat;
+  const lhn_bn_slices* slices;
+  const lhn_view*      copy_src;
+} lhn_avgpool_job;
+int lhn_maxpool2_fwd_pair(const lhn_maxpool_job* a, const lhn_maxpool_job* b, void* stream);
+int lhn_maxpool2_bwd_pair(const lhn_maxpool_job* a, const lhn_maxpool_job* b, void* stream);
+int lhn_ew_fwd_pair(const lhn_ew_job* a, const lhn_ew_job* b, void* stream);
+int lhn_ew_bwd_pair(const lhn_ew_job* a, const lhn_ew_job* b, void* stream);
+int lhn_ew_bwd_multi_pair(const lhn_ew_job* a, const lhn_ew_job* b, void* stream);
+int lhn_avgpool_fwd_pair(const lhn_avgpool_job* a, const lhn_avgpool_job* b, void* stream);
+/* lhn_bn_finalize2 for two separate BatchNorms.  Per job: the statistics, the lhn_bnfin slice (counter unused; C = the channels the
+ * BatchNorm really has) and the channel stride of the statistics / save layout (>= C).  Tables, running statistics, saved
+ * mean | invstd and num_batches_tracked of the two jobs must not overlap. */
+int lhn_bn_finalize_pair(const double* stats_a, const lhn_bnfin* a, int stat_channels_a, const double* stats_b, const lhn_bnfin* b,
+                         int stat_channels_b, int training, void* stream);
+
 /* ---------------------------------------------------------------- plan executor
  * A plan is a static list of the calls above over one workspace arena, built by the Python
  * mirror of the reference's nn.Module tree (models/__init__.py:20-26 get_model).  One
@@ -837,6 +888,17 @@ int   lhn_plan_pw_dz_dead(void* plan, int bwd_index);
  * lhn_bnfinsrc): a whole-plan training run then launches no lhn_bn_finalize for it.  0 otherwise, also with LHN_FWD_FIN_CONSUMER=0
  * or LHN_FUSE_FINALIZE=1; -1: index out of range.  The op lists are the same either way. */
 int   lhn_plan_fwd_fin_consumer(void* plan, int fwd_index);
+/* Pair launches of a whole-plan run (phase 0 = forward list, 1 = backward list): 1 when op `index` is the first op of a pair, 2 when
+ * it is the second, 0 otherwise, also with LHN_PAIR_LAUNCH=0; -1: phase or index out of range.  Two kinds of pair:
+ *   pool / combine: ops index and index + 1 of one kind and mode (MAXPOOL, plain AVGPOOL on the workgroup kernel, sum EW, MAXPOOL_BWD,
+ *     leaky EW_BWD in its single- or multi-source form) with equal geometry, disjoint outputs (gradient buffers included, aliases too),
+ *     neither reading what the other writes: the first op launches an lhn_*_pair entry, the second launches nothing;
+ *   finalize (forward list, training and eval runs): two consecutive convolution + BatchNorm ops that both keep their separate
+ *     lhn_bn_finalize launch (not handed to the next convolution, no LHN_FUSE_FINALIZE, no padded or twice-evaluated unit), the
+ *     second convolution reading nothing of the first one's output: the first finalize waits and runs as job 0 of the second
+ *     one's lhn_bn_finalize_pair.
+ * lhn_plan_run_range never pairs.  The op lists are the same either way. */
+int   lhn_plan_pair(void* plan, int phase, int index);
 /* io: phase 0 {image NCHW, heatmap NCHW out}; phase 1 {image NCHW, d(heatmap) NCHW}.
  * training: a bit set -- bit 0 = train-mode BatchNorm (batch statistics, running statistics updated); bit 1 (LHN_RUN_TABLES_CURRENT,
  * eval only) = the workspace's per-buffer BatchNorm tables were built by an earlier eval run of THIS plan and no parameter

@@ -59,6 +59,8 @@ SYMBOLS = [
     "lhn_ca_mlp_bwd", "lhn_reduce_replicas", "lhn_fold_stat_replicas", "lhn_plan_create", "lhn_plan_destroy", "lhn_plan_run", "lhn_plan_run_range",
     "lhn_cbam_layout", "lhn_cbam_fwd", "lhn_cbam_bwd",
     "lhn_ccw_scratch_bytes", "lhn_ccw_pool_fwd", "lhn_ccw_gate_fwd", "lhn_ccw_dw_fwd", "lhn_ccw_shuffle_fwd",
+    "lhn_maxpool2_fwd_pair", "lhn_maxpool2_bwd_pair", "lhn_ew_fwd_pair", "lhn_ew_bwd_pair", "lhn_ew_bwd_multi_pair", "lhn_avgpool_fwd_pair",
+    "lhn_bn_finalize_pair", "lhn_plan_pair",
 ]
 
 

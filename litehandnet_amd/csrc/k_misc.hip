@@ -17,21 +17,23 @@ static inline bool pow2i(int v) { return v > 0 && (v & (v - 1)) == 0; }
 // together), the G partial sums of a channel meet in LDS in a fixed order (run-to-run reproducible), one thread per channel
 // does the arithmetic.  (The first version walked one thread per channel through 64 dependent double loads: 6 us per launch,
 // 52 launches per forward of the MSRB hourglass.)  LHN_FIN_THREADS = 1024: lhn_common.h.
-__global__ void __launch_bounds__(LHN_FIN_THREADS) k_bn_finalize(const double* __restrict__ stats, const float* __restrict__ gamma,
+// One job = one BatchNorm.  nt = the threads the single launcher gives this BatchNorm: k_bn_finalize runs with exactly nt, the pair
+// kernel with the larger of its two jobs' -- threads past nt only keep the barriers company, so a job folds its replicas in the same
+// groups and the same order in either launch.
+__device__ __forceinline__ void bn_finalize_job(const double* __restrict__ stats, const float* __restrict__ gamma,
                               const float* __restrict__ beta, float* __restrict__ rmean, float* __restrict__ rvar,
                               int64_t* __restrict__ nbt, float* __restrict__ table, int cs, int coff, int C,
                               float* __restrict__ save, double count, float eps, float momentum, float slope, int training,
-                              const float* __restrict__ cbias, int SC) {
+                              const float* __restrict__ cbias, int SC, int nt, double* __restrict__ part) {
   // SC = channels of the statistics / save layout (>= C: a convolution whose output view is padded to a multiple of 4
   // accumulates SC columns, the BatchNorm owns the first C)
-  __shared__ double part[2 * LHN_FIN_THREADS];
-  const int nt = blockDim.x;
+  const bool mine = (int)threadIdx.x < nt;
   int G = nt / C;
   G = G < 1 ? 1 : (G > LHN_STAT_REPLICAS ? LHN_STAT_REPLICAS : G);
   for (int c0 = 0; c0 < C; c0 += nt) {           // (one round unless C > 1024)
     const int g = threadIdx.x / C, c = c0 + (G > 1 ? threadIdx.x - g * C : threadIdx.x);
     if (c0) __syncthreads();
-    if (training && g < G && c < C) {
+    if (training && mine && g < G && c < C) {
       double s1 = 0, s2 = 0;
 #pragma unroll 4
       for (int r = g; r < LHN_STAT_REPLICAS; r += G) {
@@ -42,7 +44,7 @@ __global__ void __launch_bounds__(LHN_FIN_THREADS) k_bn_finalize(const double* _
       part[2 * threadIdx.x + 1] = s2;
     }
     __syncthreads();
-    if (g != 0 || c >= C) continue;
+    if (!mine || g != 0 || c >= C) continue;
     double mean, var;
     const double cb = cbias ? (double)cbias[c] : 0.0;   // bias of the conv in front: stored output excludes it
     if (training) {
@@ -68,6 +70,35 @@ __global__ void __launch_bounds__(LHN_FIN_THREADS) k_bn_finalize(const double* _
     }
   }
   if (training && nbt && threadIdx.x == 0) nbt[0] += 1;
+}
+__global__ void __launch_bounds__(LHN_FIN_THREADS) k_bn_finalize(const double* __restrict__ stats, const float* __restrict__ gamma,
+                              const float* __restrict__ beta, float* __restrict__ rmean, float* __restrict__ rvar,
+                              int64_t* __restrict__ nbt, float* __restrict__ table, int cs, int coff, int C,
+                              float* __restrict__ save, double count, float eps, float momentum, float slope, int training,
+                              const float* __restrict__ cbias, int SC) {
+  __shared__ double part[2 * LHN_FIN_THREADS];
+  bn_finalize_job(stats, gamma, beta, rmean, rvar, nbt, table, cs, coff, C, save, count, eps, momentum, slope, training, cbias, SC,
+                  blockDim.x, part);
+}
+// Two BatchNorms in one launch: blockIdx.y selects the job (one workgroup each).  The jobs are separate by-value structs read
+// through a uniform branch, never an array indexed by the block (such an array ends up in scratch).
+struct FinJob {
+  const double* stats;
+  const float *gamma, *beta, *cbias;
+  float *rmean, *rvar, *table, *save;
+  int64_t* nbt;
+  double count;
+  int cs, coff, C, SC, nt;
+  float eps, momentum, slope;
+};
+__global__ void __launch_bounds__(LHN_FIN_THREADS) k_bn_finalize_pair(FinJob a, FinJob b, int training) {
+  __shared__ double part[2 * LHN_FIN_THREADS];
+  if (blockIdx.y == 0)
+    bn_finalize_job(a.stats, a.gamma, a.beta, a.rmean, a.rvar, a.nbt, a.table, a.cs, a.coff, a.C, a.save, a.count, a.eps, a.momentum,
+                    a.slope, training, a.cbias, a.SC, a.nt, part);
+  else
+    bn_finalize_job(b.stats, b.gamma, b.beta, b.rmean, b.rvar, b.nbt, b.table, b.cs, b.coff, b.C, b.save, b.count, b.eps, b.momentum,
+                    b.slope, training, b.cbias, b.SC, b.nt, part);
 }
 
 __global__ void k_table_fill(float* __restrict__ table, int cs, int coff, int C, float sc, float sh, float sl) {
@@ -123,7 +154,7 @@ __device__ __forceinline__ int nearest_src(int d, int in, int out) {
   return s < in - 1 ? s : in - 1;
 }
 template <bool BIL>
-__global__ void __launch_bounds__(256, BIL ? 1 : 3) k_ew_fwd(EwSrcs S, int nsrc, lhn_view dst, float out_slope) {
+__device__ __forceinline__ void ew_fwd_body(const EwSrcs& S, int nsrc, const lhn_view& dst, float out_slope) {
   const int C4 = dst.C >> 2, c4 = threadIdx.x % C4, pl = threadIdx.x / C4, PL = 256 / C4;
   const int rows = dst.N * dst.H;
   Xf4 xf[3];
@@ -235,13 +266,28 @@ __global__ void __launch_bounds__(256, BIL ? 1 : 3) k_ew_fwd(EwSrcs S, int nsrc,
     }
   }
 }
+template <bool BIL>
+__global__ void __launch_bounds__(256, BIL ? 1 : 3) k_ew_fwd(EwSrcs S, int nsrc, lhn_view dst, float out_slope) {
+  ew_fwd_body<BIL>(S, nsrc, dst, out_slope);
+}
+// Pair kernels (this one and the *_pair kernels below): two jobs of equal geometry in one launch, blockIdx.y selects the job and
+// blockIdx.x is the single launch's grid.  Every job argument is a by-value struct of its own, read behind ONE uniform branch.
+struct EwFwdJob {
+  EwSrcs S;
+  int nsrc;
+  lhn_view dst;
+  float out_slope;
+};
+__global__ void __launch_bounds__(256, 3) k_ew_fwd_pair(EwFwdJob a, EwFwdJob b) {
+  if (blockIdx.y == 0) ew_fwd_body<false>(a.S, a.nsrc, a.dst, a.out_slope);
+  else ew_fwd_body<false>(b.S, b.nsrc, b.dst, b.out_slope);
+}
 
 // backward of the combine: d(value_i) (+)= d(dst) * lrelu'(dst); upsampled sources sum their fan-out.
 // One launch per source (gather form: each source element sums the dst elements that read it).
-__global__ void __launch_bounds__(256) k_ew_bwd_src(lhn_view src, lhn_view dst, const float* __restrict__ ddst,
-                                                    const float* __restrict__ dst_dpool, float out_slope,
-                                                    float* __restrict__ dsrc, int accumulate, lhn_bnsum bs) {
-  __shared__ f4 bred[512];
+__device__ __forceinline__ void ew_bwd_src_job(const lhn_view& src, const lhn_view& dst, const float* __restrict__ ddst,
+                                               const float* __restrict__ dst_dpool, float out_slope,
+                                               float* __restrict__ dsrc, int accumulate, const lhn_bnsum& bs, f4* bred) {
   const int C4 = src.C >> 2, c4 = threadIdx.x % C4, pl = threadIdx.x / C4, PL = 256 / C4;
   // bs.sums: this launch's part of the BatchNorm-backward sums of the convolution that produced src (see lhn_bnsum)
   f4 bsum = (f4){0.f, 0.f, 0.f, 0.f}, bsq = bsum, bmean = bsum, binv = bsum;
@@ -305,6 +351,25 @@ __global__ void __launch_bounds__(256) k_ew_bwd_src(lhn_view src, lhn_view dst, 
   }
   if (bs.sums) lhn_bns_flush(bs, bsum, bsq, C4, bred);
 }
+__global__ void __launch_bounds__(256) k_ew_bwd_src(lhn_view src, lhn_view dst, const float* __restrict__ ddst,
+                                                    const float* __restrict__ dst_dpool, float out_slope,
+                                                    float* __restrict__ dsrc, int accumulate, lhn_bnsum bs) {
+  __shared__ f4 bred[512];
+  ew_bwd_src_job(src, dst, ddst, dst_dpool, out_slope, dsrc, accumulate, bs, bred);
+}
+struct EwBwdSrcJob {
+  lhn_view src, dst;
+  const float *ddst, *dst_dpool;
+  float* dsrc;
+  float out_slope;
+  int accumulate;
+  lhn_bnsum bs;
+};
+__global__ void __launch_bounds__(256) k_ew_bwd_src_pair(EwBwdSrcJob a, EwBwdSrcJob b) {
+  __shared__ f4 bred[512];
+  if (blockIdx.y == 0) ew_bwd_src_job(a.src, a.dst, a.ddst, a.dst_dpool, a.out_slope, a.dsrc, a.accumulate, a.bs, bred);
+  else ew_bwd_src_job(b.src, b.dst, b.ddst, b.dst_dpool, b.out_slope, b.dsrc, b.accumulate, b.bs, bred);
+}
 
 // The same for up to THREE sources of the destination's own resolution in one pass (residual sums: d(dst) * lrelu'(dst) is the
 // gradient of every one of them): d(dst) and dst are read once instead of once per source.
@@ -315,9 +380,8 @@ struct EwBwdMulti {
   int acc[3];
   lhn_bnsum bs[3];
 };
-__global__ void __launch_bounds__(256) k_ew_bwd_multi(EwBwdMulti m, lhn_view dst, const float* __restrict__ ddst,
-                                                      const float* __restrict__ dst_dpool, float out_slope) {
-  __shared__ f4 bred[512];
+__device__ __forceinline__ void ew_bwd_multi_job(const EwBwdMulti& m, const lhn_view& dst, const float* __restrict__ ddst,
+                                                 const float* __restrict__ dst_dpool, float out_slope, f4* bred) {
   const int C4 = dst.C >> 2, c4 = threadIdx.x % C4, pl = threadIdx.x / C4, PL = 256 / C4;
   f4 bsum[3], bsq[3], bmean[3], binv[3];
   Xf4 bxf[3];
@@ -374,9 +438,25 @@ __global__ void __launch_bounds__(256) k_ew_bwd_multi(EwBwdMulti m, lhn_view dst
       __syncthreads();
     }
 }
+__global__ void __launch_bounds__(256) k_ew_bwd_multi(EwBwdMulti m, lhn_view dst, const float* __restrict__ ddst,
+                                                      const float* __restrict__ dst_dpool, float out_slope) {
+  __shared__ f4 bred[512];
+  ew_bwd_multi_job(m, dst, ddst, dst_dpool, out_slope, bred);
+}
+struct EwBwdMultiJob {
+  EwBwdMulti m;
+  lhn_view dst;
+  const float *ddst, *dst_dpool;
+  float out_slope;
+};
+__global__ void __launch_bounds__(256) k_ew_bwd_multi_pair(EwBwdMultiJob a, EwBwdMultiJob b) {
+  __shared__ f4 bred[512];
+  if (blockIdx.y == 0) ew_bwd_multi_job(a.m, a.dst, a.ddst, a.dst_dpool, a.out_slope, bred);
+  else ew_bwd_multi_job(b.m, b.dst, b.ddst, b.dst_dpool, b.out_slope, bred);
+}
 
 // ------------------------------------------------------------------ 2x2 stride-2 max pool (ceil_mode)
-__global__ void __launch_bounds__(256) k_maxpool2_fwd(lhn_view x, lhn_view y) {
+__device__ __forceinline__ void maxpool2_fwd_job(const lhn_view& x, const lhn_view& y) {
   const int C4 = y.C >> 2, c4 = threadIdx.x % C4, pl = threadIdx.x / C4, PL = 256 / C4;
   const int ca = x.coff + 4 * c4;
   const Xf4 xf = lhn_load_xf(x, ca);
@@ -401,14 +481,22 @@ __global__ void __launch_bounds__(256) k_maxpool2_fwd(lhn_view x, lhn_view y) {
     }
   }
 }
+__global__ void __launch_bounds__(256) k_maxpool2_fwd(lhn_view x, lhn_view y) { maxpool2_fwd_job(x, y); }
+struct MaxpoolFwdJob {
+  lhn_view x, y;
+};
+__global__ void __launch_bounds__(256) k_maxpool2_fwd_pair(MaxpoolFwdJob a, MaxpoolFwdJob b) {
+  if (blockIdx.y == 0) maxpool2_fwd_job(a.x, a.y);
+  else maxpool2_fwd_job(b.x, b.y);
+}
 // gradient goes to the first window element (scan order) holding the max.  One thread per OUTPUT element
 // re-evaluates its 2x2 window (every input pixel belongs to exactly one window), so the comparison never
 // depends on two kernels rounding the pending transform identically.
 // ADD: the gradients of other readers of x (lhn_grad_adds) join the same store -- one pass over d(x) instead of three
 template <bool ADD>
-__global__ void __launch_bounds__(256) k_maxpool2_bwd(lhn_view x, lhn_view y, const float* __restrict__ dy,
-                                                      float* __restrict__ dx, int accumulate, lhn_bnsum bs, lhn_grad_adds ad) {
-  __shared__ f4 bred[512];
+__device__ __forceinline__ void maxpool2_bwd_job(const lhn_view& x, const lhn_view& y, const float* __restrict__ dy,
+                                                 float* __restrict__ dx, int accumulate, const lhn_bnsum& bs, const lhn_grad_adds& ad,
+                                                 f4* bred) {
   const int C4 = y.C >> 2, c4 = threadIdx.x % C4, pl = threadIdx.x / C4, PL = 256 / C4;
   const int ca = x.coff + 4 * c4;
   const Xf4 xf = lhn_load_xf(x, ca);
@@ -473,6 +561,28 @@ __global__ void __launch_bounds__(256) k_maxpool2_bwd(lhn_view x, lhn_view y, co
   }
   if (bs.sums) lhn_bns_flush(bs, bsum, bsq, C4, bred);
 }
+template <bool ADD>
+__global__ void __launch_bounds__(256) k_maxpool2_bwd(lhn_view x, lhn_view y, const float* __restrict__ dy,
+                                                      float* __restrict__ dx, int accumulate, lhn_bnsum bs, lhn_grad_adds ad) {
+  __shared__ f4 bred[512];
+  maxpool2_bwd_job<ADD>(x, y, dy, dx, accumulate, bs, ad, bred);
+}
+// (ADD: either job carries addends; a job without any has NULL pointers in its own lhn_grad_adds and skips them as the single
+// ADD instance does)
+struct MaxpoolBwdJob {
+  lhn_view x, y;
+  const float* dy;
+  float* dx;
+  int accumulate;
+  lhn_bnsum bs;
+  lhn_grad_adds ad;
+};
+template <bool ADD>
+__global__ void __launch_bounds__(256) k_maxpool2_bwd_pair(MaxpoolBwdJob a, MaxpoolBwdJob b) {
+  __shared__ f4 bred[512];
+  if (blockIdx.y == 0) maxpool2_bwd_job<ADD>(a.x, a.y, a.dy, a.dx, a.accumulate, a.bs, a.ad, bred);
+  else maxpool2_bwd_job<ADD>(b.x, b.y, b.dy, b.dx, b.accumulate, b.bs, b.ad, bred);
+}
 
 // BatchNorms behind channel slices of one buffer (a gated buffer is written by up to two convolutions, each with its own
 // BatchNorm): saved (mean | invstd) per slice, optionally the slice's BatchNorm-backward sums.  Channels outside every slice
@@ -506,9 +616,8 @@ __device__ __forceinline__ f4 lhn_dact4(f4 raw, const Xf4& t) {      // derivati
 // pass-through half, which nobody has written yet -- this kernel reads them from `src` (pending transform and gate applied),
 // pools them AND stores them into x (each pixel by the one bin that owns it): the separate copy pass and its re-read disappear.
 template <bool STAT, bool COPY>
-__global__ void __launch_bounds__(256) k_avgpool_fwd(lhn_view x, float* __restrict__ out, int OH, int OW, int ostride,
-                                                     int ocoff, float* __restrict__ pstat, BnSlices sl, lhn_view src) {
-  __shared__ f4 red[STAT ? 768 : 256];
+__device__ __forceinline__ void avgpool_fwd_job(const lhn_view& x, float* __restrict__ out, int OH, int OW, int ostride,
+                                                int ocoff, float* __restrict__ pstat, const BnSlices& sl, const lhn_view& src, f4* red) {
   const int C4 = x.C >> 2, PL = 256 / C4;
   const int b = blockIdx.x;
   const int ow = b % OW, oh = (b / OW) % OH, n = b / (OW * OH);
@@ -616,6 +725,25 @@ __global__ void __launch_bounds__(256) k_avgpool_fwd(lhn_view x, float* __restri
       *reinterpret_cast<f4*>(pstat + ((int64_t)b * 2 + 1) * x.C + 4 * threadIdx.x) = t1;
     }
   }
+}
+template <bool STAT, bool COPY>
+__global__ void __launch_bounds__(256) k_avgpool_fwd(lhn_view x, float* __restrict__ out, int OH, int OW, int ostride,
+                                                     int ocoff, float* __restrict__ pstat, BnSlices sl, lhn_view src) {
+  __shared__ f4 red[STAT ? 768 : 256];
+  avgpool_fwd_job<STAT, COPY>(x, out, OH, OW, ostride, ocoff, pstat, sl, src, red);
+}
+// the plain form (no STAT, no COPY) for two jobs: their slices and copy source are empty
+struct AvgpoolFwdJob {
+  lhn_view x;
+  float* out;
+  int ostride, ocoff;
+};
+__global__ void __launch_bounds__(256) k_avgpool_fwd_pair(AvgpoolFwdJob a, AvgpoolFwdJob b, int OH, int OW) {
+  __shared__ f4 red[256];
+  BnSlices sl;
+  sl.n = 0;
+  if (blockIdx.y == 0) avgpool_fwd_job<false, false>(a.x, a.out, OH, OW, a.ostride, a.ocoff, nullptr, sl, a.x, red);
+  else avgpool_fwd_job<false, false>(b.x, b.out, OH, OW, b.ostride, b.ocoff, nullptr, sl, b.x, red);
 }
 // Small bins (<= 16 pixels: the 2x2 / 4x4 bins of lite_hrnet.py:56-60, every branch pooled to the smallest map): one THREAD
 // per (bin, 4 channels) instead of one workgroup per bin -- 65,536 workgroups of 4 pixels each took 121 us for a 42 MB map.
@@ -1740,9 +1868,10 @@ int lhn_bn_finalize(const double* stats, const float* gamma, const float* beta, 
   return lhn_bn_finalize2(stats, gamma, beta, running_mean, running_var, nbt, table, cstride, coff, C, C, save, count, eps, momentum,
                           slope, training, conv_bias, stream);
 }
-int lhn_bn_finalize2(const double* stats, const float* gamma, const float* beta, float* running_mean, float* running_var,
-                     int64_t* nbt, float* table, int cstride, int coff, int C, int stat_channels, float* save, double count,
-                     float eps, float momentum, float slope, int training, const float* conv_bias, void* stream) {
+// checks and launch geometry of one finalize: what lhn_bn_finalize2 launches and what lhn_bn_finalize_pair takes as a job
+static int fin_args(const double* stats, const float* gamma, const float* beta, float* running_mean, float* running_var, int64_t* nbt,
+                   float* table, int cstride, int coff, int C, int stat_channels, float* save, double count, float eps, float momentum,
+                   float slope, int training, const float* conv_bias, FinJob* j) {
   LHN_CHECK_ARG(table && C > 0 && coff >= 0 && coff + C <= cstride && stat_channels >= C, "lhn_bn_finalize: bad table slice");
   LHN_CHECK_ARG(training ? (stats != nullptr) : (running_mean && running_var), "lhn_bn_finalize: missing statistics");
   LHN_CHECK_ARG(!training || count >= 1, "lhn_bn_finalize: count");
@@ -1750,10 +1879,53 @@ int lhn_bn_finalize2(const double* stats, const float* gamma, const float* beta,
   int nt = training ? (C >= LHN_FIN_THREADS ? LHN_FIN_THREADS : (LHN_FIN_THREADS / C > LHN_STAT_REPLICAS ? LHN_STAT_REPLICAS : LHN_FIN_THREADS / C) * C)
                     : (C <= 64 ? 64 : (C <= 128 ? 128 : 256));
   nt = (nt + 63) / 64 * 64;
-  hipLaunchKernelGGL(k_bn_finalize, dim3(1), dim3(nt), 0, (hipStream_t)stream, stats,
+  j->stats = stats; j->gamma = gamma; j->beta = beta; j->cbias = conv_bias;
+  j->rmean = running_mean; j->rvar = running_var; j->table = table; j->save = save; j->nbt = nbt;
+  j->count = count;
+  j->cs = cstride; j->coff = coff; j->C = C; j->SC = stat_channels; j->nt = nt;
+  j->eps = eps; j->momentum = momentum; j->slope = slope;
+  return 0;
+}
+int lhn_bn_finalize2(const double* stats, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                     int64_t* nbt, float* table, int cstride, int coff, int C, int stat_channels, float* save, double count,
+                     float eps, float momentum, float slope, int training, const float* conv_bias, void* stream) {
+  FinJob j;
+  if (fin_args(stats, gamma, beta, running_mean, running_var, nbt, table, cstride, coff, C, stat_channels, save, count, eps, momentum, slope,
+              training, conv_bias, &j))
+    return 1;
+  hipLaunchKernelGGL(k_bn_finalize, dim3(1), dim3(j.nt), 0, (hipStream_t)stream, stats,
                      gamma, beta, running_mean, running_var, nbt, table, cstride, coff, C, save, count, eps, momentum,
                      slope, training, conv_bias, stat_channels);
   LHN_CHECK_LAUNCH("lhn_bn_finalize");
+  return 0;
+}
+// [a, a + na) and [b, b + nb) floats share an element (NULL: nothing)
+static bool spans_meet(const float* a, int64_t na, const float* b, int64_t nb) {
+  return a && b && a < b + nb && b < a + na;
+}
+// two channel views [coff, coff + C) of `pix` pixels at pixel stride cs: the same base and stride -> the channel ranges decide;
+// anything else -> the address ranges from the first to the last element
+static bool views_meet(const float* a, int64_t pix_a, int cs_a, int co_a, int C_a, const float* b, int64_t pix_b, int cs_b, int co_b, int C_b) {
+  if (!a || !b) return false;
+  if (a == b && cs_a == cs_b) return co_a < co_b + C_b && co_b < co_a + C_a;
+  return spans_meet(a + co_a, (pix_a - 1) * cs_a + C_a, b + co_b, (pix_b - 1) * cs_b + C_b);
+}
+int lhn_bn_finalize_pair(const double* stats_a, const lhn_bnfin* a, int stat_channels_a, const double* stats_b, const lhn_bnfin* b,
+                         int stat_channels_b, int training, void* stream) {
+  LHN_CHECK_ARG(a && b, "lhn_bn_finalize_pair: two jobs");
+  FinJob ja, jb;
+  if (fin_args(stats_a, a->gamma, a->beta, a->running_mean, a->running_var, a->num_batches_tracked, a->table, a->cstride, a->coff, a->C,
+              stat_channels_a, a->save_mean_invstd, a->count, a->eps, a->momentum, a->slope, training, a->conv_bias, &ja) ||
+      fin_args(stats_b, b->gamma, b->beta, b->running_mean, b->running_var, b->num_batches_tracked, b->table, b->cstride, b->coff, b->C,
+              stat_channels_b, b->save_mean_invstd, b->count, b->eps, b->momentum, b->slope, training, b->conv_bias, &jb))
+    return 1;
+  LHN_CHECK_ARG(!views_meet(ja.table, 3, ja.cs, ja.coff, ja.C, jb.table, 3, jb.cs, jb.coff, jb.C), "lhn_bn_finalize_pair: the table slices overlap");
+  LHN_CHECK_ARG(!training || (!spans_meet(ja.rmean, ja.C, jb.rmean, jb.C) && !spans_meet(ja.rvar, ja.C, jb.rvar, jb.C) &&
+                              !spans_meet(ja.rmean, ja.C, jb.rvar, jb.C) && !spans_meet(ja.rvar, ja.C, jb.rmean, jb.C) &&
+                              !(ja.nbt && ja.nbt == jb.nbt) && !spans_meet(ja.save, 2 * ja.SC, jb.save, 2 * jb.SC)),
+                "lhn_bn_finalize_pair: running statistics, num_batches_tracked or saved statistics overlap");
+  hipLaunchKernelGGL(k_bn_finalize_pair, dim3(1, 2), dim3(ja.nt > jb.nt ? ja.nt : jb.nt), 0, (hipStream_t)stream, ja, jb, training);
+  LHN_CHECK_LAUNCH("lhn_bn_finalize_pair");
   return 0;
 }
 
@@ -1777,22 +1949,54 @@ int lhn_ew_fwd(const lhn_view* srcs, int nsrc, const lhn_view* dst, float out_sl
 int lhn_ew_fwd2(const lhn_view* srcs, int nsrc, const float* coef, const lhn_view* dst, float out_slope, void* stream) {
   return lhn_ew_fwd3(srcs, nsrc, coef, dst, out_slope, 0, stream);
 }
-int lhn_ew_fwd3(const lhn_view* srcs, int nsrc, const float* coef, const lhn_view* dst, float out_slope, int mode, void* stream) {
+// Every pool / combine launcher below is split the same way: *_args checks one call's arguments and fills the kernel's job struct,
+// the single entry launches it, the *_pair entry checks two of them against each other and launches both (see include/lhn.h).
+static int ew_fwd_args(const lhn_view* srcs, int nsrc, const float* coef, const lhn_view* dst, float out_slope, int mode, EwFwdJob* j) {
   LHN_CHECK_ARG(srcs && nsrc >= 1 && nsrc <= 3 && lhn_view_ok(dst) && mode >= 0 && mode <= 3, "lhn_ew_fwd: 1..3 sources, valid dst");
-  EwSrcs S;
-  memset(&S, 0, sizeof(S));
-  S.mode = mode;
+  memset(j, 0, sizeof(*j));
+  j->S.mode = mode;
   for (int i = 0; i < nsrc; ++i) {
     LHN_CHECK_ARG(lhn_view_ok(&srcs[i]) && srcs[i].C == dst->C && srcs[i].N == dst->N && lhn_no_pend(&srcs[i]), "lhn_ew_fwd: source %d mismatch", i);
-    S.v[i] = srcs[i];
-    S.coef[i] = coef ? coef[i] : 1.f;
+    j->S.v[i] = srcs[i];
+    j->S.coef[i] = coef ? coef[i] : 1.f;
   }
   LHN_CHECK_ARG(dst->C % 4 == 0 && dst->C <= 1024, "lhn_ew_fwd: C=%d", dst->C);
-  if (S.mode & 2)
-    hipLaunchKernelGGL(k_ew_fwd<true>, dim3(grid_cap((int64_t)dst->N * dst->H, 8)), dim3(256), 0, (hipStream_t)stream, S, nsrc, *dst, out_slope);
+  j->nsrc = nsrc;
+  j->dst = *dst;
+  j->out_slope = out_slope;
+  return 0;
+}
+int lhn_ew_fwd3(const lhn_view* srcs, int nsrc, const float* coef, const lhn_view* dst, float out_slope, int mode, void* stream) {
+  EwFwdJob j;
+  if (ew_fwd_args(srcs, nsrc, coef, dst, out_slope, mode, &j)) return 1;
+  if (j.S.mode & 2)
+    hipLaunchKernelGGL(k_ew_fwd<true>, dim3(grid_cap((int64_t)dst->N * dst->H, 8)), dim3(256), 0, (hipStream_t)stream, j.S, nsrc, *dst, out_slope);
   else
-    hipLaunchKernelGGL(k_ew_fwd<false>, dim3(grid_cap((int64_t)dst->N * dst->H, 8)), dim3(256), 0, (hipStream_t)stream, S, nsrc, *dst, out_slope);
+    hipLaunchKernelGGL(k_ew_fwd<false>, dim3(grid_cap((int64_t)dst->N * dst->H, 8)), dim3(256), 0, (hipStream_t)stream, j.S, nsrc, *dst, out_slope);
   LHN_CHECK_LAUNCH("lhn_ew_fwd");
+  return 0;
+}
+static bool same_geometry(const lhn_view& a, const lhn_view& b) { return a.N == b.N && a.H == b.H && a.W == b.W && a.C == b.C; }
+static bool view_outputs_meet(const lhn_view& a, const lhn_view& b) {
+  return views_meet(a.data, (int64_t)a.N * a.H * a.W, a.cstride, a.coff, a.C, b.data, (int64_t)b.N * b.H * b.W, b.cstride, b.coff, b.C);
+}
+// gradient of view v's values at base d (v's own layout)
+static bool grad_outputs_meet(const float* da, const lhn_view& a, const float* db, const lhn_view& b) {
+  return views_meet(da, (int64_t)a.N * a.H * a.W, a.cstride, a.coff, a.C, db, (int64_t)b.N * b.H * b.W, b.cstride, b.coff, b.C);
+}
+int lhn_ew_fwd_pair(const lhn_ew_job* a, const lhn_ew_job* b, void* stream) {
+  LHN_CHECK_ARG(a && b, "lhn_ew_fwd_pair: two jobs");
+  EwFwdJob ja, jb;
+  if (ew_fwd_args(a->srcs, a->nsrc, a->coef, a->dst, a->out_slope, a->mode, &ja) ||
+      ew_fwd_args(b->srcs, b->nsrc, b->coef, b->dst, b->out_slope, b->mode, &jb))
+    return 1;
+  LHN_CHECK_ARG(a->mode == 0 && b->mode == 0, "lhn_ew_fwd_pair: product and bilinear combines take lhn_ew_fwd3");
+  bool geo = same_geometry(ja.dst, jb.dst) && ja.nsrc == jb.nsrc;
+  for (int i = 0; geo && i < ja.nsrc; ++i) geo = same_geometry(ja.S.v[i], jb.S.v[i]);
+  LHN_CHECK_ARG(geo, "lhn_ew_fwd_pair: the two jobs differ in geometry");
+  LHN_CHECK_ARG(!view_outputs_meet(ja.dst, jb.dst), "lhn_ew_fwd_pair: the two outputs overlap");
+  hipLaunchKernelGGL(k_ew_fwd_pair, dim3(grid_cap((int64_t)ja.dst.N * ja.dst.H, 8), 2), dim3(256), 0, (hipStream_t)stream, ja, jb);
+  LHN_CHECK_LAUNCH("lhn_ew_fwd_pair");
   return 0;
 }
 
@@ -1831,6 +2035,18 @@ static int bns_of(const lhn_bnsum* in, const lhn_view* v, lhn_bnsum* out, const 
   *out = *in;
   return 0;
 }
+static int ew_bwd_src_args(const lhn_view* src, const lhn_view* dst, const float* ddst, const float* dst_dpool, float out_slope,
+                           float* dsrc, int accumulate, const lhn_bnsum* bns, EwBwdSrcJob* j) {
+  LHN_CHECK_ARG(lhn_view_ok(src) && lhn_view_ok(dst) && ddst && dsrc && src->C == dst->C && lhn_no_pend(src) && lhn_no_pend(dst), "lhn_ew_bwd2: bad args");
+  LHN_CHECK_ARG(dst->H % src->H == 0 && dst->W % src->W == 0, "lhn_ew_bwd2: non-integer upsample");
+  LHN_CHECK_ARG((out_slope != LHN_SLOPE_SILU && out_slope != LHN_SLOPE_RELU_SIGMOID) || (dst->H == src->H && dst->W == src->W), "lhn_ew_bwd2: SiLU / ReLU-sigmoid need a single same-size source");
+  LHN_CHECK_ARG(src->C % 4 == 0 && src->C <= 1024, "lhn_ew_bwd2: C=%d", src->C);
+  if (bns_of(bns, src, &j->bs, "lhn_ew_bwd3")) return 1;
+  j->src = *src; j->dst = *dst;
+  j->ddst = ddst; j->dst_dpool = dst_dpool; j->dsrc = dsrc;
+  j->out_slope = out_slope; j->accumulate = accumulate;
+  return 0;
+}
 int lhn_ew_bwd2(const lhn_view* src, const lhn_view* dst, const float* ddst, const float* dst_dpool, float out_slope,
                 float* dsrc, int accumulate, void* stream) {
   return lhn_ew_bwd3(src, dst, ddst, dst_dpool, out_slope, dsrc, accumulate, nullptr, stream);
@@ -1838,26 +2054,38 @@ int lhn_ew_bwd2(const lhn_view* src, const lhn_view* dst, const float* ddst, con
 // variant used by the plan: dst may carry a channel-attention gate and its pooled-gradient (dpool)
 int lhn_ew_bwd3(const lhn_view* src, const lhn_view* dst, const float* ddst, const float* dst_dpool, float out_slope,
                 float* dsrc, int accumulate, const lhn_bnsum* bns, void* stream) {
-  LHN_CHECK_ARG(lhn_view_ok(src) && lhn_view_ok(dst) && ddst && dsrc && src->C == dst->C && lhn_no_pend(src) && lhn_no_pend(dst), "lhn_ew_bwd2: bad args");
-  LHN_CHECK_ARG(dst->H % src->H == 0 && dst->W % src->W == 0, "lhn_ew_bwd2: non-integer upsample");
-  LHN_CHECK_ARG((out_slope != LHN_SLOPE_SILU && out_slope != LHN_SLOPE_RELU_SIGMOID) || (dst->H == src->H && dst->W == src->W), "lhn_ew_bwd2: SiLU / ReLU-sigmoid need a single same-size source");
-  LHN_CHECK_ARG(src->C % 4 == 0 && src->C <= 1024, "lhn_ew_bwd2: C=%d", src->C);
-  lhn_bnsum bs;
-  if (bns_of(bns, src, &bs, "lhn_ew_bwd3")) return 1;
+  EwBwdSrcJob j;
+  if (ew_bwd_src_args(src, dst, ddst, dst_dpool, out_slope, dsrc, accumulate, bns, &j)) return 1;
   hipLaunchKernelGGL(k_ew_bwd_src, dim3(grid_cap((int64_t)src->N * src->H, 8)), dim3(256), 0, (hipStream_t)stream, *src, *dst, ddst,
-                     dst_dpool, out_slope, dsrc, accumulate, bs);
+                     dst_dpool, out_slope, dsrc, accumulate, j.bs);
   LHN_CHECK_LAUNCH("lhn_ew_bwd2");
+  return 0;
+}
+int lhn_ew_bwd_pair(const lhn_ew_job* a, const lhn_ew_job* b, void* stream) {
+  LHN_CHECK_ARG(a && b && a->nsrc == 1 && b->nsrc == 1 && a->dsrcs && b->dsrcs && a->accumulate && b->accumulate,
+                "lhn_ew_bwd_pair: two single-source jobs");
+  EwBwdSrcJob ja, jb;
+  if (ew_bwd_src_args(a->srcs, a->dst, a->ddst, a->dst_dpool, a->out_slope, a->dsrcs[0], a->accumulate[0], a->bns ? a->bns[0] : nullptr, &ja) ||
+      ew_bwd_src_args(b->srcs, b->dst, b->ddst, b->dst_dpool, b->out_slope, b->dsrcs[0], b->accumulate[0], b->bns ? b->bns[0] : nullptr, &jb))
+    return 1;
+  LHN_CHECK_ARG(a->out_slope != LHN_SLOPE_SILU && a->out_slope != LHN_SLOPE_RELU_SIGMOID && b->out_slope != LHN_SLOPE_SILU &&
+                    b->out_slope != LHN_SLOPE_RELU_SIGMOID,
+                "lhn_ew_bwd_pair: SiLU / ReLU-sigmoid take lhn_ew_bwd3");
+  LHN_CHECK_ARG(same_geometry(ja.src, jb.src) && same_geometry(ja.dst, jb.dst), "lhn_ew_bwd_pair: the two jobs differ in geometry");
+  LHN_CHECK_ARG(!grad_outputs_meet(ja.dsrc, ja.src, jb.dsrc, jb.src), "lhn_ew_bwd_pair: the two outputs overlap");
+  hipLaunchKernelGGL(k_ew_bwd_src_pair, dim3(grid_cap((int64_t)ja.src.N * ja.src.H, 8), 2), dim3(256), 0, (hipStream_t)stream, ja, jb);
+  LHN_CHECK_LAUNCH("lhn_ew_bwd_pair");
   return 0;
 }
 
 // up to three sources of dst's own resolution in one pass (see k_ew_bwd_multi)
-int lhn_ew_bwd_multi(const lhn_view* srcs, int nsrc, const lhn_view* dst, const float* ddst, const float* dst_dpool, float out_slope,
-                     float* const* dsrcs, const int* accumulate, const lhn_bnsum* const* bns, void* stream) {
+static int ew_bwd_multi_args(const lhn_view* srcs, int nsrc, const lhn_view* dst, const float* ddst, const float* dst_dpool, float out_slope,
+                             float* const* dsrcs, const int* accumulate, const lhn_bnsum* const* bns, EwBwdMultiJob* j) {
   LHN_CHECK_ARG(srcs && nsrc >= 1 && nsrc <= 3 && lhn_view_ok(dst) && ddst && dsrcs && accumulate && lhn_no_pend(dst), "lhn_ew_bwd_multi: bad args");
   LHN_CHECK_ARG(out_slope != LHN_SLOPE_SILU && out_slope != LHN_SLOPE_RELU_SIGMOID, "lhn_ew_bwd_multi: SiLU / ReLU-sigmoid take lhn_ew_bwd3");
   LHN_CHECK_ARG(dst->C % 4 == 0 && dst->C <= 1024, "lhn_ew_bwd_multi: C=%d", dst->C);
-  EwBwdMulti m;
-  memset(&m, 0, sizeof(m));
+  memset(j, 0, sizeof(*j));
+  EwBwdMulti& m = j->m;
   m.n = nsrc;
   for (int k = 0; k < nsrc; ++k) {
     const lhn_view* v = &srcs[k];
@@ -1868,18 +2096,57 @@ int lhn_ew_bwd_multi(const lhn_view* srcs, int nsrc, const lhn_view* dst, const 
     m.acc[k] = accumulate[k];
     if (bns_of(bns ? bns[k] : nullptr, v, &m.bs[k], "lhn_ew_bwd_multi")) return 1;
   }
-  hipLaunchKernelGGL(k_ew_bwd_multi, dim3(grid_cap((int64_t)dst->N * dst->H, 8)), dim3(256), 0, (hipStream_t)stream, m, *dst, ddst, dst_dpool, out_slope);
+  j->dst = *dst;
+  j->ddst = ddst; j->dst_dpool = dst_dpool;
+  j->out_slope = out_slope;
+  return 0;
+}
+int lhn_ew_bwd_multi(const lhn_view* srcs, int nsrc, const lhn_view* dst, const float* ddst, const float* dst_dpool, float out_slope,
+                     float* const* dsrcs, const int* accumulate, const lhn_bnsum* const* bns, void* stream) {
+  EwBwdMultiJob j;
+  if (ew_bwd_multi_args(srcs, nsrc, dst, ddst, dst_dpool, out_slope, dsrcs, accumulate, bns, &j)) return 1;
+  hipLaunchKernelGGL(k_ew_bwd_multi, dim3(grid_cap((int64_t)dst->N * dst->H, 8)), dim3(256), 0, (hipStream_t)stream, j.m, *dst, ddst, dst_dpool, out_slope);
   LHN_CHECK_LAUNCH("lhn_ew_bwd_multi");
   return 0;
 }
+int lhn_ew_bwd_multi_pair(const lhn_ew_job* a, const lhn_ew_job* b, void* stream) {
+  LHN_CHECK_ARG(a && b, "lhn_ew_bwd_multi_pair: two jobs");
+  EwBwdMultiJob ja, jb;
+  if (ew_bwd_multi_args(a->srcs, a->nsrc, a->dst, a->ddst, a->dst_dpool, a->out_slope, a->dsrcs, a->accumulate, a->bns, &ja) ||
+      ew_bwd_multi_args(b->srcs, b->nsrc, b->dst, b->ddst, b->dst_dpool, b->out_slope, b->dsrcs, b->accumulate, b->bns, &jb))
+    return 1;
+  LHN_CHECK_ARG(same_geometry(ja.dst, jb.dst) && ja.m.n == jb.m.n, "lhn_ew_bwd_multi_pair: the two jobs differ in geometry");
+  for (int k = 0; k < ja.m.n; ++k)
+    for (int l = 0; l < jb.m.n; ++l)
+      LHN_CHECK_ARG(!grad_outputs_meet(ja.m.dsrc[k], ja.m.src[k], jb.m.dsrc[l], jb.m.src[l]), "lhn_ew_bwd_multi_pair: outputs %d and %d of the two jobs overlap", k, l);
+  hipLaunchKernelGGL(k_ew_bwd_multi_pair, dim3(grid_cap((int64_t)ja.dst.N * ja.dst.H, 8), 2), dim3(256), 0, (hipStream_t)stream, ja, jb);
+  LHN_CHECK_LAUNCH("lhn_ew_bwd_multi_pair");
+  return 0;
+}
 
-int lhn_maxpool2_fwd(const lhn_view* x, const lhn_view* y, void* stream) {
+static int maxpool2_fwd_args(const lhn_view* x, const lhn_view* y, MaxpoolFwdJob* j) {
   LHN_CHECK_ARG(lhn_view_ok(x) && lhn_view_ok(y) && x->C == y->C, "lhn_maxpool2_fwd: bad views");
   LHN_CHECK_ARG(y->H == (x->H + 1) / 2 && y->W == (x->W + 1) / 2 && y->N == x->N, "lhn_maxpool2_fwd: geometry");
   LHN_CHECK_ARG(y->C % 4 == 0 && y->C <= 1024, "lhn_maxpool2_fwd: C=%d", y->C);
   LHN_CHECK_ARG(lhn_no_pend(x), "lhn_maxpool2_fwd: lhn_view.pend is reserved (NULL)");
+  j->x = *x; j->y = *y;
+  return 0;
+}
+int lhn_maxpool2_fwd(const lhn_view* x, const lhn_view* y, void* stream) {
+  MaxpoolFwdJob j;
+  if (maxpool2_fwd_args(x, y, &j)) return 1;
   hipLaunchKernelGGL(k_maxpool2_fwd, dim3(grid_cap((int64_t)y->N * y->H, 8)), dim3(256), 0, (hipStream_t)stream, *x, *y);
   LHN_CHECK_LAUNCH("lhn_maxpool2_fwd");
+  return 0;
+}
+int lhn_maxpool2_fwd_pair(const lhn_maxpool_job* a, const lhn_maxpool_job* b, void* stream) {
+  LHN_CHECK_ARG(a && b, "lhn_maxpool2_fwd_pair: two jobs");
+  MaxpoolFwdJob ja, jb;
+  if (maxpool2_fwd_args(a->x, a->y, &ja) || maxpool2_fwd_args(b->x, b->y, &jb)) return 1;
+  LHN_CHECK_ARG(same_geometry(ja.x, jb.x) && same_geometry(ja.y, jb.y), "lhn_maxpool2_fwd_pair: the two jobs differ in geometry");
+  LHN_CHECK_ARG(!view_outputs_meet(ja.y, jb.y), "lhn_maxpool2_fwd_pair: the two outputs overlap");
+  hipLaunchKernelGGL(k_maxpool2_fwd_pair, dim3(grid_cap((int64_t)ja.y.N * ja.y.H, 8), 2), dim3(256), 0, (hipStream_t)stream, ja, jb);
+  LHN_CHECK_LAUNCH("lhn_maxpool2_fwd_pair");
   return 0;
 }
 int lhn_maxpool2_bwd(const lhn_view* x, const lhn_view* y, const float* dy, float* dx, int dx_accumulate, void* stream) {
@@ -1889,15 +2156,15 @@ int lhn_maxpool2_bwd2(const lhn_view* x, const lhn_view* y, const float* dy, flo
                       void* stream) {
   return lhn_maxpool2_bwd3(x, y, dy, dx, dx_accumulate, bns, nullptr, stream);
 }
-int lhn_maxpool2_bwd3(const lhn_view* x, const lhn_view* y, const float* dy, float* dx, int dx_accumulate, const lhn_bnsum* bns,
-                      const lhn_grad_adds* adds, void* stream) {
+static int maxpool2_bwd_args(const lhn_view* x, const lhn_view* y, const float* dy, float* dx, int dx_accumulate, const lhn_bnsum* bns,
+                             const lhn_grad_adds* adds, MaxpoolBwdJob* j, bool* with_adds) {
   LHN_CHECK_ARG(lhn_view_ok(x) && lhn_view_ok(y) && dy && dx && x->C == y->C && lhn_no_pend(x), "lhn_maxpool2_bwd: bad args");
   LHN_CHECK_ARG(y->C % 4 == 0 && y->C <= 1024, "lhn_maxpool2_bwd: C=%d", y->C);
-  lhn_bnsum bs;
-  if (bns_of(bns, x, &bs, "lhn_maxpool2_bwd2")) return 1;
-  lhn_grad_adds ad;
+  if (bns_of(bns, x, &j->bs, "lhn_maxpool2_bwd2")) return 1;
+  lhn_grad_adds& ad = j->ad;
   memset(&ad, 0, sizeof(ad));
-  if (adds && (adds->same || adds->pooled)) {
+  *with_adds = adds && (adds->same || adds->pooled);
+  if (*with_adds) {
     ad = *adds;
     LHN_CHECK_ARG(x->H % 2 == 0 && x->W % 2 == 0 && y->H == x->H / 2 && y->W == x->W / 2, "lhn_maxpool2_bwd3: gradient addends need even H, W (%dx%d)", x->H, x->W);
     LHN_CHECK_ARG(!ad.same || (ad.same_cstride % 4 == 0 && ad.same_coff % 4 == 0 && ad.same_coff >= 0 && ad.same_coff + x->C <= ad.same_cstride),
@@ -1905,25 +2172,78 @@ int lhn_maxpool2_bwd3(const lhn_view* x, const lhn_view* y, const float* dy, flo
     LHN_CHECK_ARG(!ad.pooled || (ad.OH > 0 && ad.OW > 0 && ad.OH <= x->H && ad.OW <= x->W && ad.pooled_cstride % 4 == 0 && ad.pooled_coff % 4 == 0 &&
                                  ad.pooled_coff >= 0 && ad.pooled_coff + x->C <= ad.pooled_cstride),
                   "lhn_maxpool2_bwd3: pooled addend layout");
-    hipLaunchKernelGGL(k_maxpool2_bwd<true>, dim3(grid_cap((int64_t)y->N * y->H, 8)), dim3(256), 0, (hipStream_t)stream, *x, *y, dy, dx, dx_accumulate, bs, ad);
-  } else {
-    hipLaunchKernelGGL(k_maxpool2_bwd<false>, dim3(grid_cap((int64_t)y->N * y->H, 8)), dim3(256), 0, (hipStream_t)stream, *x, *y, dy, dx, dx_accumulate, bs, ad);
   }
+  j->x = *x; j->y = *y;
+  j->dy = dy; j->dx = dx;
+  j->accumulate = dx_accumulate;
+  return 0;
+}
+int lhn_maxpool2_bwd3(const lhn_view* x, const lhn_view* y, const float* dy, float* dx, int dx_accumulate, const lhn_bnsum* bns,
+                      const lhn_grad_adds* adds, void* stream) {
+  MaxpoolBwdJob j;
+  bool with_adds;
+  if (maxpool2_bwd_args(x, y, dy, dx, dx_accumulate, bns, adds, &j, &with_adds)) return 1;
+  if (with_adds)
+    hipLaunchKernelGGL(k_maxpool2_bwd<true>, dim3(grid_cap((int64_t)y->N * y->H, 8)), dim3(256), 0, (hipStream_t)stream, *x, *y, dy, dx, dx_accumulate, j.bs, j.ad);
+  else
+    hipLaunchKernelGGL(k_maxpool2_bwd<false>, dim3(grid_cap((int64_t)y->N * y->H, 8)), dim3(256), 0, (hipStream_t)stream, *x, *y, dy, dx, dx_accumulate, j.bs, j.ad);
   LHN_CHECK_LAUNCH("lhn_maxpool2_bwd");
+  return 0;
+}
+int lhn_maxpool2_bwd_pair(const lhn_maxpool_job* a, const lhn_maxpool_job* b, void* stream) {
+  LHN_CHECK_ARG(a && b, "lhn_maxpool2_bwd_pair: two jobs");
+  MaxpoolBwdJob ja, jb;
+  bool adds_a, adds_b;
+  if (maxpool2_bwd_args(a->x, a->y, a->dy, a->dx, a->dx_accumulate, a->bns, a->adds, &ja, &adds_a) ||
+      maxpool2_bwd_args(b->x, b->y, b->dy, b->dx, b->dx_accumulate, b->bns, b->adds, &jb, &adds_b))
+    return 1;
+  LHN_CHECK_ARG(same_geometry(ja.x, jb.x) && same_geometry(ja.y, jb.y), "lhn_maxpool2_bwd_pair: the two jobs differ in geometry");
+  LHN_CHECK_ARG(!grad_outputs_meet(ja.dx, ja.x, jb.dx, jb.x), "lhn_maxpool2_bwd_pair: the two outputs overlap");
+  const dim3 g(grid_cap((int64_t)ja.y.N * ja.y.H, 8), 2);
+  if (adds_a || adds_b) hipLaunchKernelGGL(k_maxpool2_bwd_pair<true>, g, dim3(256), 0, (hipStream_t)stream, ja, jb);
+  else hipLaunchKernelGGL(k_maxpool2_bwd_pair<false>, g, dim3(256), 0, (hipStream_t)stream, ja, jb);
+  LHN_CHECK_LAUNCH("lhn_maxpool2_bwd_pair");
   return 0;
 }
 
 int lhn_avgpool_fwd(const lhn_view* x, float* out, int OH, int OW, void* stream) {
   return lhn_avgpool_fwd2(x, out, OH, OW, x ? x->C : 0, 0, stream);
 }
-int lhn_avgpool_fwd2(const lhn_view* x, float* out, int OH, int OW, int out_cstride, int out_coff, void* stream) {
+static int avgpool_fwd_args(const lhn_view* x, float* out, int OH, int OW, int out_cstride, int out_coff, AvgpoolFwdJob* j, bool* small) {
   LHN_CHECK_ARG(lhn_view_ok(x) && out && OH > 0 && OW > 0 && out_coff >= 0 && out_coff % 4 == 0 && out_cstride % 4 == 0 &&
                     out_coff + x->C <= out_cstride,
                 "lhn_avgpool_fwd: bad args");
   LHN_CHECK_ARG(x->C % 4 == 0 && x->C <= 1024, "lhn_avgpool_fwd: C=%d", x->C);
   LHN_CHECK_ARG(lhn_no_pend(x), "lhn_avgpool_fwd: lhn_view.pend is reserved (NULL)");
   const int binmax = ((x->H + OH - 1) / OH + 1) * ((x->W + OW - 1) / OW + 1);
-  if (binmax <= 25) {          // bins of at most 4x4 (+1: adaptive bins may overlap by a pixel)
+  *small = binmax <= 25;       // bins of at most 4x4 (+1: adaptive bins may overlap by a pixel)
+  j->x = *x;
+  j->out = out;
+  j->ostride = out_cstride; j->ocoff = out_coff;
+  return 0;
+}
+int lhn_avgpool_fwd_pair(const lhn_avgpool_job* a, const lhn_avgpool_job* b, void* stream) {
+  LHN_CHECK_ARG(a && b, "lhn_avgpool_fwd_pair: two jobs");
+  LHN_CHECK_ARG(!a->pstat && !a->copy_src && !b->pstat && !b->copy_src, "lhn_avgpool_fwd_pair: the statistics / copy forms take lhn_avgpool_fwd4");
+  AvgpoolFwdJob ja, jb;
+  bool small_a, small_b;
+  if (avgpool_fwd_args(a->x, a->out, a->OH, a->OW, a->out_cstride, a->out_coff, &ja, &small_a) ||
+      avgpool_fwd_args(b->x, b->out, b->OH, b->OW, b->out_cstride, b->out_coff, &jb, &small_b))
+    return 1;
+  LHN_CHECK_ARG(same_geometry(ja.x, jb.x) && a->OH == b->OH && a->OW == b->OW, "lhn_avgpool_fwd_pair: the two jobs differ in geometry");
+  LHN_CHECK_ARG(!small_a && !small_b, "lhn_avgpool_fwd_pair: bins of at most 4x4 take lhn_avgpool_fwd2 (one thread per bin)");
+  const int64_t bins = (int64_t)ja.x.N * a->OH * a->OW;
+  LHN_CHECK_ARG(!views_meet(ja.out, bins, ja.ostride, ja.ocoff, ja.x.C, jb.out, bins, jb.ostride, jb.ocoff, jb.x.C),
+                "lhn_avgpool_fwd_pair: the two outputs overlap");
+  hipLaunchKernelGGL(k_avgpool_fwd_pair, dim3((unsigned)bins, 2), dim3(256), 0, (hipStream_t)stream, ja, jb, a->OH, a->OW);
+  LHN_CHECK_LAUNCH("lhn_avgpool_fwd_pair");
+  return 0;
+}
+int lhn_avgpool_fwd2(const lhn_view* x, float* out, int OH, int OW, int out_cstride, int out_coff, void* stream) {
+  AvgpoolFwdJob j;
+  bool small;
+  if (avgpool_fwd_args(x, out, OH, OW, out_cstride, out_coff, &j, &small)) return 1;
+  if (small) {
     const int64_t total = (int64_t)x->N * OH * OW * (x->C / 4);
     hipLaunchKernelGGL(k_avgpool_small, dim3(grid_cap((total + 255) / 256, 16)), dim3(256), 0, (hipStream_t)stream, *x, out, OH, OW, out_cstride, out_coff);
   } else

@@ -45,6 +45,7 @@ struct Plan {
   std::vector<lhn_op> fwd, bwd;
   std::vector<uint8_t> pw_dz_dead;     // per backward op: an NHWC PW_BWD whose dz no later op touches (pw_dz_dead_at)
   std::vector<uint8_t> fwd_fin;        // per forward op: a convolution + BatchNorm whose finalize the next op takes (fwd_fin_consumer_at)
+  std::vector<uint8_t> pair[2];        // per forward / backward op: 1 = first, 2 = second op of a pair launch (pair_at)
   std::vector<GraphEntry> graphs;     // LHN_GRAPH=1: replayed instead of ~150-400 individual launches
   uint64_t tick = 0;
   int graph_misses = 0;
@@ -242,6 +243,245 @@ static bool pw_dz_dead_at(const Plan* P, const std::vector<lhn_op>& ops, size_t 
   return true;
 }
 
+// Pair launches (LHN_PAIR_LAUNCH, default 1, read once; 0 = single launches, for A/B runs).  An ungated RepBasicUnit returns a two-part
+// tensor (left | depthwise(right), no copy), so every pool and combine over it stands in the op lists twice, once per half: adjacent,
+// equal in geometry, independent.  Such a pair runs as ONE launch of the family's *_pair entry (blockIdx.y = the job, each job with
+// the grid, replicas and arithmetic of its single launch: the same bits), the second op launches nothing.  The same for two
+// consecutive convolution + BatchNorm ops that both keep their separate finalize launch (the two depthwise branches of an MSRB round):
+// the first finalize has no reader before the second, waits, and runs as job 0 of lhn_bn_finalize_pair.  Decided here, once per plan,
+// for whole-plan runs (lhn_plan_pair); the op lists do not change.  Variant B: 15 pool / combine pairs + 4 finalize pairs, 228 -> 209
+// launches per step.
+static bool pair_launch() {
+  static int v = -1;
+  if (v < 0) {
+    const char* e = getenv("LHN_PAIR_LAUNCH");
+    v = (e && e[0] == '0') ? 0 : 1;
+  }
+  return v == 1;
+}
+// what an op reads or writes: `pix` pixels of channels [coff, coff + C) at pixel stride cs, from byte offset `base` of the workspace
+struct Region {
+  int64_t base, pix;
+  int cs, coff, C;
+};
+// the rule of pw_dz_dead_at: one base and pixel stride -> the channel ranges decide; another layout over the same bytes -> any overlap
+static bool regions_meet(const Region& a, const Region& b) {
+  if (a.base < 0 || b.base < 0) return false;
+  if (a.base == b.base && a.cs == b.cs) return a.coff < b.coff + b.C && b.coff < a.coff + a.C;
+  const int64_t alo = a.base + 4 * (int64_t)a.coff, ahi = a.base + 4 * ((a.pix - 1) * a.cs + a.coff + a.C);
+  const int64_t blo = b.base + 4 * (int64_t)b.coff, bhi = b.base + 4 * ((b.pix - 1) * b.cs + b.coff + b.C);
+  return alo < bhi && blo < ahi;
+}
+struct Access {
+  std::vector<Region> rd, wr;
+};
+// reads and writes of a pool / combine op as data or as gradient (tables, gates and pooled gradients have no writer among these ops;
+// BatchNorm-backward sums are only added to, atomically)
+static bool pair_access(const Plan* P, const lhn_op& o, Access* A) {
+  auto data = [&](int buf, int coff, int C) {
+    const lhn_buf& b = P->bufs[buf];
+    return Region{b.data_off, (int64_t)b.N * b.H * b.W, b.C, coff, C};
+  };
+  auto grad = [&](int buf, int coff, int C) {
+    const lhn_buf& b = P->bufs[buf];
+    return Region{b.grad_off, (int64_t)b.N * b.H * b.W, b.C, coff, C};
+  };
+  if (o.out_buf < 0 && o.kind != OP_AVGPOOL) return false;
+  switch (o.kind) {
+    case OP_MAXPOOL:
+      if (o.in_buf[0] < 0) return false;
+      A->rd.push_back(data(o.in_buf[0], o.in_coff[0], o.in_C[0]));
+      A->wr.push_back(data(o.out_buf, o.out_coff, o.out_C));
+      return true;
+    case OP_EW:
+      if (o.i[0] < 1 || o.i[0] > 3 || o.i[2] != 0) return false;                                   // product / bilinear: single
+      for (int k = 0; k < o.i[0]; ++k) {
+        if (o.in_buf[k] < 0) return false;
+        A->rd.push_back(data(o.in_buf[k], o.in_coff[k], o.in_C[k]));
+      }
+      A->wr.push_back(data(o.out_buf, o.out_coff, o.out_C));
+      return true;
+    case OP_AVGPOOL: {
+      if (o.in_buf[0] < 0 || o.ws[0] < 0 || o.ws[1] >= 0 || o.in_buf[1] >= 0) return false;          // STAT / COPY: single
+      const lhn_buf& b = P->bufs[o.in_buf[0]];
+      const int OH = o.i[0], OW = o.i[1];
+      if (OH < 1 || OW < 1 || ((b.H + OH - 1) / OH + 1) * ((b.W + OW - 1) / OW + 1) <= 25) return false;      // the small-bin kernel: single
+      A->rd.push_back(data(o.in_buf[0], o.in_coff[0], o.in_C[0]));
+      A->wr.push_back(Region{o.ws[0], (int64_t)b.N * OH * OW, o.i[3] > 0 ? o.i[3] : o.in_C[0], o.i[4], o.in_C[0]});
+      return true;
+    }
+    case OP_MAXPOOL_BWD: {
+      if (o.in_buf[0] < 0) return false;
+      const lhn_buf& xb = P->bufs[o.in_buf[0]];
+      A->rd.push_back(data(o.in_buf[0], o.in_coff[0], o.in_C[0]));
+      A->rd.push_back(grad(o.out_buf, o.out_coff, o.out_C));
+      if (o.ws[2] >= 0) A->rd.push_back(Region{o.ws[2], (int64_t)xb.N * xb.H * xb.W, o.i[1], o.i[2], o.in_C[0]});
+      if (o.ws[3] >= 0) A->rd.push_back(Region{o.ws[3], (int64_t)xb.N * (o.i[7] >> 16) * (o.i[7] & 0xffff), o.i[3], o.i[6], o.in_C[0]});
+      A->wr.push_back(grad(o.in_buf[0], o.in_coff[0], o.in_C[0]));
+      return true;
+    }
+    case OP_EW_BWD: {
+      if ((o.i[1] != 0 && o.i[1] != 3) || o.f[0] == LHN_SLOPE_SILU || o.f[0] == LHN_SLOPE_RELU_SIGMOID) return false;
+      A->rd.push_back(data(o.out_buf, o.out_coff, o.out_C));
+      A->rd.push_back(grad(o.out_buf, o.out_coff, o.out_C));
+      for (int k = 0; k < (o.i[1] == 3 ? 3 : 1) && o.in_buf[k] >= 0; ++k) {
+        A->rd.push_back(data(o.in_buf[k], o.in_coff[k], o.in_C[k]));
+        A->wr.push_back(grad(o.in_buf[k], o.in_coff[k], o.in_C[k]));
+      }
+      return !A->wr.empty();
+    }
+    default:
+      return false;
+  }
+}
+static bool same_shape(const Plan* P, int a, int b) {
+  if ((a < 0) != (b < 0)) return false;
+  if (a < 0) return true;
+  const lhn_buf &x = P->bufs[a], &y = P->bufs[b];
+  return x.N == y.N && x.H == y.H && x.W == y.W;
+}
+static bool conv_keeps_finalize_launch(const Plan* P, const std::vector<lhn_op>& ops, size_t oi) {
+  const lhn_op& o = ops[oi];
+  const bool conv = o.kind == OP_STEM || o.kind == OP_PW || o.kind == OP_DW || (o.kind == OP_KXK && o.i[1] != 1);
+  if (!conv || !conv_has_bn(o) || o.ws[0] < 0 || o.out_buf < 0 || P->bufs[o.out_buf].table_off < 0) return false;
+  if (o.kind == OP_PW && (o.i[1] || o.i[2] > 0)) return false;                                  // NCHW head, padded channel count
+  if ((o.kind == OP_PW || o.kind == OP_DW) && (int)o.f[3] > 1) return false;                    // a unit the reference evaluates twice
+  return !fuse_finalize() && !P->fwd_fin[oi];
+}
+// 0: ops oi and oi + 1 launch on their own; 1: a pool / combine pair; 2: a finalize pair (forward list only)
+static int pair_at(const Plan* P, const std::vector<lhn_op>& ops, size_t oi, bool forward) {
+  if (!pair_launch() || oi + 1 >= ops.size()) return 0;
+  const lhn_op &a = ops[oi], &b = ops[oi + 1];
+  if (forward && conv_keeps_finalize_launch(P, ops, oi) && conv_keeps_finalize_launch(P, ops, oi + 1)) {
+    for (int k = 0; k < 3; ++k)      // the second convolution reads nothing of the first one's output view (its table is not there yet)
+      if (b.in_buf[k] == a.out_buf && b.in_coff[k] < a.out_coff + a.out_C && a.out_coff < b.in_coff[k] + b.in_C[k]) return 0;
+    if (b.kind == OP_STEM) return 0;
+    // two separate BatchNorms: table slices, parameters, saved statistics
+    if (a.out_buf == b.out_buf && a.out_coff < b.out_coff + b.out_C && b.out_coff < a.out_coff + a.out_C) return 0;
+    for (int k = 2; k <= 6; ++k)
+      if (a.p[k] >= 0 && a.p[k] == b.p[k]) return 0;
+    if (a.ws[0] == b.ws[0] || (a.ws[1] >= 0 && a.ws[1] == b.ws[1])) return 0;
+    return 2;
+  }
+  if (a.kind != b.kind) return 0;
+  // the same mode bits and geometry
+  if (a.kind == OP_EW && (a.i[0] != b.i[0] || a.i[2] != b.i[2])) return 0;
+  if (a.kind == OP_EW_BWD && a.i[1] != b.i[1]) return 0;
+  if (a.kind == OP_AVGPOOL && (a.i[0] != b.i[0] || a.i[1] != b.i[1])) return 0;
+  if (a.out_C != b.out_C || !same_shape(P, a.out_buf, b.out_buf)) return 0;
+  for (int k = 0; k < 3; ++k)
+    if (!same_shape(P, a.in_buf[k], b.in_buf[k]) || (a.in_buf[k] >= 0 && a.in_C[k] != b.in_C[k])) return 0;
+  Access A, B;
+  if (!pair_access(P, a, &A) || !pair_access(P, b, &B)) return 0;
+  for (const Region& w : A.wr) {
+    for (const Region& q : B.wr)
+      if (regions_meet(w, q)) return 0;
+    for (const Region& q : B.rd)
+      if (regions_meet(w, q)) return 0;
+  }
+  for (const Region& w : B.wr)
+    for (const Region& q : A.rd)
+      if (regions_meet(w, q)) return 0;
+  return 1;
+}
+
+// arguments of one pool / combine op as its entry point takes them (single or as one job of a pair)
+struct MaxpoolArgs {
+  lhn_view x, y;
+  lhn_bnsum bs;
+  lhn_grad_adds ad;
+  lhn_maxpool_job job;
+};
+static void mk_maxpool(const Plan* P, void* ws, const lhn_op& o, bool backward, MaxpoolArgs* A) {
+  A->x = mkview(P, ws, o.in_buf[0], o.in_coff[0], o.in_C[0]);
+  A->y = mkview(P, ws, o.out_buf, o.out_coff, o.out_C);
+  memset(&A->job, 0, sizeof(A->job));
+  A->job.x = &A->x;
+  A->job.y = &A->y;
+  if (!backward) return;
+  A->bs = mkbns(ws, o.ws[0], o.ws[1], o.i[4], o.i[5]);
+  // ws[2] / i[1], i[2]: gradient of a plain sum that also reads x (base, pixel stride, first channel); ws[3] / i[3], i[6], i[7]:
+  // gradient of an adaptive average pool of x (base, pixel stride, first channel, OH << 16 | OW) -- lhn_grad_adds
+  lhn_grad_adds& ad = A->ad;
+  memset(&ad, 0, sizeof(ad));
+  if (o.ws[2] >= 0) {
+    ad.same = reinterpret_cast<const float*>(at(ws, o.ws[2]));
+    ad.same_cstride = o.i[1]; ad.same_coff = o.i[2];
+  }
+  if (o.ws[3] >= 0) {
+    ad.pooled = reinterpret_cast<const float*>(at(ws, o.ws[3]));
+    ad.pooled_cstride = o.i[3]; ad.pooled_coff = o.i[6];
+    ad.OH = o.i[7] >> 16; ad.OW = o.i[7] & 0xffff;
+  }
+  A->job.dy = reinterpret_cast<const float*>(at(ws, P->bufs[o.out_buf].grad_off));
+  A->job.dx = reinterpret_cast<float*>(at(ws, P->bufs[o.in_buf[0]].grad_off));
+  A->job.dx_accumulate = o.i[0];
+  A->job.bns = A->bs.sums ? &A->bs : nullptr;
+  A->job.adds = (ad.same || ad.pooled) ? &ad : nullptr;
+}
+struct EwArgs {
+  lhn_view srcs[3], d;
+  float coef[3];
+  float* dsrcs[3];
+  int acc[3];
+  lhn_bnsum bsv[3];
+  const lhn_bnsum* bsp[3];
+  lhn_ew_job job;
+};
+static void mk_ew_fwd(const Plan* P, void* ws, const lhn_op& o, EwArgs* A) {
+  for (int k = 0; k < o.i[0]; ++k) A->srcs[k] = mkview(P, ws, o.in_buf[k], o.in_coff[k], o.in_C[k]);
+  A->d = mkview(P, ws, o.out_buf, o.out_coff, o.out_C);
+  for (int k = 0; k < 3; ++k) A->coef[k] = o.f[4 + k];
+  memset(&A->job, 0, sizeof(A->job));
+  A->job.srcs = A->srcs;
+  A->job.nsrc = o.i[0];
+  A->job.coef = o.i[1] ? A->coef : nullptr;      // i[1]: coefficients given; i[2]: mode
+  A->job.dst = &A->d;
+  A->job.out_slope = o.f[0];
+  A->job.mode = o.i[2];
+}
+// the sum forms of EW_BWD.  i[1] == 0: one source, accumulate flag i[0], its producer's sums ws[0..1] / i[4..5].  i[1] == 3: 2 or 3 sources
+// of the destination's resolution in one pass: in_buf[0..2]; accumulate flags i[0], i[2], i[3]; their producers' sums ws[0..5],
+// (C, coff) in i[4..7] and f[4..5]
+static void mk_ew_bwd(const Plan* P, void* ws, const lhn_op& o, EwArgs* A) {
+  const lhn_buf& db = P->bufs[o.out_buf];
+  A->d = mkview(P, ws, o.out_buf, o.out_coff, o.out_C);
+  const bool multi = o.i[1] == 3;
+  A->acc[0] = o.i[0]; A->acc[1] = o.i[2]; A->acc[2] = o.i[3];
+  A->bsv[0] = mkbns(ws, o.ws[0], o.ws[1], o.i[4], o.i[5]);
+  A->bsv[1] = multi ? mkbns(ws, o.ws[2], o.ws[3], o.i[6], o.i[7]) : mkbns(ws, -1, -1, 0, 0);
+  A->bsv[2] = multi ? mkbns(ws, o.ws[4], o.ws[5], (int)o.f[4], (int)o.f[5]) : mkbns(ws, -1, -1, 0, 0);
+  int ns = 0;
+  for (; ns < (multi ? 3 : 1) && o.in_buf[ns] >= 0; ++ns) {
+    A->srcs[ns] = mkview(P, ws, o.in_buf[ns], o.in_coff[ns], o.in_C[ns]);
+    A->dsrcs[ns] = reinterpret_cast<float*>(at(ws, P->bufs[o.in_buf[ns]].grad_off));
+    A->bsp[ns] = A->bsv[ns].sums ? &A->bsv[ns] : nullptr;
+  }
+  memset(&A->job, 0, sizeof(A->job));
+  A->job.srcs = A->srcs;
+  A->job.nsrc = ns;
+  A->job.dst = &A->d;
+  A->job.out_slope = o.f[0];
+  A->job.ddst = reinterpret_cast<const float*>(at(ws, db.grad_off));
+  A->job.dst_dpool = reinterpret_cast<const float*>(at(ws, db.dpool_off));
+  A->job.dsrcs = A->dsrcs;
+  A->job.accumulate = A->acc;
+  A->job.bns = A->bsp;
+}
+struct AvgpoolArgs {
+  lhn_view x;
+  lhn_avgpool_job job;
+};
+static void mk_avgpool(const Plan* P, void* ws, const lhn_op& o, AvgpoolArgs* A) {      // the plain form (no statistics, no copy source)
+  A->x = mkview(P, ws, o.in_buf[0], o.in_coff[0], o.in_C[0], o.i[2] == 0);
+  memset(&A->job, 0, sizeof(A->job));
+  A->job.x = &A->x;
+  A->job.out = reinterpret_cast<float*>(at(ws, o.ws[0]));
+  A->job.OH = o.i[0]; A->job.OW = o.i[1];
+  A->job.out_cstride = o.i[3] > 0 ? o.i[3] : A->x.C;
+  A->job.out_coff = o.i[4];
+}
+
 // creal: channels the BatchNorm really has when the convolution's output view is padded to a multiple of 4 (f.C then is the
 // layout of the statistics); repeat: the reference evaluates some units twice per forward (lite_hrnet.py:192-197), which
 // moves their running statistics twice -- the table is the same both times.
@@ -279,7 +519,23 @@ void* lhn_plan_create(const lhn_buf* bufs, int nbufs, const lhn_op* fwd, int nfw
   for (size_t oi = 0; oi < p->fwd.size(); ++oi) p->fwd_fin[oi] = fwd_fin_consumer_at(p, p->fwd, oi) ? 1 : 0;
   p->pw_dz_dead.resize(p->bwd.size());
   for (size_t oi = 0; oi < p->bwd.size(); ++oi) p->pw_dz_dead[oi] = pw_dz_dead_at(p, p->bwd, oi) ? 1 : 0;
+  for (int phase = 0; phase < 2; ++phase) {      // left to right: an op belongs to one pair at most
+    const std::vector<lhn_op>& ops = phase == 0 ? p->fwd : p->bwd;
+    std::vector<uint8_t>& pr = p->pair[phase];
+    pr.assign(ops.size(), 0);
+    for (size_t oi = 0; oi + 1 < ops.size(); ++oi)
+      if (!pr[oi] && pair_at(p, ops, oi, phase == 0)) {
+        pr[oi] = 1;
+        pr[oi + 1] = 2;
+      }
+  }
   return p;
+}
+
+int lhn_plan_pair(void* plan, int phase, int index) {
+  const Plan* p = static_cast<const Plan*>(plan);
+  if (!p || phase < 0 || phase > 1 || index < 0 || (size_t)index >= p->pair[phase].size()) return -1;
+  return p->pair[phase][index];
 }
 
 int lhn_plan_head_gate_fold(void* plan) {
@@ -343,6 +599,28 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
     ffin_for = oi + 1;
     return true;
   };
+  // pair launches (pair_at): whole-plan runs only.  pr[oi] == 1: op oi launches for itself and op oi + 1; 2: launches nothing
+  const uint8_t* pr = whole ? P->pair[phase].data() : nullptr;
+  lhn_bnfin dfin;                       // the finalize of the convolution in front of op dfin_for, waiting for that op's
+  const double* dstats = nullptr;
+  size_t dfin_for = (size_t)-1;
+  auto finalize = [&](size_t oi, const lhn_bnfin& fin, const double* stats, int creal, int repeat) -> int {
+    if (pr && pr[oi] == 1) {
+      dfin = fin;
+      dstats = stats;
+      dfin_for = oi + 1;
+      return 0;
+    }
+    if (pr && pr[oi] == 2 && dfin_for == oi) {
+      lhn_bnfin fa = dfin, fb = fin;
+      if (!training) {      // as sep_finalize: the table from the running statistics, nothing else is touched
+        fa.num_batches_tracked = fb.num_batches_tracked = nullptr;
+        fa.save_mean_invstd = fb.save_mean_invstd = nullptr;
+      }
+      return lhn_bn_finalize_pair(training ? dstats : nullptr, &fa, fa.C, training ? stats : nullptr, &fb, fb.C, training, stream);
+    }
+    return sep_finalize(fin, stats, training, stream, creal, repeat);
+  };
   size_t gfold_at = (size_t)-1;         // the GATE_REDUCE op whose sums the head's backward in front of it added (head_gate_fold_at)
   for (size_t oi = 0; oi < ops.size() && rc == 0; ++oi) {
     const lhn_op& o = ops[oi];
@@ -387,7 +665,7 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
                                (training && o.ws[0] >= 0) ? reinterpret_cast<double*>(at(ws, o.ws[0])) : nullptr, o.i[3], o.i[4], o.i[0], o.i[1],
                                o.i[2], (bn && fz) ? &fin : nullptr, stream);
         if (!rc && bn && h1 && !skip_tables && !deferred && !fz && !hand_over(oi, fin, reinterpret_cast<const double*>(at(ws, o.ws[0]))))
-          rc = sep_finalize(fin, reinterpret_cast<const double*>(at(ws, o.ws[0])), training, stream);
+          rc = finalize(oi, fin, reinterpret_cast<const double*>(at(ws, o.ws[0])), 0, 1);
         break;
       }
       case OP_PW: {
@@ -441,7 +719,7 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
                               (training && o.ws[0] >= 0) ? reinterpret_cast<double*>(at(ws, o.ws[0])) : nullptr, o.i[0], nchw,
                               (bn && fz) ? &fin : nullptr, &po, ffin_for == oi ? &ffin : nullptr, stream);
         if (!rc && bn && h1 && !skip_tables && !deferred && !fz && !hand_over(oi, fin, reinterpret_cast<const double*>(at(ws, o.ws[0]))))
-          rc = sep_finalize(fin, reinterpret_cast<const double*>(at(ws, o.ws[0])), training, stream, o.i[2], (int)o.f[3]);
+          rc = finalize(oi, fin, reinterpret_cast<const double*>(at(ws, o.ws[0])), o.i[2], (int)o.f[3]);
         break;
       }
       case OP_DW: {
@@ -471,7 +749,7 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
                               (bn && fz) ? &fin : nullptr, o.i[6] > 1 ? &extra : nullptr, coef2,
                               so ? &sumv : nullptr, ffin_for == oi ? &ffin : nullptr, stream);
         if (!rc && bn && h1 && !skip_tables && !deferred && !fz && !hand_over(oi, fin, reinterpret_cast<const double*>(at(ws, o.ws[0]))))
-          rc = sep_finalize(fin, reinterpret_cast<const double*>(at(ws, o.ws[0])), training, stream, 0, (int)o.f[3]);
+          rc = finalize(oi, fin, reinterpret_cast<const double*>(at(ws, o.ws[0])), 0, (int)o.f[3]);
         break;
       }
       case OP_KXK: {
@@ -500,7 +778,7 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
                               (bn && fz) ? &fin : nullptr,
                               o.ws[3] >= 0 ? reinterpret_cast<float*>(at(ws, o.ws[3])) : nullptr, stream);
         if (!rc && bn && h1 && !skip_tables && !deferred && !fz && !hand_over(oi, fin, reinterpret_cast<const double*>(at(ws, o.ws[0]))))
-          rc = sep_finalize(fin, reinterpret_cast<const double*>(at(ws, o.ws[0])), training, stream);
+          rc = finalize(oi, fin, reinterpret_cast<const double*>(at(ws, o.ws[0])), 0, 1);
         break;
       }
       case OP_PWDW: {  // in: x, the intermediate buffer (only its table exists); p: w1, w2.  Inference plans only.
@@ -678,19 +956,25 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
         break;
       }
       case OP_EW: {
-        lhn_view srcs[3];
-        for (int k = 0; k < o.i[0]; ++k) {
-          srcs[k] = mkview(P, ws, o.in_buf[k], o.in_coff[k], o.in_C[k]);
-        }
-        lhn_view d = mkview(P, ws, o.out_buf, o.out_coff, o.out_C);
-        const float coef[3] = {o.f[4], o.f[5], o.f[6]};
-        rc = lhn_ew_fwd3(srcs, o.i[0], o.i[1] ? coef : nullptr, &d, o.f[0], o.i[2], stream);      // i[1]: coefficients given; i[2]: mode
+        if (pr && pr[oi] == 2) break;      // ran as job 1 of the op in front
+        EwArgs A, B;
+        mk_ew_fwd(P, ws, o, &A);
+        if (pr && pr[oi] == 1) {
+          mk_ew_fwd(P, ws, ops[oi + 1], &B);
+          rc = lhn_ew_fwd_pair(&A.job, &B.job, stream);
+        } else
+          rc = lhn_ew_fwd3(A.srcs, A.job.nsrc, A.job.coef, &A.d, A.job.out_slope, A.job.mode, stream);
         break;
       }
       case OP_MAXPOOL: {
-        lhn_view x = mkview(P, ws, o.in_buf[0], o.in_coff[0], o.in_C[0]);
-        lhn_view y = mkview(P, ws, o.out_buf, o.out_coff, o.out_C);
-        rc = lhn_maxpool2_fwd(&x, &y, stream);
+        if (pr && pr[oi] == 2) break;
+        MaxpoolArgs A, B;
+        mk_maxpool(P, ws, o, false, &A);
+        if (pr && pr[oi] == 1) {
+          mk_maxpool(P, ws, ops[oi + 1], false, &B);
+          rc = lhn_maxpool2_fwd_pair(&A.job, &B.job, stream);
+        } else
+          rc = lhn_maxpool2_fwd(&A.x, &A.y, stream);
         break;
       }
       case OP_SHUFFLE: {
@@ -701,6 +985,14 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
         break;
       }
       case OP_AVGPOOL: {
+        if (pr && pr[oi] == 2) break;
+        if (pr && pr[oi] == 1) {      // two plain pools (pair_at)
+          AvgpoolArgs A, B;
+          mk_avgpool(P, ws, o, &A);
+          mk_avgpool(P, ws, ops[oi + 1], &B);
+          rc = lhn_avgpool_fwd_pair(&A.job, &B.job, stream);
+          break;
+        }
         lhn_view x = mkview(P, ws, o.in_buf[0], o.in_coff[0], o.in_C[0], o.i[2] == 0);
         if (o.ws[1] >= 0 || o.in_buf[1] >= 0) {
           // channel attention: ws[1] = pooling statistics its backward assembles BatchNorm sums from (training plans);
@@ -866,6 +1158,14 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
         break;
       }
       case OP_EW_BWD: {
+        if (pr && pr[oi] == 2) break;
+        if (pr && pr[oi] == 1) {      // two sums of one form (pair_at)
+          EwArgs A, B;
+          mk_ew_bwd(P, ws, o, &A);
+          mk_ew_bwd(P, ws, ops[oi + 1], &B);
+          rc = o.i[1] == 3 ? lhn_ew_bwd_multi_pair(&A.job, &B.job, stream) : lhn_ew_bwd_pair(&A.job, &B.job, stream);
+          break;
+        }
         lhn_view src = mkview(P, ws, o.in_buf[0], o.in_coff[0], o.in_C[0]);
         lhn_view d = mkview(P, ws, o.out_buf, o.out_coff, o.out_C);
         const lhn_buf& db = P->bufs[o.out_buf];
@@ -901,25 +1201,14 @@ static int run_ops(const Plan* P, int phase, void* ws, void* const* params, void
         break;
       }
       case OP_MAXPOOL_BWD: {
-        lhn_view x = mkview(P, ws, o.in_buf[0], o.in_coff[0], o.in_C[0]);
-        lhn_view y = mkview(P, ws, o.out_buf, o.out_coff, o.out_C);
-        const lhn_bnsum bs = mkbns(ws, o.ws[0], o.ws[1], o.i[4], o.i[5]);
-        // ws[2] / i[1], i[2]: gradient of a plain sum that also reads x (base, pixel stride, first channel); ws[3] / i[3], i[6], i[7]:
-        // gradient of an adaptive average pool of x (base, pixel stride, first channel, OH << 16 | OW) -- lhn_grad_adds
-        lhn_grad_adds ad;
-        memset(&ad, 0, sizeof(ad));
-        if (o.ws[2] >= 0) {
-          ad.same = reinterpret_cast<const float*>(at(ws, o.ws[2]));
-          ad.same_cstride = o.i[1]; ad.same_coff = o.i[2];
-        }
-        if (o.ws[3] >= 0) {
-          ad.pooled = reinterpret_cast<const float*>(at(ws, o.ws[3]));
-          ad.pooled_cstride = o.i[3]; ad.pooled_coff = o.i[6];
-          ad.OH = o.i[7] >> 16; ad.OW = o.i[7] & 0xffff;
-        }
-        rc = lhn_maxpool2_bwd3(&x, &y, reinterpret_cast<const float*>(at(ws, P->bufs[o.out_buf].grad_off)),
-                               reinterpret_cast<float*>(at(ws, P->bufs[o.in_buf[0]].grad_off)), o.i[0], bs.sums ? &bs : nullptr,
-                               (ad.same || ad.pooled) ? &ad : nullptr, stream);
+        if (pr && pr[oi] == 2) break;
+        MaxpoolArgs A, B;
+        mk_maxpool(P, ws, o, true, &A);
+        if (pr && pr[oi] == 1) {
+          mk_maxpool(P, ws, ops[oi + 1], true, &B);
+          rc = lhn_maxpool2_bwd_pair(&A.job, &B.job, stream);
+        } else
+          rc = lhn_maxpool2_bwd3(&A.x, &A.y, A.job.dy, A.job.dx, A.job.dx_accumulate, A.job.bns, A.job.adds, stream);
         break;
       }
       case OP_AVGPOOL_BWD: {
