@@ -151,7 +151,8 @@ int         lhn_device_ok(void);              /* 0 if a gfx950 device is usable 
  * lhn_heatmap_encode    datasets/data_pipeline/generateTarget.py:74-159 (_msra_generate_target)
  * lhn_heatmap_argmax    utils/post_processing/evaluation/top_down_eval.py:199-231 (_get_max_preds)
  * lhn_heatmap_refine    .../top_down_eval.py:440-452 ('default' +-0.25 shift); mode 1 =
- *                       utils/heatmap_post_processing.py:6-33 / utils/HeatmapParser.py:197-223 twin
+ *                       utils/heatmap_post_processing.py:6-33 / utils/HeatmapParser.py:197-223 twin; a mode-1 coordinate
+ *                       outside the map (the (-1, -1) of a map without a positive maximum) reads nothing: both shifts -0.25
  * lhn_transform_preds   datasets/data_pipeline/post_transforms.py:6-48
  * lhn_heatmap_decode    .../top_down_eval.py:375-463 (keypoints_from_heatmaps, 'default'), fused
  * lhn_heatmap_nms       utils/HeatmapParser.py:41-50 (k x k max-pool peak keep)

@@ -45,16 +45,17 @@ __global__ void __launch_bounds__(256) k_encode(const float* __restrict__ joints
     }
   } else {
     const int mx = (int)((double)jx / stride_x + 0.5), my = (int)((double)jy / stride_y + 0.5);
-    const int ri = (int)r;
     const int ulx = (int)((double)mx - r), uly = (int)((double)my - r);
     const int brx = (int)((double)mx + r + 1), bry = (int)((double)my + r + 1);
     if (ulx >= W || uly >= H || brx < 0 || bry < 0) wgt = 0.f;
     const bool on = wgt > 0.5f;
     const float den = 2.f * sigma * sigma;
-    const int size = 2 * ri + 1, c0 = size / 2;
+    // generateTarget.py:139-142: size = 2 * r + 1 in floating point, centre size // 2 = floor(r + 0.5); with 3 * sigma not an
+    // integer (sigma = 1.5) that is one more than the centre of the integer patch 2 * (int)r + 1
+    const double c0 = floor(r + 0.5);
     // UDP (generateTarget.py:160-236, stride_* = (image-1)/(heatmap-1)): same patch, but the Gaussian is centred on the
     // sub-pixel position  size//2 + (joint/stride - mu)  and evaluated in float64 like the reference's mixed-type expression
-    const double x0 = (double)c0 + ((double)jx / stride_x - (double)mx), y0 = (double)c0 + ((double)jy / stride_y - (double)my);
+    const double x0 = c0 + ((double)jx / stride_x - (double)mx), y0 = c0 + ((double)jy / stride_y - (double)my);
     for (int i = threadIdx.x; i < HW; i += blockDim.x) {
       const int x = i % W, y = i / W;
       float v = 0.f;
@@ -136,9 +137,16 @@ __device__ __forceinline__ void refine_xy(const float* __restrict__ m, int H, in
       y = add_rn(y, sgn(dy) * 0.25f);
     }
   } else {
-    const int xr = min(px + 1, W - 1), xl = max(px - 1, 0), yd = min(py + 1, H - 1), yu = max(py - 1, 0);
-    x = add_rn(x, m[py * W + xr] > m[py * W + xl] ? 0.25f : -0.25f);
-    y = add_rn(y, m[yd * W + px] > m[yu * W + px] ? 0.25f : -0.25f);
+    // a coordinate outside the map ((-1, -1): _get_max_preds on a map without a positive maximum) loads nothing; the reference's
+    // wrap-around then compares an element with itself: both shifts -0.25
+    bool gx = false, gy = false;
+    if (px >= 0 && px < W && py >= 0 && py < H) {
+      const int xr = min(px + 1, W - 1), xl = max(px - 1, 0), yd = min(py + 1, H - 1), yu = max(py - 1, 0);
+      gx = m[py * W + xr] > m[py * W + xl];
+      gy = m[yd * W + px] > m[yu * W + px];
+    }
+    x = add_rn(x, gx ? 0.25f : -0.25f);
+    y = add_rn(y, gy ? 0.25f : -0.25f);
     x = add_rn(x, 0.5f);
     y = add_rn(y, 0.5f);
   }
@@ -377,6 +385,7 @@ int lhn_heatmap_argmax(const float* hm, float* preds, float* maxvals, int32_t* i
 int lhn_heatmap_refine(const float* hm, float* preds, int N, int K, int H, int W, int mode, void* stream) {
   LHN_CHECK_ARG(hm && preds, "lhn_heatmap_refine: null pointer");
   LHN_CHECK_ARG(mode == 0 || mode == 1, "lhn_heatmap_refine: mode %d", mode);
+  LHN_CHECK_ARG(N > 0 && K > 0 && H > 0 && W > 0, "lhn_heatmap_refine: bad shape N=%d K=%d H=%d W=%d", N, K, H, W);
   const int NK = N * K;
   hipLaunchKernelGGL(k_refine, dim3((NK + 255) / 256), dim3(256), 0, (hipStream_t)stream, hm, preds, NK, H, W, mode);
   LHN_CHECK_LAUNCH("lhn_heatmap_refine");
@@ -386,6 +395,7 @@ int lhn_heatmap_refine(const float* hm, float* preds, int N, int K, int H, int W
 int lhn_transform_preds(const float* coords, const float* center, const float* scale, float* out, int N, int K, int W,
                         int H, int use_udp, void* stream) {
   LHN_CHECK_ARG(coords && center && scale && out, "lhn_transform_preds: null pointer");
+  LHN_CHECK_ARG(N > 0 && K > 0 && H > 0 && W > 0, "lhn_transform_preds: bad shape N=%d K=%d H=%d W=%d", N, K, H, W);
   const int NK = N * K;
   hipLaunchKernelGGL(k_transform, dim3((NK + 255) / 256), dim3(256), 0, (hipStream_t)stream, coords, center, scale, out,
                      NK, K, W, H, use_udp);
@@ -397,6 +407,7 @@ int lhn_heatmap_decode(const float* hm, const float* center, const float* scale,
                        float* maxvals, int N, int K, int H, int W, int post_process, void* stream) {
   LHN_CHECK_ARG(hm && center && scale && hm_preds && preds && maxvals, "lhn_heatmap_decode: null pointer");
   LHN_CHECK_ARG(post_process == 0 || post_process == 1, "lhn_heatmap_decode: post_process %d (0 none, 1 default)", post_process);
+  LHN_CHECK_ARG(N > 0 && K > 0 && H > 0 && W > 0, "lhn_heatmap_decode: bad shape N=%d K=%d H=%d W=%d", N, K, H, W);
   LHN_CHECK_ARG((H * W) % 4 == 0, "lhn_heatmap_decode: H*W must be a multiple of 4");
   hipLaunchKernelGGL(k_decode, dim3(N * K), dim3(256), 0, (hipStream_t)stream, hm, center, scale, hm_preds, preds,
                      maxvals, (int32_t*)nullptr, K, H, W, post_process);
@@ -407,6 +418,7 @@ int lhn_heatmap_decode(const float* hm, const float* center, const float* scale,
 int lhn_heatmap_nms(float* hm, float* scratch, int N, int K, int H, int W, int kernel, void* stream) {
   LHN_CHECK_ARG(hm && scratch, "lhn_heatmap_nms: null pointer");
   LHN_CHECK_ARG(kernel % 2 == 1 && kernel > 0, "lhn_heatmap_nms: kernel must be odd");
+  LHN_CHECK_ARG(N > 0 && K > 0 && H > 0 && W > 0, "lhn_heatmap_nms: bad shape N=%d K=%d H=%d W=%d", N, K, H, W);
   hipLaunchKernelGGL(k_nms, dim3(N * K), dim3(256), 0, (hipStream_t)stream, hm, scratch, H, W, kernel);
   LHN_CHECK_LAUNCH("lhn_heatmap_nms");
   return 0;
@@ -416,6 +428,7 @@ int lhn_pck_accuracy(const float* pred, const float* gt, const uint8_t* mask, co
                      float* acc, float* avg_cnt, int N, int K, void* stream) {
   LHN_CHECK_ARG(pred && gt && mask && normalize && acc && avg_cnt, "lhn_pck_accuracy: null pointer");
   LHN_CHECK_ARG(K <= 1024, "lhn_pck_accuracy: K <= 1024");
+  LHN_CHECK_ARG(N > 0 && K > 0, "lhn_pck_accuracy: bad shape N=%d K=%d", N, K);
   hipLaunchKernelGGL(k_pck, dim3(1), dim3(256), 0, (hipStream_t)stream, pred, gt, mask, normalize, thr, acc, avg_cnt, N, K);
   LHN_CHECK_LAUNCH("lhn_pck_accuracy");
   return 0;
@@ -542,6 +555,7 @@ extern "C" int lhn_heatmap_decode_dark(const float* hm, const float* center, con
                                        float* maxvals, int N, int K, int H, int W, int kernel, void* stream) {
   LHN_CHECK_ARG(hm && center && scale && hm_preds && preds && maxvals, "lhn_heatmap_decode_dark: null pointer");
   LHN_CHECK_ARG(kernel % 2 == 1 && kernel >= 3 && kernel <= 31, "lhn_heatmap_decode_dark: kernel %d (odd, 3..31)", kernel);
+  LHN_CHECK_ARG(N > 0 && K > 0 && H > 0 && W > 0, "lhn_heatmap_decode_dark: bad shape N=%d K=%d H=%d W=%d", N, K, H, W);
   LHN_CHECK_ARG((H * W) % 4 == 0 && H * W <= 16384, "lhn_heatmap_decode_dark: H*W must be a multiple of 4 and <= 16384");
   const size_t lds = (size_t)2 * H * W * sizeof(float);
   static LhnKernelCfg cfg;
@@ -1014,6 +1028,7 @@ extern "C" int lhn_heatmap_decode_dark_udp(const float* hm, const float* center,
                                            float* maxvals, int N, int K, int H, int W, int kernel, void* stream) {
   LHN_CHECK_ARG(hm && center && scale && hm_preds && preds && maxvals, "lhn_heatmap_decode_dark_udp: null pointer");
   LHN_CHECK_ARG(kernel % 2 == 1 && kernel >= 3 && kernel <= 31, "lhn_heatmap_decode_dark_udp: kernel %d (odd, 3..31)", kernel);
+  LHN_CHECK_ARG(N > 0 && K > 0 && H > 0 && W > 0, "lhn_heatmap_decode_dark_udp: bad shape N=%d K=%d H=%d W=%d", N, K, H, W);
   LHN_CHECK_ARG((H * W) % 4 == 0 && H * W <= 16384 && H > 1 && W > 1, "lhn_heatmap_decode_dark_udp: H*W must be a multiple of 4 and <= 16384");
   const size_t lds = (size_t)2 * H * W * sizeof(float);
   static LhnKernelCfg cfg;

@@ -123,9 +123,10 @@ def opencv_gaussian_kernel1d(ksize):
     return (k / k.sum())
 
 
-def gaussian_blur(heatmaps, kernel=11):
-    """Separable blur of the zero-padded map then max re-normalisation (top_down_eval.py:233-272)."""
-    k1 = opencv_gaussian_kernel1d(kernel).astype(np.float32)
+def gaussian_blur(heatmaps, kernel=11, dtype=np.float32):
+    """Separable blur of the zero-padded map then max re-normalisation (top_down_eval.py:233-272).
+    dtype: the arithmetic's type (float64: the same steps without float32 rounding, to measure what float32 loses)."""
+    k1 = opencv_gaussian_kernel1d(kernel).astype(dtype)
     b = (kernel - 1) // 2
     out = np.empty_like(heatmaps)
     N, K, H, W = heatmaps.shape
@@ -133,7 +134,7 @@ def gaussian_blur(heatmaps, kernel=11):
         for j in range(K):
             src = heatmaps[n, j]
             omax = src.max()
-            pad = np.zeros((H + 2 * b, W + 2 * b), np.float32)
+            pad = np.zeros((H + 2 * b, W + 2 * b), dtype)
             pad[b:-b, b:-b] = src
             tmp = np.zeros_like(pad)
             for t in range(kernel):           # rows (x direction) first, zero border
@@ -166,13 +167,15 @@ def taylor(hm, coord):
     return coord
 
 
-def keypoints_from_heatmaps(heatmaps, center, scale, post_process="default", kernel=11):
-    """-> (hm_preds [N,K,2], preds [N,K,2] image coords, maxvals [N,K,1]); use_udp=False path."""
-    heatmaps = heatmaps.copy()
+def keypoints_from_heatmaps(heatmaps, center, scale, post_process="default", kernel=11, dtype=np.float32):
+    """-> (hm_preds [N,K,2], preds [N,K,2] image coords, maxvals [N,K,1]); use_udp=False path.
+    dtype=np.float64: float64 heat maps in, every step of the 'unbiased' branch and the back-transform in float64."""
+    heatmaps = heatmaps.astype(dtype)
     N, K, H, W = heatmaps.shape
     hm_preds, maxvals = get_max_preds(heatmaps)
+    hm_preds = hm_preds.astype(dtype)
     if post_process == "unbiased":
-        lg = np.log(np.maximum(gaussian_blur(heatmaps, kernel), 1e-10))
+        lg = np.log(np.maximum(gaussian_blur(heatmaps, kernel, dtype), 1e-10))
         for n in range(N):
             for k in range(K):
                 hm_preds[n, k] = taylor(lg[n, k], hm_preds[n, k])
@@ -286,9 +289,10 @@ def warp_matrix_udp(theta, size_input, size_dst, size_target):
 
 
 def warp_affine_normalize(img_u8, center, scale, rot, output_size, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225),
-                          use_udp=False):
+                          use_udp=False, return_pre=False):
     """TopDownAffine (topdown_affine.py:95-107) + ToTensor + NormalizeTensor for one HWC uint8 image, with exact bilinear
-    interpolation (cv2 interpolates with 5-bit fixed-point weights -- parity unpinned, cv2 absent) and uint8 rounding."""
+    interpolation (cv2 interpolates with 5-bit fixed-point weights -- parity unpinned, cv2 absent) and uint8 rounding.
+    return_pre: also the interpolated value before the uint8 rounding, float64 [H, W, 3] in levels."""
     M = affine_matrix(center, scale, rot, output_size)
     if use_udp:       # topdown_affine.py:76-93
         M = warp_matrix_udp(rot, np.asarray(center, np.float64) * 2.0, np.asarray(output_size, np.float64) - 1.0,
@@ -309,7 +313,8 @@ def warp_affine_normalize(img_u8, center, scale, rot, output_size, mean=(0.485, 
             wgt = (ax if i else 1 - ax) * (ay if j else 1 - ay)
             out += (wgt * ok)[..., None] * img_u8[np.clip(yy, 0, Hs - 1), np.clip(xx, 0, Ws - 1)].astype(np.float64)
     u8 = np.clip(np.rint(out), 0, 255)
-    return (((u8 / 255.0) - np.asarray(mean)) / np.asarray(std)).transpose(2, 0, 1).astype(np.float32), M
+    res = (((u8 / 255.0) - np.asarray(mean)) / np.asarray(std)).transpose(2, 0, 1).astype(np.float32)
+    return (res, M, out) if return_pre else (res, M)
 
 
 def udp_generate_target(joints_3d, joints_3d_visible, image_size, heatmap_size, sigma=2):
@@ -345,29 +350,29 @@ def udp_generate_target(joints_3d, joints_3d_visible, image_size, heatmap_size, 
     return target, weight
 
 
-def gaussian_blur_reflect(hm, k):
+def gaussian_blur_reflect(hm, k, dtype=np.float32):
     """cv2.GaussianBlur(hm, (k, k), 0) with its default BORDER_REFLECT_101, restated (cv2 absent: parity unpinned)."""
     k1 = opencv_gaussian_kernel1d(k)
     b = (k - 1) // 2
-    p = np.pad(hm.astype(np.float32), b, mode="reflect")
+    p = np.pad(hm.astype(dtype), b, mode="reflect")
     H, W = hm.shape
-    tmp = np.zeros((H + 2 * b, W), np.float32)
+    tmp = np.zeros((H + 2 * b, W), dtype)
     for t in range(k):
         tmp += k1[t] * p[:, t:t + W]
-    out = np.zeros((H, W), np.float32)
+    out = np.zeros((H, W), dtype)
     for t in range(k):
         out += k1[t] * tmp[t:t + H]
     return out
 
 
-def post_dark_udp(coords, batch_heatmaps, kernel=3):
-    """utils/post_processing/evaluation/top_down_eval.py:275-337."""
+def post_dark_udp(coords, batch_heatmaps, kernel=3, dtype=np.float32):
+    """utils/post_processing/evaluation/top_down_eval.py:275-337 (dtype: type of the blur and of the result)."""
     batch_heatmaps = batch_heatmaps.copy()
     B, K, H, W = batch_heatmaps.shape
     N = coords.shape[0]
     for b in range(B):
         for k in range(K):
-            batch_heatmaps[b, k] = gaussian_blur_reflect(batch_heatmaps[b, k], kernel)
+            batch_heatmaps[b, k] = gaussian_blur_reflect(batch_heatmaps[b, k], kernel, dtype)
     np.clip(batch_heatmaps, 0.001, 50, batch_heatmaps)
     np.log(batch_heatmaps, batch_heatmaps)
     pad = np.pad(batch_heatmaps, ((0, 0), (0, 0), (1, 1), (1, 1)), mode="edge").flatten()
@@ -384,15 +389,15 @@ def post_dark_udp(coords, batch_heatmaps, kernel=3):
     hessian = np.concatenate([dxx, dxy, dxy, dyy], axis=1).reshape(N, K, 2, 2)
     hessian = np.linalg.inv(hessian + np.finfo(np.float32).eps * np.eye(2))
     coords = coords - np.einsum("ijmn,ijnk->ijmk", hessian, derivative).squeeze()
-    return coords.astype(np.float32)
+    return coords.astype(dtype)
 
 
-def keypoints_from_heatmaps_udp(heatmaps, center, scale, kernel=11):
+def keypoints_from_heatmaps_udp(heatmaps, center, scale, kernel=11, dtype=np.float32):
     """keypoints_from_heatmaps(use_udp=True, target_type='GaussianHeatmap') (top_down_eval.py:404-411, 455-463)."""
-    heatmaps = heatmaps.copy()
+    heatmaps = heatmaps.astype(dtype)
     N, K, H, W = heatmaps.shape
     hm_preds, maxvals = get_max_preds(heatmaps)
-    hm_preds = post_dark_udp(hm_preds, heatmaps, kernel)
+    hm_preds = post_dark_udp(hm_preds, heatmaps, kernel, dtype)
     preds = hm_preds.copy()
     for i in range(N):
         preds[i] = transform_preds(preds[i], center[i], scale[i], [W, H], use_udp=True)
