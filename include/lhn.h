@@ -398,7 +398,12 @@ int lhn_msrb_round_fwd(const lhn_view x[2], const lhn_view* extra /*[2] or NULL*
 int lhn_conv_stem_fwd(const float* img /*[N,3,Hi,Wi]*/, const float* w /*[Cout,3,k,k]*/, const lhn_view* y,
                       double* stats, int Hi, int Wi, int k, int stride, int pad, const lhn_bnfin* fin, void* stream);
 /* wt_scratch: optional 9*Cout*Cin floats of caller-owned scratch; the call re-lays the OIHW weights tap-major into it
- * (16-byte weight loads per tap instead of 36-byte-strided gathers).  NULL = read the OIHW tensor directly. */
+ * (16-byte weight loads per tap instead of 36-byte-strided gathers).  NULL = read the OIHW tensor directly.
+ * Cin in {32, 64, 128, 256}; Cout in {32, 64, 128, 256} (1, 2, 4 or 8 tiles of 32 features; a Cout whose tile count is one of
+ * these may end in a partial tile, e.g. 40).  Cin = 256 runs as two 128-channel K slices per tap inside one launch, Cout = 256 as
+ * blocks of at most 128 features on gridDim.y; statistics and the fused finalize (`fin`) see the complete sums either way.  Any
+ * other channel count returns the invalid-argument status ("unsupported channels") before the first launch and writes nothing,
+ * the scratch included.  wt_scratch holds 9*Cout*Cin floats ([tap][Cout][Cin]; 589,824 floats = 2.25 MiB at 256 -> 256). */
 int lhn_conv_kxk_fwd(const lhn_view* x, const float* w /*[Cout,Cin,3,3]*/, const lhn_view* y, double* stats,
                      int stride, const lhn_bnfin* fin, float* wt_scratch, void* stream);
 /* Inference only: the stride-1 dense 3x3 of lhn_conv_kxk_fwd (liteHandNet.py:31,45: RepConv(.., 3, 1, 1) of BottleNeck / BasicBlock;
@@ -588,7 +593,12 @@ int lhn_conv_dw_bwd3(const lhn_view* x, const float* w, const lhn_view* y, const
 int lhn_conv_stem_bwd(const float* img, const lhn_view* y, const lhn_gradview* gy, float* dw, int Hi, int Wi,
                       int k, int stride, int pad, int nrep, int64_t rep_stride, void* stream);
 /* NOTE: lhn_conv_kxk_bwd and the large-channel path of lhn_conv_pw_bwd CONSUME gy->dz (it is overwritten in place
- * with dy before the MFMA kernels stream it). */
+ * with dy before the MFMA kernels stream it).
+ * lhn_conv_kxk_bwd: Cin, Cout in {32, 64, 128, 256} (3x3, pad 1, stride 1 or 2); anything else returns the invalid-argument status
+ * ("unsupported channels") before the first launch: dz, dx, dw and the scratch are left as they were.  256 channels run as two
+ * 128-channel slices: Cout = 256 inside the data-gradient kernel (dx is written once), Cin = 256 as one weight-gradient launch per
+ * input slice.  With a side of 256 dy is always formed in place first (LHN_PLAIN=0 does not apply).  wt_scratch: 9*Cout*Cin floats
+ * (589,824 at 256 -> 256), written [tap][Cin][Cout] by the call when dx != NULL, or NULL. */
 int lhn_conv_kxk_bwd(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
                      int dx_accumulate, float* dw, int stride, int nrep, int64_t rep_stride,
                      float* wt_scratch /*9*Cout*Cin floats or NULL, as above (dgrad layout)*/, void* stream);

@@ -61,13 +61,18 @@ static void launch_dy_inplace(const lhn_view* y, const lhn_gradview* gy, hipStre
 // flight into registers (raw loads; the pending BN/activation/gate or the dy formula is applied when they are
 // committed to LDS after the MFMA loop).  Weights of the next tap are fetched at the start of the commit; for
 // 1x1 (TAPS = 1) they are staged once per block.
+// KD = 256 does not fit LDS whole (the A tile alone would be 133 KB): it runs as NSL = 2 slices of KW = 128 channels, a phase is
+// then (tap, slice) -- 18 per tile -- on the LDS images and the MFMA loop of the <128, NT> instance, into the same accumulators.
+// The per-thread channel offset and the pending transform belong to a slice: issue() sets them for the phase it loads.
 template <int KD, int NT, int MODE, int TAPS, bool PLAIN = false>
 __global__ void __launch_bounds__(256) k_kxk(lhn_view x, const float* __restrict__ w, lhn_view y, lhn_gradview gy,
                                              double* __restrict__ stats, float* __restrict__ dx, int dx_acc, int stride,
                                              int nout, int Mhost, int ntiles, lhn_bnfin fin, const float* __restrict__ wt) {
-  constexpr int BM = 128, LDA = KD + 4;
-  constexpr int C4 = KD / 4, RP = 256 / C4, PF = BM / RP;     // float4 per thread per phase
-  constexpr int NW = 32 * NT * KD / 256;                      // weight scalars per thread per tap
+  constexpr int KW = KD > 128 ? 128 : KD, NSL = KD / KW;     // K slice held in LDS, slices per tap
+  static_assert(NSL == 1 || (TAPS == 9 && (MODE == 0 || PLAIN)), "sliced K: 3x3 forward and plain dgrad only");
+  constexpr int BM = 128, LDA = KW + 4;
+  constexpr int C4 = KW / 4, RP = 256 / C4, PF = BM / RP;     // float4 per thread per phase
+  constexpr int NW = 32 * NT * KW / 256;                      // weight scalars per thread per phase
   constexpr int WCH = NW > 16 ? 16 : NW;                      // staged in chunks of <= 16 registers
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* Ws = smem;                   // [32*NT][LDA]
@@ -92,8 +97,12 @@ __global__ void __launch_bounds__(256) k_kxk(lhn_view x, const float* __restrict
     return (ph ? 2 * a : 1) * 3 + (pw2 ? 2 * b : 1);
   };
   const int cin_total = MODE == 0 ? KD : nout;
-  const int cabs = av.coff + 4 * c4;
-  const Xf4 xf = lhn_load_xf(av, cabs);
+  const int cabs0 = av.coff + 4 * c4;
+  const Xf4 xf0 = lhn_load_xf(av, cabs0);
+  int cabs_s = cabs0;               // NSL > 1: offset and transform of the slice whose loads are in flight
+  Xf4 xf_s = xf0;
+  const int& cabs = NSL > 1 ? cabs_s : cabs0;
+  const Xf4& xf = NSL > 1 ? xf_s : xf0;
   Gr4 gr;
   if (MODE == 1) gr = lhn_load_coef(gy, y.cstride, cabs);
   double ssum[NT], ssq[NT];          // per-tile fp32 partials promoted to double (see k_conv_pw.hip)
@@ -119,8 +128,12 @@ __global__ void __launch_bounds__(256) k_kxk(lhn_view x, const float* __restrict
       rw[p] = par ? 2 * j2 + pw2 : j2;
     }
   };
-  auto issue = [&](int tap) __attribute__((always_inline)) {
+  auto issue = [&](int tap, int sl) __attribute__((always_inline)) {
     const int kh = TAPS == 1 ? 1 : tap / 3, kw = TAPS == 1 ? 1 : tap - (tap / 3) * 3;
+    if (NSL > 1) {       // the previous phase is committed: its offset and transform are dead
+      cabs_s = cabs0 + sl * KW;
+      if (MODE == 0) xf_s = lhn_load_xf(av, cabs_s);
+    }
     if (LIN) {
 #pragma unroll
       for (int p = 0; p < PF; ++p) {
@@ -156,24 +169,25 @@ __global__ void __launch_bounds__(256) k_kxk(lhn_view x, const float* __restrict
       }
     }
   };
-  auto stage_w = [&](int tap) __attribute__((always_inline)) {
+  auto stage_w = [&](int tap, int sl) __attribute__((always_inline)) {
     if (TAPS > 1 && wt) {
       // tap-major copy of the weights (k_w_tapmajor): row = output feature of this GEMM, KD contiguous floats per row ->
-      // 16-byte loads/stores instead of 4-byte gathers with a 36-byte stride (which cost more than the MFMAs of a phase)
-      constexpr int NWV = 32 * NT * KD / 4 / 256, K4 = KD / 4;
+      // 16-byte loads/stores instead of 4-byte gathers with a 36-byte stride (which cost more than the MFMAs of a phase).
+      // A slice takes KW of a row's KD floats, from sl * KW.
+      constexpr int NWV = 32 * NT * KW / 4 / 256, K4 = KW / 4;
       // NWV < 4 (32 * NT * KD < 4096): the fixed group of four below runs past the W image, and vector j >= NWV of thread tid
       // lands in As at exactly the slot that commit() writes for p = j - NWV of the SAME thread (both map the linear index
       // tid + 256 * j to (row, k4) the same way, and 32 * NT * K4 == 256 * NWV).  commit() always follows stage_w() before the
       // barrier, so the stray value is overwritten in program order by its own thread: in bounds (j - NWV < PF), no effect.
       // That holds only while the two mappings stay equal -- change either and this becomes an LDS write-write race
-      // between waves; bound the loop by NWV then.
+      // between waves; bound the loop by NWV then.  (The sliced instances have KW = 128: NWV >= 4, nothing runs past.)
 #pragma unroll
       for (int j0 = 0; j0 < NWV; j0 += 4) {
         f4 t[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int i = tid + 256 * (j0 + j), nn = i / K4, k4 = i - nn * K4;
-          t[j] = *reinterpret_cast<const f4*>(wt + ((size_t)tap * nout + min(n0 + nn, nout - 1)) * KD + 4 * k4);
+          t[j] = *reinterpret_cast<const f4*>(wt + ((size_t)tap * nout + min(n0 + nn, nout - 1)) * KD + sl * KW + 4 * k4);
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -191,8 +205,8 @@ __global__ void __launch_bounds__(256) k_kxk(lhn_view x, const float* __restrict
         const int i = tid + 256 * (j0 + j);
         float v = 0.f;
         if (MODE == 0 || TAPS > 1) {
-          const int nn = i / KD, kk = i - nn * KD;
-          if (n0 + nn < nout) v = MODE == 0 ? w[((size_t)(n0 + nn) * cin_total + kk) * TAPS + tap] : w[((size_t)kk * cin_total + n0 + nn) * TAPS + tap];
+          const int nn = i / KW, kk = i - nn * KW, ka = sl * KW + kk;
+          if (n0 + nn < nout) v = MODE == 0 ? w[((size_t)(n0 + nn) * cin_total + ka) * TAPS + tap] : w[((size_t)ka * cin_total + n0 + nn) * TAPS + tap];
         } else {   // 1x1 dgrad: W[co = k][ci = n], coalesced along n
           const int kk = i / (32 * NT), nn = i - kk * (32 * NT);
           if (n0 + nn < nout) v = w[(size_t)kk * cin_total + n0 + nn];
@@ -203,7 +217,7 @@ __global__ void __launch_bounds__(256) k_kxk(lhn_view x, const float* __restrict
       for (int j = 0; j < WCH; ++j) {
         const int i = tid + 256 * (j0 + j);
         if (MODE == 0 || TAPS > 1) {
-          const int nn = i / KD, kk = i - nn * KD;
+          const int nn = i / KW, kk = i - nn * KW;
           Ws[nn * LDA + kk] = t[j];
         } else {
           const int kk = i / (32 * NT), nn = i - kk * (32 * NT);
@@ -236,8 +250,8 @@ __global__ void __launch_bounds__(256) k_kxk(lhn_view x, const float* __restrict
   int tile = blockIdx.x;
   if (tile < ntiles) {
     geom(tile);
-    issue(tap_of(0));
-    stage_w(tap_of(0));
+    issue(tap_of(0), 0);
+    stage_w(tap_of(0), 0);
     commit(tap_of(0));
   }
   __syncthreads();
@@ -248,18 +262,20 @@ __global__ void __launch_bounds__(256) k_kxk(lhn_view x, const float* __restrict
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
     const int next_tile = tile + gridDim.x;
-    for (int ti = 0; ti < ntaps; ++ti) {
-      const bool more = (ti + 1 < ntaps) || (next_tile < ntiles);
-      const int ntap = tap_of(ti + 1 < ntaps ? ti + 1 : 0);
-      if (ti + 1 < ntaps) issue(ntap);
+    const int nph = ntaps * NSL;              // phases of a tile: (tap, K slice), slices innermost
+    for (int q = 0; q < nph; ++q) {
+      const bool more = (q + 1 < nph) || (next_tile < ntiles);
+      const int qn = q + 1 < nph ? q + 1 : 0;
+      const int ntap = tap_of(qn / NSL), nsl = NSL > 1 ? qn % NSL : 0;
+      if (q + 1 < nph) issue(ntap, nsl);
       else if (next_tile < ntiles) {
         geom(next_tile);
-        issue(ntap);
+        issue(ntap, nsl);
       }
       const float* arow = As + (wave * 32 + l31) * LDA + 4 * lh;
       const float* brow = Ws + l31 * LDA + 4 * lh;
 #pragma unroll 4
-      for (int kc = 0; kc < KD / 8; ++kc) {
+      for (int kc = 0; kc < KW / 8; ++kc) {
         const f4 a = *reinterpret_cast<const f4*>(arow + kc * 8);
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
@@ -272,7 +288,7 @@ __global__ void __launch_bounds__(256) k_kxk(lhn_view x, const float* __restrict
       }
       if (more) {
         __syncthreads();                 // every wave is done reading this phase's LDS images
-        if (TAPS > 1) stage_w(ntap);
+        if (TAPS > 1) stage_w(ntap, nsl);
         commit(ntap);
         __syncthreads();
       }
@@ -521,7 +537,8 @@ static int launch_kxk(const lhn_view* x, const float* w, const lhn_view* y, cons
   if (finp && stats) fin = *finp; else fin.counter = nullptr;
   const lhn_view* ov = MODE == 0 ? y : x;
   const int M = parity ? ov->N * ((ov->H + 1) / 2) * ((ov->W + 1) / 2) : ov->N * ov->H * ov->W, ntiles = (M + 127) / 128;
-  const size_t lds = (size_t)((32 * NT + 128) * (KD + 4) + 4 * 32 * NT * 2) * sizeof(float);
+  constexpr int KW = KD > 128 ? 128 : KD;       // the K slice that is resident in LDS
+  const size_t lds = (size_t)((32 * NT + 128) * (KW + 4) + 4 * 32 * NT * 2) * sizeof(float);
   static LhnKernelCfg cfg;
   int per_cu = 1;
   if (!lhn_kernel_cfg(cfg, &k_kxk<KD, NT, MODE, TAPS, PLAIN>, lds, 4, &per_cu)) {
@@ -538,7 +555,7 @@ static int launch_kxk(const lhn_view* x, const float* w, const lhn_view* y, cons
 
 template <int CIN, int NTO, int TAPS, bool PLAIN = false>
 static int launch_kxk_wgrad(const lhn_view* x, const lhn_view* y, const lhn_gradview* gy, float* dw, int stride, int nrep,
-                            int64_t rep_stride, hipStream_t s, int cosplit = 1, int wstride = CIN) {
+                            int64_t rep_stride, hipStream_t s, int cosplit = 1, int wstride = CIN, bool chunked = true) {
   const int M = y->N * y->H * y->W, ntiles = (M + 63) / 64;
   constexpr int COP = 32 * NTO;
   const size_t lds = (size_t)(64 * (COP + 4) + 64 * (CIN + 4)) * sizeof(float);
@@ -549,7 +566,8 @@ static int launch_kxk_wgrad(const lhn_view* x, const lhn_view* y, const lhn_grad
     return 2;
   }
   int grid = TAPS == 1 ? lhn_num_cus() * per_cu / cosplit : lhn_num_cus() / 4;      // x 9 taps
-  if (TAPS > 1 && cosplit > 1 && nrep > 1) grid = nrep;                   // exclusive replica slices: no atomics in the flush
+  // exclusive replica slices: no atomics in the flush (chunked = false: Cout = 256 is split over gridDim.z on long maps as well)
+  if (TAPS > 1 && cosplit > 1 && nrep > 1 && chunked) grid = nrep;
   if (grid < 1) grid = 1;
   if (grid > ntiles) grid = ntiles;
   hipLaunchKernelGGL((k_kxk_wgrad<CIN, NTO, TAPS, PLAIN>), dim3(grid, TAPS, cosplit), dim3(256), lds, s, *x, *y, *gy, dw, stride, y->C, M, ntiles, nrep,
@@ -563,21 +581,24 @@ static int kxk_geometry_ok(const lhn_view* x, const lhn_view* y, int stride) {
 
 // Small maps give few 128-pixel tiles (8x8 maps at batch 64: 32 tiles for 256 CUs): split the N = 32*nt output features
 // over gridDim.y so that about two workgroups per CU exist.  Returns the per-block tile count (1, 2 or 4 -> nt / splits).
+// nt = 8 (256 features) starts from two splits: a block holds at most four accumulator tiles.
 static int kxk_nt_block(int M, int nt) {
   const int ntiles = (M + 127) / 128;
-  int splits = 1;
+  int splits = nt > 4 ? nt / 4 : 1;
   while (splits < nt && nt % (splits * 2) == 0 && ntiles * splits < 2 * lhn_num_cus()) splits *= 2;
   return nt / splits;
 }
 
-// The instantiated (K, tiles-per-block) pairs of k_kxk / k_kxk_wgrad: K = 32, 64 or 128 channels exactly, 1, 2 or 4 tiles of 32.
-static bool kxk_instance_ok(int k, int nt) { return (k == 32 || k == 64 || k == 128) && (nt == 1 || nt == 2 || nt == 4); }
+// The instantiated (K, tiles-per-block) pairs of k_kxk / k_kxk_wgrad: K = 32, 64, 128 or 256 channels exactly, 1, 2 or 4 tiles
+// of 32.  K = 256 is two 128-channel slices: inside k_kxk, and one k_kxk_wgrad<128, ...> launch per slice.
+static bool kxk_instance_ok(int k, int nt) { return (k == 32 || k == 64 || k == 128 || k == 256) && (nt == 1 || nt == 2 || nt == 4); }
+static bool kxk_tiles_ok(int ntot) { return ntot == 1 || ntot == 2 || ntot == 4 || ntot == 8; }
 
 extern "C" int lhn_conv_kxk_fwd(const lhn_view* x, const float* w, const lhn_view* y, double* stats, int stride,
                                 const lhn_bnfin* fin, float* wt_scratch, void* stream) {
   LHN_CHECK_ARG(lhn_view_ok(x) && lhn_view_ok(y) && w && lhn_no_pend(x), "lhn_conv_kxk_fwd: bad view / null pointer (no pending BatchNorm here)");
   LHN_CHECK_ARG((stride == 1 || stride == 2) && kxk_geometry_ok(x, y, stride), "lhn_conv_kxk_fwd: geometry / stride %d", stride);
-  const int ntot = (y->C + 31) / 32, nt = (ntot == 1 || ntot == 2 || ntot == 4) ? kxk_nt_block(y->N * y->H * y->W, ntot) : ntot;
+  const int ntot = (y->C + 31) / 32, nt = kxk_tiles_ok(ntot) ? kxk_nt_block(y->N * y->H * y->W, ntot) : ntot;
   // decided BEFORE the first launch: a refused call writes nothing (not even the weight scratch)
   LHN_CHECK_ARG(kxk_instance_ok(x->C, nt), "lhn_conv_kxk_fwd: unsupported channels Cin=%d Cout=%d", x->C, y->C);
   hipStream_t s = (hipStream_t)stream;
@@ -585,6 +606,7 @@ extern "C" int lhn_conv_kxk_fwd(const lhn_view* x, const float* w, const lhn_vie
   if (wt_scratch) launch_w_tapmajor(w, wt_scratch, y->C, x->C, 0, s);
 #define KF(CI, NTV) if (x->C == CI && nt == NTV) rc = launch_kxk<CI, NTV, 0, 9>(x, w, y, nullptr, stats, nullptr, 0, stride, y->C, s, fin, ntot / nt, 0, wt_scratch);
   KF(32, 1) KF(64, 2) KF(128, 4) KF(32, 2) KF(64, 1) KF(64, 4) KF(128, 2) KF(128, 1) KF(32, 4)
+  KF(256, 4) KF(256, 2) KF(256, 1)
 #undef KF
   LHN_CHECK_ARG(rc != -1, "lhn_conv_kxk_fwd: unsupported channels Cin=%d Cout=%d", x->C, y->C);
   if (rc) return rc;
@@ -605,14 +627,18 @@ extern "C" int lhn_conv_kxk_bwd(const lhn_view* x, const float* w, const lhn_vie
   const int wtot = (y->C + 31) / 32, wtiles = (y->N * y->H * y->W + 63) / 64;
   // Cout >= 64: one 32-channel group per block (gridDim.z), pixel chunks = gradient replicas -> atomic-free flush
   // (only while a pixel chunk stays short: <= 16 tiles of 64 pixels per block; big maps amortise the atomic flush)
-  const int cosplit = (wtot == 2 || wtot == 4) && x->C >= 64 && nrep > 1 && wtiles <= 16 * nrep ? wtot : 1, nto = wtot / cosplit;
-  const int dtot = (x->C + 31) / 32, dnt = (dtot == 1 || dtot == 2 || dtot == 4) ? kxk_nt_block(x->N * x->H * x->W, dtot) : dtot;
+  // Cout = 256: eight groups the same way, or two groups of four tiles (a block holds at most four) with the atomic flush
+  const bool chunked = x->C >= 64 && nrep > 1 && wtiles <= 16 * nrep;
+  const int cosplit = wtot == 8 ? (chunked ? 8 : 2) : ((wtot == 2 || wtot == 4) && chunked ? wtot : 1), nto = wtot / cosplit;
+  const int dtot = (x->C + 31) / 32, dnt = kxk_tiles_ok(dtot) ? kxk_nt_block(x->N * x->H * x->W, dtot) : dtot;
   LHN_CHECK_ARG((!dx || kxk_instance_ok(y->C, dnt)) && kxk_instance_ok(x->C, nto), "lhn_conv_kxk_bwd: unsupported channels Cin=%d Cout=%d",
                 x->C, y->C);
   // large channel counts: turn dz into dy in place, then stream it plain (LHN_PLAIN=0/1 overrides the size rule).  A
   // channel-attention pooled gradient always takes this path: lhn_dy_fast has no pooled term.
+  // A side of 256 channels is always plain, whatever LHN_PLAIN says: the sliced dgrad has no dy-on-the-fly instance (a second
+  // set of y-transform and coefficient registers per slice), and by the size rule these cases are plain anyway.
   const char* pe = getenv("LHN_PLAIN");
-  const bool plain = gy->dpool || (pe ? (pe[0] == '1') : (x->C * y->C >= 64 * 64));
+  const bool plain = gy->dpool || x->C > 128 || y->C > 128 || (pe ? (pe[0] == '1') : (x->C * y->C >= 64 * 64));
   if (plain) launch_dy_inplace(y, gy, s);
   if (dx) {
     // GEMM N = Cin, K = Cout
@@ -622,15 +648,27 @@ extern "C" int lhn_conv_kxk_bwd(const lhn_view* x, const float* w, const lhn_vie
 #define KB(CO, NTV) if (y->C == CO && nt == NTV) rc = plain ? launch_kxk<CO, NTV, 1, 9, true>(x, w, y, gy, nullptr, dx, dx_accumulate, stride, x->C, s, nullptr, ntot / nt, par, wt_scratch) : launch_kxk<CO, NTV, 1, 9, false>(x, w, y, gy, nullptr, dx, dx_accumulate, stride, x->C, s, nullptr, ntot / nt, par, wt_scratch);
     KB(32, 1) KB(64, 2) KB(128, 4) KB(32, 2) KB(64, 1) KB(64, 4) KB(128, 2) KB(128, 1) KB(32, 4)
 #undef KB
+    // K = Cout = 256 in two slices inside the kernel (dx written once); plain only
+#define KB(NTV) if (y->C == 256 && nt == NTV) rc = launch_kxk<256, NTV, 1, 9, true>(x, w, y, gy, nullptr, dx, dx_accumulate, stride, x->C, s, nullptr, ntot / nt, par, wt_scratch);
+    KB(4) KB(2) KB(1)
+#undef KB
     LHN_CHECK_ARG(rc != -1, "lhn_conv_kxk_bwd: unsupported channels Cin=%d Cout=%d", x->C, y->C);      // (kxk_instance_ok lists them all)
     if (rc) return rc;
   }
-  rc = -1;
-#define KW(CI, NTV) if (x->C == CI && nto == NTV) rc = plain ? launch_kxk_wgrad<CI, NTV, 9, true>(x, y, gy, dw, stride, nrep, rep_stride, s, cosplit) : launch_kxk_wgrad<CI, NTV, 9, false>(x, y, gy, dw, stride, nrep, rep_stride, s, cosplit);
-  KW(32, 1) KW(64, 2) KW(128, 4) KW(32, 2) KW(64, 1) KW(64, 4) KW(128, 2) KW(128, 1) KW(32, 4)
+  // Cin = 256: once per 128-channel input slice (disjoint columns of dW: row length wstride = Cin, the slice starts 9 * k0 in)
+  const int kslice = x->C > 128 ? 128 : x->C;
+  for (int k0 = 0; k0 < x->C; k0 += kslice) {
+    lhn_view xv = *x;
+    xv.coff += k0;
+    xv.C = kslice;
+    float* dwk = dw + (size_t)9 * k0;
+    rc = -1;
+#define KW(CI, NTV) if (kslice == CI && nto == NTV) rc = plain ? launch_kxk_wgrad<CI, NTV, 9, true>(&xv, y, gy, dwk, stride, nrep, rep_stride, s, cosplit, x->C, chunked) : launch_kxk_wgrad<CI, NTV, 9, false>(&xv, y, gy, dwk, stride, nrep, rep_stride, s, cosplit, x->C, chunked);
+    KW(32, 1) KW(64, 2) KW(128, 4) KW(32, 2) KW(64, 1) KW(64, 4) KW(128, 2) KW(128, 1) KW(32, 4)
 #undef KW
-  LHN_CHECK_ARG(rc != -1, "lhn_conv_kxk_bwd: unsupported channels Cin=%d Cout=%d", x->C, y->C);
-  if (rc) return rc;
+    LHN_CHECK_ARG(rc != -1, "lhn_conv_kxk_bwd: unsupported channels Cin=%d Cout=%d", x->C, y->C);
+    if (rc) return rc;
+  }
   LHN_CHECK_LAUNCH("lhn_conv_kxk_bwd");
   return 0;
 }

@@ -1,7 +1,8 @@
 """The BottleNecks of a variant-A forward at width 256, timed on their own: the network of tests/test_infer_fuse_bneck256_gpu.py
 (Hourglass256: the model's thirteen 256-channel BottleNecks on the maps the model gives them, joined by max pools, nearest upsampling
 and residual sums) on a [bs, 256, 64, 64] input -- at a 256 x 256 image that is one block on the 64 x 64 map, two at 32 x 32, four at
-16 x 16 and six at 8 x 8.  Variant A itself cannot be timed at this width: its Residuals' 256 -> 256 dense 3x3 has no kernel.
+16 x 16 and six at 8 x 8.  (Written when variant A could not run at this width; `scripts/bench_infer.py A 64 off|bneck|full 2 256` now
+times the model itself, this script the BottleNecks without the rest.)
 python scripts/bench_bottleneck256.py [bs] [off|bneck|bf16x3|bneck+bf16x3] [reduction]
 LHN_BENCH_BNECK_CHANNELS="256:64" restricts the pass to those (C, Cm) classes, as in scripts/bench_infer.py.  Events on the launch
 stream, 20 forwards after 5, tables current; the time includes the engine's NCHW <-> NHWC copies of the 268 MB input and output, the

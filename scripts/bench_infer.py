@@ -10,9 +10,9 @@ python scripts/bench_infer.py [A|B|M|H|L] [bs] [every|off|on|dwpw|both|msrb|all|
   bneck and full where the BottleNeck pass finds blocks, bf16x3 and full+bf16x3 (the 3x3 pass alone / on top of the four fusion passes)
   where the model has eligible 3x3 convolutions, stem and full+stem (the stem pass alone / on top of the four fusion passes; `full` keeps
   its meaning) where the stem pass finds its pattern (A, M).  A model without a deployed form (H) runs its eval form only.  reduction: the `reduction` of variant A's Residual blocks (config default 4).
-  channels: the model width (`input_channel`, config default 128; the reference's width-256 configs run 256).  Variant B runs at 256; variant A
-  does not (its Residuals' 256 -> 256 dense 3x3 has no kernel: lhn_conv_kxk_fwd refuses it) -- scripts/bench_bottleneck256.py times A's BottleNecks at
-  that width on their own.  bneck+bf16x3 (only when asked for): the BottleNeck pass and the 3x3 pass together -- the inner 3x3s belong to the
+  channels: the model width (`input_channel`, config default 128; the reference's width-256 configs run 256).  Every variant runs at 256: the
+  256 -> 256 dense 3x3 of variant A's / mynet's Residuals is lhn_conv_kxk_fwd's K-sliced instance (`A 64 off|bneck|full 2 256` is the
+  width-256 model itself; scripts/bench_bottleneck256.py times its BottleNecks on their own).  bneck+bf16x3 (only when asked for): the BottleNeck pass and the 3x3 pass together -- the inner 3x3s belong to the
   BottleNeck launches and stay fp32.  LHN_BENCH_BNECK_CHANNELS="128:32,128:64" restricts the BottleNeck pass to those (C, Cm) classes.
 Launches: kernel launches of one steady-state forward (tables current), and the table-only launches a first forward adds."""
 import os, sys, time
