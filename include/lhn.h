@@ -597,11 +597,35 @@ int lhn_conv_stem_bwd(const float* img, const lhn_view* y, const lhn_gradview* g
  * lhn_conv_kxk_bwd: Cin, Cout in {32, 64, 128, 256} (3x3, pad 1, stride 1 or 2); anything else returns the invalid-argument status
  * ("unsupported channels") before the first launch: dz, dx, dw and the scratch are left as they were.  256 channels run as two
  * 128-channel slices: Cout = 256 inside the data-gradient kernel (dx is written once), Cin = 256 as one weight-gradient launch per
- * input slice.  With a side of 256 dy is always formed in place first (LHN_PLAIN=0 does not apply).  wt_scratch: 9*Cout*Cin floats
- * (589,824 at 256 -> 256), written [tap][Cin][Cout] by the call when dx != NULL, or NULL. */
+ * input slice.  wt_scratch: 9*Cout*Cin floats (589,824 at 256 -> 256), written [tap][Cin][Cout] by the call when dx != NULL, or NULL.
+ * dz is consumed ("plain": k_dy_inplace in front) with a pooled gradient, with a side of 256, and otherwise when Cin * Cout >= 4096.
+ * LHN_PLAIN=0 / 1 replaces that last size rule alone (never / always; it does not apply to a pooled gradient or a side of 256).  The
+ * variable is read once, at the first dense 3x3 call or query of the process: set it before the process starts.
+ * Which kernels a call launches is kxk_fwd_route / kxk_bwd_route's decision (csrc/k_conv_kxk.hip); lhn_conv_kxk_route below asks them. */
 int lhn_conv_kxk_bwd(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
                      int dx_accumulate, float* dw, int stride, int nrep, int64_t rep_stride,
                      float* wt_scratch /*9*Cout*Cin floats or NULL, as above (dgrad layout)*/, void* stream);
+/* Which kernels lhn_conv_kxk_fwd (backward = 0) / lhn_conv_kxk_bwd (backward = 1) launch for this shape, in order: host-only (no device
+ * needed, nothing is launched), answered by the two functions the calls themselves ask.  N, H, W are x's; nrep as passed to the
+ * backward call.  features: what the call carries.  cus: the compute units grids are sized for, <= 0 = what the library uses (the
+ * device's; 2 under LHN_DETERMINISTIC=1; 256 without a device).  switches: -1 = as this process read LHN_PLAIN, else 0 or one of
+ * LHN_KXK_SW_*.  Returns a static string (per thread, valid until the next call): the launches as a kernel trace prints them, joined
+ * with " + ", each followed by the decisions its template arguments do not show --
+ *   " yN"    N blocks of features on gridDim.y (forward: Cout, data gradient: Cin), where N > 1
+ *   " par"   stride-2 data gradient: the four pixel-parity classes on gridDim.z
+ *   " zN"    weight gradient: N groups of output channels on gridDim.z ("cosplit"), where N > 1
+ *   " excl" / " atomic"   weight gradient: every block owns its slice of a gradient replica (read-add-write flush), or atomics
+ *   " x 2"   weight gradient: one launch per 128-channel input slice (Cin = 256)
+ * e.g. "k_dy_inplace + k_w_tapmajor + k_kxk<128, 1, 1, 9, true> y4 + k_kxk_wgrad<128, 1, 9, true> z4 excl"; profiles/kxk_instances.md is
+ * printed from it.  NULL: no kernel instance (the call is refused with "unsupported channels" before any launch), or a stride other
+ * than 1 or 2.  Arguments a call would refuse for another reason are not checked. */
+#define LHN_KXK_F_DX    1   /* backward: dx != NULL */
+#define LHN_KXK_F_DPOOL 2   /* backward: gy->dpool != NULL */
+#define LHN_KXK_F_WT    4   /* wt_scratch != NULL: k_w_tapmajor re-lays the weights (backward: only ahead of a data gradient) */
+#define LHN_KXK_SW_PLAIN0 1 /* LHN_PLAIN is set and does not start with '1' */
+#define LHN_KXK_SW_PLAIN1 2 /* LHN_PLAIN=1 */
+const char* lhn_conv_kxk_route(int backward, int N, int H, int W, int Cin, int Cout, int stride, int nrep, int features, int cus,
+                               int switches);
 /* out[i] = sum_r part[r*rep_stride + i]  (folds the replicated weight-gradient partials into the flat gradient) */
 /* SyncBatchNorm (train/spawn_dist.py:37-38): run half-steps [step_begin, step_end) of a phase -- step 2*i = main
  * launches of op i, step 2*i+1 = the consumer of its statistics.  The caller all-reduces (SUM) the op's statistics

@@ -54,7 +54,7 @@ SYMBOLS = [
     "lhn_loss_balanced_mse_fwd", "lhn_loss_balanced_mse_bwd", "lhn_affine_warp_normalize", "lhn_affine_warp_normalize2", "lhn_random_flip", "lhn_hsv_jitter", "lhn_simdr_encode", "lhn_simdr_loss_fwd", "lhn_simdr_loss_bwd",
     "lhn_conv_pw_fwd", "lhn_conv_pw_fwd2", "lhn_conv_pw_bwd2", "lhn_conv_dw_fwd", "lhn_conv_dw_fwd2", "lhn_conv_dw_fwd3", "lhn_conv_pw_dw3_fwd", "lhn_conv_dw3_pw_fwd", "lhn_msrb_round_scratch_bytes", "lhn_msrb_round_fwd", "lhn_bottleneck_fwd", "lhn_stem_tail_fwd", "lhn_conv_stem_fwd", "lhn_conv_kxk_fwd", "lhn_conv_kxk_fwd_bf16x3",
     "lhn_bn_finalize", "lhn_table_fill", "lhn_table_bias", "lhn_fold_bn", "lhn_ew_fwd", "lhn_ew_fwd2", "lhn_ew_fwd3", "lhn_ew_mul_bwd", "lhn_bilinear_bwd", "lhn_shuffle2_fwd", "lhn_shuffle2_bwd", "lhn_bn_finalize2", "lhn_bn_bwd_finalize2", "lhn_maxpool2_fwd", "lhn_avgpool_fwd", "lhn_avgpool_fwd2", "lhn_avgpool_bwd2", "lhn_se_mlp_fwd2", "lhn_se_mlp_bwd2", "lhn_ca_mlp_fwd", "lhn_att_mlp_fwd", "lhn_att_mlp_bwd", "lhn_se_mlp_fwd", "lhn_se_mlp_bwd",
-    "lhn_bn_bwd_reduce", "lhn_bn_bwd_finalize", "lhn_conv_pw_bwd", "lhn_conv_dw_bwd", "lhn_conv_dw_bwd2", "lhn_conv_dw_bwd3", "lhn_conv_dw_bwd4", "lhn_conv_dw_route", "lhn_conv_pw_route", "lhn_conv_pw_bwd4", "lhn_conv_pw_bwd5", "lhn_conv_pw_bwd6", "lhn_plan_head_gate_fold", "lhn_plan_pw_dz_dead", "lhn_plan_fwd_fin_consumer", "lhn_conv_dw_fwd4", "lhn_conv_pw_fwd3", "lhn_conv_stem_bwd",
+    "lhn_bn_bwd_reduce", "lhn_bn_bwd_finalize", "lhn_conv_pw_bwd", "lhn_conv_dw_bwd", "lhn_conv_dw_bwd2", "lhn_conv_dw_bwd3", "lhn_conv_dw_bwd4", "lhn_conv_dw_route", "lhn_conv_pw_route", "lhn_conv_kxk_route", "lhn_conv_pw_bwd4", "lhn_conv_pw_bwd5", "lhn_conv_pw_bwd6", "lhn_plan_head_gate_fold", "lhn_plan_pw_dz_dead", "lhn_plan_fwd_fin_consumer", "lhn_conv_dw_fwd4", "lhn_conv_pw_fwd3", "lhn_conv_stem_bwd",
     "lhn_conv_kxk_bwd", "lhn_ew_bwd", "lhn_ew_bwd2", "lhn_maxpool2_bwd", "lhn_maxpool2_bwd2", "lhn_maxpool2_bwd3", "lhn_ew_bwd3", "lhn_ew_bwd_multi", "lhn_avgpool_bwd3", "lhn_conv_pw_bwd3", "lhn_avgpool_bwd", "lhn_gate_bwd_reduce", "lhn_gate_bwd_reduce2", "lhn_gate_bwd_reduce3", "lhn_adam_step", "lhn_avgpool_fwd3", "lhn_avgpool_fwd4", "lhn_ca_mlp_bwd2",
     "lhn_ca_mlp_bwd", "lhn_reduce_replicas", "lhn_fold_stat_replicas", "lhn_plan_create", "lhn_plan_destroy", "lhn_plan_run", "lhn_plan_run_range",
     "lhn_cbam_layout", "lhn_cbam_fwd", "lhn_cbam_bwd",
@@ -82,6 +82,9 @@ def lib():
         # (backward, N, H, W, Cin, Cout, stride, w_rows, w_cols, features, switches) -> the launches in order or NULL; host only
         _lib.lhn_conv_pw_route.argtypes = [C.c_int] * 11
         _lib.lhn_conv_pw_route.restype = C.c_char_p
+        # (backward, N, H, W, Cin, Cout, stride, nrep, features, cus, switches) -> the launches in order or NULL; host only
+        _lib.lhn_conv_kxk_route.argtypes = [C.c_int] * 11
+        _lib.lhn_conv_kxk_route.restype = C.c_char_p
         # (x, w_dw, dil, t_table, w_pw, bias, y, stream)
         _lib.lhn_conv_dw3_pw_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.lhn_conv_dw3_pw_fwd.restype = C.c_int

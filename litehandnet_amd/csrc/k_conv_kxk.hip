@@ -553,6 +553,14 @@ static int launch_kxk(const lhn_view* x, const float* w, const lhn_view* y, cons
   return 0;
 }
 
+// gridDim.x of the nine-tap wgrad (x 9 taps x cosplit groups): a quarter of the CUs, or one pixel chunk per gradient replica --
+// exclusive replica slices, no atomics in the flush (chunked = false: Cout = 256 is split over gridDim.z on long maps as well)
+static int kxk_wgrad_grid(int cus, int ntiles, int nrep, int cosplit, bool chunked) {
+  int grid = (cosplit > 1 && nrep > 1 && chunked) ? nrep : cus / 4;
+  if (grid < 1) grid = 1;
+  return grid > ntiles ? ntiles : grid;
+}
+
 template <int CIN, int NTO, int TAPS, bool PLAIN = false>
 static int launch_kxk_wgrad(const lhn_view* x, const lhn_view* y, const lhn_gradview* gy, float* dw, int stride, int nrep,
                             int64_t rep_stride, hipStream_t s, int cosplit = 1, int wstride = CIN, bool chunked = true) {
@@ -565,9 +573,7 @@ static int launch_kxk_wgrad(const lhn_view* x, const lhn_view* y, const lhn_grad
     lhn_set_error("lhn_conv_kxk_bwd: cannot reserve %zu B of LDS", lds);
     return 2;
   }
-  int grid = TAPS == 1 ? lhn_num_cus() * per_cu / cosplit : lhn_num_cus() / 4;      // x 9 taps
-  // exclusive replica slices: no atomics in the flush (chunked = false: Cout = 256 is split over gridDim.z on long maps as well)
-  if (TAPS > 1 && cosplit > 1 && nrep > 1 && chunked) grid = nrep;
+  int grid = TAPS == 1 ? lhn_num_cus() * per_cu / cosplit : kxk_wgrad_grid(lhn_num_cus(), ntiles, nrep, cosplit, chunked);
   if (grid < 1) grid = 1;
   if (grid > ntiles) grid = ntiles;
   hipLaunchKernelGGL((k_kxk_wgrad<CIN, NTO, TAPS, PLAIN>), dim3(grid, TAPS, cosplit), dim3(256), lds, s, *x, *y, *gy, dw, stride, y->C, M, ntiles, nrep,
@@ -575,40 +581,154 @@ static int launch_kxk_wgrad(const lhn_view* x, const lhn_view* y, const lhn_grad
   return 0;
 }
 
-static int kxk_geometry_ok(const lhn_view* x, const lhn_view* y, int stride) {
-  return y->N == x->N && y->H == (x->H - 1) / stride + 1 && y->W == (x->W - 1) / stride + 1;
+// =====================================================================================================
+// Instances: one list per kernel template.  The launch switches and kxk_name() (the printed name; NULL = no instance) are generated
+// from them and nothing else states the set.  K = 32, 64 or 128 channels exactly, 1, 2 or 4 tiles of 32 per block; K = 256 is two
+// 128-channel slices: inside k_kxk (forward and plain dgrad only), and one k_kxk_wgrad<128, ...> launch per slice.  The one-tap
+// pairs are those of lhn_pw_bwd_split (LHN_KXK_ONETAP, lhn_common.h).
+#define KXK_NT(X, K, ...) X(K, 1, __VA_ARGS__) X(K, 2, __VA_ARGS__) X(K, 4, __VA_ARGS__)
+// k_kxk<KD, NT, MODE, TAPS, PLAIN>: forward; dgrad of the in-place dy; dgrad with dy on the fly; one tap
+#define KXK_INSTANCES(X)                                                                                                \
+  KXK_NT(X, 32, 0, 9, false) KXK_NT(X, 64, 0, 9, false) KXK_NT(X, 128, 0, 9, false) KXK_NT(X, 256, 0, 9, false)         \
+  KXK_NT(X, 32, 1, 9, true) KXK_NT(X, 64, 1, 9, true) KXK_NT(X, 128, 1, 9, true) KXK_NT(X, 256, 1, 9, true)             \
+  KXK_NT(X, 32, 1, 9, false) KXK_NT(X, 64, 1, 9, false) KXK_NT(X, 128, 1, 9, false) LHN_KXK_ONETAP(X, 1, 1, true)
+// k_kxk_wgrad<CIN, NTO, TAPS, PLAIN>
+#define KXK_WGRAD_INSTANCES(X)                                                                                          \
+  KXK_NT(X, 32, 9, true) KXK_NT(X, 64, 9, true) KXK_NT(X, 128, 9, true) KXK_NT(X, 32, 9, false) KXK_NT(X, 64, 9, false) \
+  KXK_NT(X, 128, 9, false) LHN_KXK_ONETAP(X, 1, true)
+
+constexpr int KXK_WGRAD = 2;      // KxkInst::mode of a k_kxk_wgrad instance (0 forward, 1 dgrad: k_kxk's MODE)
+struct KxkInst {
+  int k, nt, mode, taps;          // k = 0: none
+  bool plain;
+};
+constexpr int kxk_key(int k, int nt, int mode, int taps, bool plain) { return (((k * 8 + nt) * 4 + mode) * 16 + taps) * 2 + (plain ? 1 : 0); }
+constexpr int kxk_key(const KxkInst& i) { return kxk_key(i.k, i.nt, i.mode, i.taps, i.plain); }
+
+static const char* kxk_name(const KxkInst& i) {
+  switch (kxk_key(i)) {
+#define X(K, NT, MODE, TAPS, PLAIN) case kxk_key(K, NT, MODE, TAPS, PLAIN): return "k_kxk<" #K ", " #NT ", " #MODE ", " #TAPS ", " #PLAIN ">";
+    KXK_INSTANCES(X)
+#undef X
+#define X(K, NT, TAPS, PLAIN) case kxk_key(K, NT, KXK_WGRAD, TAPS, PLAIN): return "k_kxk_wgrad<" #K ", " #NT ", " #TAPS ", " #PLAIN ">";
+    KXK_WGRAD_INSTANCES(X)
+#undef X
+  }
+  return nullptr;
 }
 
-// Small maps give few 128-pixel tiles (8x8 maps at batch 64: 32 tiles for 256 CUs): split the N = 32*nt output features
-// over gridDim.y so that about two workgroups per CU exist.  Returns the per-block tile count (1, 2 or 4 -> nt / splits).
-// nt = 8 (256 features) starts from two splits: a block holds at most four accumulator tiles.
-static int kxk_nt_block(int M, int nt) {
+static int kxk_launch(const KxkInst& i, const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, double* stats, float* dx,
+                      int dx_acc, int stride, int nout, hipStream_t s, const lhn_bnfin* fin, int nsplit, int parity, const float* wt) {
+  switch (kxk_key(i)) {
+#define X(K, NT, MODE, TAPS, PLAIN) \
+  case kxk_key(K, NT, MODE, TAPS, PLAIN): return launch_kxk<K, NT, MODE, TAPS, PLAIN>(x, w, y, gy, stats, dx, dx_acc, stride, nout, s, fin, nsplit, parity, wt);
+    KXK_INSTANCES(X)
+#undef X
+  }
+  LHN_CHECK_ARG(false, "lhn_conv_kxk: no k_kxk instance for K = %d, %d tiles", i.k, i.nt);
+}
+
+static int kxk_wgrad_launch(const KxkInst& i, const lhn_view* x, const lhn_view* y, const lhn_gradview* gy, float* dw, int stride, int nrep,
+                            int64_t rep_stride, hipStream_t s, int cosplit, int wstride, bool chunked) {
+  switch (kxk_key(i)) {
+#define X(K, NT, TAPS, PLAIN) \
+  case kxk_key(K, NT, KXK_WGRAD, TAPS, PLAIN): return launch_kxk_wgrad<K, NT, TAPS, PLAIN>(x, y, gy, dw, stride, nrep, rep_stride, s, cosplit, wstride, chunked);
+    KXK_WGRAD_INSTANCES(X)
+#undef X
+  }
+  LHN_CHECK_ARG(false, "lhn_conv_kxk: no k_kxk_wgrad instance for %d channels, %d tiles", i.k, i.nt);
+}
+
+// =====================================================================================================
+// Route: which kernels a dense 3x3 call launches.  kxk_fwd_route() and kxk_bwd_route() are pure and the only place that knows the
+// rules; the dispatchers below and lhn_conv_kxk_route() (the host-only query, which the tests and profiles/kxk_instances.md read)
+// call them.  `cus` is what lhn_num_cus() reports: deterministic mode is cus = 2.
+struct KxkShape {
+  int N, H, W;                    // of x
+  int Cin, Cout, stride, nrep;
+  bool dx, dpool;                 // backward: dx wanted, a pooled gradient rides in gy
+};
+struct KxkRoute {
+  bool ok;                        // false: no instance, the call is refused before any launch
+  bool plain;                     // backward: k_dy_inplace in front (dz := dy), the kernels stream dy
+  KxkInst conv;                   // the forward or the data gradient (k = 0: dx is NULL, no dgrad and none needed)
+  int nsplit, par;                //   blocks of 32 * nt features on gridDim.y;  stride-2 dgrad: four pixel-parity classes on gridDim.z
+  KxkInst wgrad;                  // backward: the weight gradient, one launch per slice of wgrad.k input channels
+  int nslices, cosplit;           //   (Cin = 256: two);  groups of 32 * nt output channels on gridDim.z
+  bool chunked, exclusive;        //   pixel chunks = gradient replicas;  the flush is a plain read-add-write (gridDim.x <= nrep)
+};
+
+// LHN_PLAIN, read from the environment on first use: 0 = unset (the size rule), else LHN_KXK_SW_PLAIN0 / LHN_KXK_SW_PLAIN1
+static int kxk_switches() {
+  static const int v = [] { const char* e = getenv("LHN_PLAIN"); return !e ? 0 : e[0] == '1' ? LHN_KXK_SW_PLAIN1 : LHN_KXK_SW_PLAIN0; }();
+  return v;
+}
+
+static int kxk_out_pixels(const KxkShape& s) { return s.N * ((s.H - 1) / s.stride + 1) * ((s.W - 1) / s.stride + 1); }
+
+// Small maps give few 128-pixel tiles (8x8 maps at batch 64: 32 tiles for 256 CUs): split the `nt` 32-feature tiles of the GEMM's N
+// over gridDim.y so that about two workgroups per CU exist.  Returns the per-block tile count (1, 2 or 4 -> nt / splits blocks).
+// nt = 8 (256 features) starts from two splits: a block holds at most four accumulator tiles.  0: not 1, 2, 4 or 8 tiles.
+static int kxk_nt_block(int M, int nt, int cus) {
+  if (nt > 8 || (nt & (nt - 1))) return 0;
   const int ntiles = (M + 127) / 128;
   int splits = nt > 4 ? nt / 4 : 1;
-  while (splits < nt && nt % (splits * 2) == 0 && ntiles * splits < 2 * lhn_num_cus()) splits *= 2;
+  while (splits < nt && ntiles * splits < 2 * cus) splits *= 2;
   return nt / splits;
 }
 
-// The instantiated (K, tiles-per-block) pairs of k_kxk / k_kxk_wgrad: K = 32, 64, 128 or 256 channels exactly, 1, 2 or 4 tiles
-// of 32.  K = 256 is two 128-channel slices: inside k_kxk, and one k_kxk_wgrad<128, ...> launch per slice.
-static bool kxk_instance_ok(int k, int nt) { return (k == 32 || k == 64 || k == 128 || k == 256) && (nt == 1 || nt == 2 || nt == 4); }
-static bool kxk_tiles_ok(int ntot) { return ntot == 1 || ntot == 2 || ntot == 4 || ntot == 8; }
+static KxkRoute kxk_fwd_route(const KxkShape& s, int cus, int) {
+  KxkRoute r = {};
+  const int ntot = (s.Cout + 31) / 32, nt = kxk_nt_block(kxk_out_pixels(s), ntot, cus);      // GEMM N = Cout, K = Cin
+  r.conv = {s.Cin, nt, 0, 9, false};
+  r.nsplit = nt ? ntot / nt : 0;
+  r.ok = kxk_name(r.conv) != nullptr;
+  return r;
+}
+
+static KxkRoute kxk_bwd_route(const KxkShape& s, int cus, int sw) {
+  KxkRoute r = {};
+  // Large channel counts: turn dz into dy in place, then stream it plain (LHN_PLAIN=0/1 overrides the size rule).  A channel-attention
+  // pooled gradient always takes this path: lhn_dy_fast has no pooled term.  So does a side of 256 channels: the sliced dgrad has no
+  // dy-on-the-fly instance (a second set of y-transform and coefficient registers per slice), and by the size rule it is plain anyway.
+  r.plain = s.dpool || s.Cin > 128 || s.Cout > 128 ||
+            ((sw & LHN_KXK_SW_PLAIN1) ? true : (sw & LHN_KXK_SW_PLAIN0) ? false : s.Cin * s.Cout >= 64 * 64);
+  if (s.dx) {      // GEMM N = Cin, K = Cout (256: two slices inside the kernel, dx written once)
+    const int ntot = (s.Cin + 31) / 32, nt = kxk_nt_block(s.N * s.H * s.W, ntot, cus);
+    r.conv = {s.Cout, nt, 1, 9, r.plain};
+    r.nsplit = nt ? ntot / nt : 0;
+    r.par = s.stride == 2;
+  }
+  // Cout >= 64: one 32-channel group per block (gridDim.z), pixel chunks = gradient replicas -> atomic-free flush (only while a pixel
+  // chunk stays short: <= 16 tiles of 64 pixels per block; big maps amortise the atomic flush).  Cout = 256: eight groups the same
+  // way, or two groups of four tiles (a block holds at most four) with the atomic flush.
+  const int wtot = (s.Cout + 31) / 32, wtiles = (kxk_out_pixels(s) + 63) / 64;
+  r.chunked = s.Cin >= 64 && s.nrep > 1 && wtiles <= 16 * s.nrep;
+  r.cosplit = wtot == 8 ? (r.chunked ? 8 : 2) : ((wtot == 2 || wtot == 4) && r.chunked ? wtot : 1);
+  // Cin = 256: once per 128-channel input slice (disjoint columns of dW)
+  r.nslices = s.Cin > 128 ? 2 : 1;
+  r.wgrad = {s.Cin / r.nslices, wtot / r.cosplit, KXK_WGRAD, 9, r.plain};
+  r.exclusive = kxk_wgrad_grid(cus, wtiles, s.nrep, r.cosplit, r.chunked) <= s.nrep;
+  r.ok = (!s.dx || kxk_name(r.conv)) && kxk_name(r.wgrad) && s.Cin % r.nslices == 0;
+  return r;
+}
+
+// =====================================================================================================
+// Dispatchers: validate, ask the route, refuse BEFORE the first launch (a refused call writes nothing, not even the weight scratch;
+// k_dy_inplace consumes dz and the dgrad writes dx, so a call refused after them would leave both changed), launch.
+static int kxk_geometry_ok(const lhn_view* x, const lhn_view* y, int stride) {
+  return y->N == x->N && y->H == (x->H - 1) / stride + 1 && y->W == (x->W - 1) / stride + 1;
+}
 
 extern "C" int lhn_conv_kxk_fwd(const lhn_view* x, const float* w, const lhn_view* y, double* stats, int stride,
                                 const lhn_bnfin* fin, float* wt_scratch, void* stream) {
   LHN_CHECK_ARG(lhn_view_ok(x) && lhn_view_ok(y) && w && lhn_no_pend(x), "lhn_conv_kxk_fwd: bad view / null pointer (no pending BatchNorm here)");
   LHN_CHECK_ARG((stride == 1 || stride == 2) && kxk_geometry_ok(x, y, stride), "lhn_conv_kxk_fwd: geometry / stride %d", stride);
-  const int ntot = (y->C + 31) / 32, nt = kxk_tiles_ok(ntot) ? kxk_nt_block(y->N * y->H * y->W, ntot) : ntot;
-  // decided BEFORE the first launch: a refused call writes nothing (not even the weight scratch)
-  LHN_CHECK_ARG(kxk_instance_ok(x->C, nt), "lhn_conv_kxk_fwd: unsupported channels Cin=%d Cout=%d", x->C, y->C);
+  const KxkRoute r = kxk_fwd_route({x->N, x->H, x->W, x->C, y->C, stride, 1, false, false}, lhn_num_cus(), kxk_switches());
+  LHN_CHECK_ARG(r.ok, "lhn_conv_kxk_fwd: unsupported channels Cin=%d Cout=%d", x->C, y->C);
   hipStream_t s = (hipStream_t)stream;
-  int rc = -1;
   if (wt_scratch) launch_w_tapmajor(w, wt_scratch, y->C, x->C, 0, s);
-#define KF(CI, NTV) if (x->C == CI && nt == NTV) rc = launch_kxk<CI, NTV, 0, 9>(x, w, y, nullptr, stats, nullptr, 0, stride, y->C, s, fin, ntot / nt, 0, wt_scratch);
-  KF(32, 1) KF(64, 2) KF(128, 4) KF(32, 2) KF(64, 1) KF(64, 4) KF(128, 2) KF(128, 1) KF(32, 4)
-  KF(256, 4) KF(256, 2) KF(256, 1)
-#undef KF
-  LHN_CHECK_ARG(rc != -1, "lhn_conv_kxk_fwd: unsupported channels Cin=%d Cout=%d", x->C, y->C);
+  const int rc = kxk_launch(r.conv, x, w, y, nullptr, stats, nullptr, 0, stride, y->C, s, fin, r.nsplit, 0, wt_scratch);
   if (rc) return rc;
   LHN_CHECK_LAUNCH("lhn_conv_kxk_fwd");
   return 0;
@@ -620,87 +740,74 @@ extern "C" int lhn_conv_kxk_bwd(const lhn_view* x, const float* w, const lhn_vie
   LHN_CHECK_ARG(lhn_view_ok(x) && lhn_view_ok(y) && w && gy && gy->dz && dw && lhn_no_pend(x) && lhn_no_pend(y), "lhn_conv_kxk_bwd: bad view / null pointer");
   LHN_CHECK_ARG((stride == 1 || stride == 2) && kxk_geometry_ok(x, y, stride), "lhn_conv_kxk_bwd: geometry / stride %d", stride);
   if (nrep < 1) nrep = 1;
+  const KxkRoute r = kxk_bwd_route({x->N, x->H, x->W, x->C, y->C, stride, nrep, dx != nullptr, gy->dpool != nullptr}, lhn_num_cus(), kxk_switches());
+  LHN_CHECK_ARG(r.ok, "lhn_conv_kxk_bwd: unsupported channels Cin=%d Cout=%d", x->C, y->C);
   hipStream_t s = (hipStream_t)stream;
-  int rc = -1;
-  // Every instance is decided BEFORE the first launch: k_dy_inplace consumes dz and the dgrad writes dx, so a call refused
-  // after them would leave both changed.
-  const int wtot = (y->C + 31) / 32, wtiles = (y->N * y->H * y->W + 63) / 64;
-  // Cout >= 64: one 32-channel group per block (gridDim.z), pixel chunks = gradient replicas -> atomic-free flush
-  // (only while a pixel chunk stays short: <= 16 tiles of 64 pixels per block; big maps amortise the atomic flush)
-  // Cout = 256: eight groups the same way, or two groups of four tiles (a block holds at most four) with the atomic flush
-  const bool chunked = x->C >= 64 && nrep > 1 && wtiles <= 16 * nrep;
-  const int cosplit = wtot == 8 ? (chunked ? 8 : 2) : ((wtot == 2 || wtot == 4) && chunked ? wtot : 1), nto = wtot / cosplit;
-  const int dtot = (x->C + 31) / 32, dnt = kxk_tiles_ok(dtot) ? kxk_nt_block(x->N * x->H * x->W, dtot) : dtot;
-  LHN_CHECK_ARG((!dx || kxk_instance_ok(y->C, dnt)) && kxk_instance_ok(x->C, nto), "lhn_conv_kxk_bwd: unsupported channels Cin=%d Cout=%d",
-                x->C, y->C);
-  // large channel counts: turn dz into dy in place, then stream it plain (LHN_PLAIN=0/1 overrides the size rule).  A
-  // channel-attention pooled gradient always takes this path: lhn_dy_fast has no pooled term.
-  // A side of 256 channels is always plain, whatever LHN_PLAIN says: the sliced dgrad has no dy-on-the-fly instance (a second
-  // set of y-transform and coefficient registers per slice), and by the size rule these cases are plain anyway.
-  const char* pe = getenv("LHN_PLAIN");
-  const bool plain = gy->dpool || x->C > 128 || y->C > 128 || (pe ? (pe[0] == '1') : (x->C * y->C >= 64 * 64));
-  if (plain) launch_dy_inplace(y, gy, s);
-  if (dx) {
-    // GEMM N = Cin, K = Cout
-    const int par = stride == 2 ? 1 : 0;     // stride 2: four parity classes of input pixels (gridDim.z)
+  if (r.plain) launch_dy_inplace(y, gy, s);
+  if (r.conv.k) {
     if (wt_scratch) launch_w_tapmajor(w, wt_scratch, y->C, x->C, 1, s);
-    const int ntot = dtot, nt = dnt;
-#define KB(CO, NTV) if (y->C == CO && nt == NTV) rc = plain ? launch_kxk<CO, NTV, 1, 9, true>(x, w, y, gy, nullptr, dx, dx_accumulate, stride, x->C, s, nullptr, ntot / nt, par, wt_scratch) : launch_kxk<CO, NTV, 1, 9, false>(x, w, y, gy, nullptr, dx, dx_accumulate, stride, x->C, s, nullptr, ntot / nt, par, wt_scratch);
-    KB(32, 1) KB(64, 2) KB(128, 4) KB(32, 2) KB(64, 1) KB(64, 4) KB(128, 2) KB(128, 1) KB(32, 4)
-#undef KB
-    // K = Cout = 256 in two slices inside the kernel (dx written once); plain only
-#define KB(NTV) if (y->C == 256 && nt == NTV) rc = launch_kxk<256, NTV, 1, 9, true>(x, w, y, gy, nullptr, dx, dx_accumulate, stride, x->C, s, nullptr, ntot / nt, par, wt_scratch);
-    KB(4) KB(2) KB(1)
-#undef KB
-    LHN_CHECK_ARG(rc != -1, "lhn_conv_kxk_bwd: unsupported channels Cin=%d Cout=%d", x->C, y->C);      // (kxk_instance_ok lists them all)
+    const int rc = kxk_launch(r.conv, x, w, y, gy, nullptr, dx, dx_accumulate, stride, x->C, s, nullptr, r.nsplit, r.par, wt_scratch);
     if (rc) return rc;
   }
-  // Cin = 256: once per 128-channel input slice (disjoint columns of dW: row length wstride = Cin, the slice starts 9 * k0 in)
-  const int kslice = x->C > 128 ? 128 : x->C;
-  for (int k0 = 0; k0 < x->C; k0 += kslice) {
+  for (int k0 = 0; k0 < x->C; k0 += r.wgrad.k) {      // row length of dW = Cin (wstride), the slice starts 9 * k0 in
     lhn_view xv = *x;
     xv.coff += k0;
-    xv.C = kslice;
-    float* dwk = dw + (size_t)9 * k0;
-    rc = -1;
-#define KW(CI, NTV) if (kslice == CI && nto == NTV) rc = plain ? launch_kxk_wgrad<CI, NTV, 9, true>(&xv, y, gy, dwk, stride, nrep, rep_stride, s, cosplit, x->C, chunked) : launch_kxk_wgrad<CI, NTV, 9, false>(&xv, y, gy, dwk, stride, nrep, rep_stride, s, cosplit, x->C, chunked);
-    KW(32, 1) KW(64, 2) KW(128, 4) KW(32, 2) KW(64, 1) KW(64, 4) KW(128, 2) KW(128, 1) KW(32, 4)
-#undef KW
-    LHN_CHECK_ARG(rc != -1, "lhn_conv_kxk_bwd: unsupported channels Cin=%d Cout=%d", x->C, y->C);
+    xv.C = r.wgrad.k;
+    const int rc = kxk_wgrad_launch(r.wgrad, &xv, y, gy, dw + (size_t)9 * k0, stride, nrep, rep_stride, s, r.cosplit, x->C, r.chunked);
     if (rc) return rc;
   }
   LHN_CHECK_LAUNCH("lhn_conv_kxk_bwd");
   return 0;
 }
 
+// Host only: the names of what the two dispatchers would launch, in order (include/lhn.h).
+extern "C" const char* lhn_conv_kxk_route(int backward, int N, int H, int W, int Cin, int Cout, int stride, int nrep, int features, int cus,
+                                          int switches) {
+  if ((stride != 1 && stride != 2) || N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) return nullptr;
+  const KxkShape sh = {N, H, W, Cin, Cout, stride, nrep < 1 ? 1 : nrep, (features & LHN_KXK_F_DX) != 0, (features & LHN_KXK_F_DPOOL) != 0};
+  const KxkRoute r = (backward ? kxk_bwd_route : kxk_fwd_route)(sh, cus > 0 ? cus : lhn_num_cus(), switches < 0 ? kxk_switches() : switches);
+  if (!r.ok) return nullptr;
+  static thread_local char buf[256];
+  size_t len = 0;
+  auto put = [&](const char* fmt, auto... a) { len += snprintf(buf + len, sizeof(buf) - len, fmt, a...); };      // (the longest answer is 110 characters)
+  auto launch = [&](const char* name) { put(len ? " + %s" : "%s", name); };
+  if (r.plain) launch("k_dy_inplace");
+  if (r.conv.k) {
+    if (features & LHN_KXK_F_WT) launch("k_w_tapmajor");
+    launch(kxk_name(r.conv));
+    if (r.nsplit > 1) put(" y%d", r.nsplit);
+    if (r.par) put("%s", " par");
+  }
+  if (backward) {
+    launch(kxk_name(r.wgrad));
+    if (r.cosplit > 1) put(" z%d", r.cosplit);
+    put(" %s", r.exclusive ? "excl" : "atomic");
+    if (r.nslices > 1) put(" x %d", r.nslices);
+  }
+  return buf;
+}
+
 // 1x1 backward as three launches (k_dy_inplace, dgrad, wgrad = the per-tap kernel with one tap): lhn_conv_pw_bwd takes it for large
 // Cin*Cout where the fused kernel is LDS-bound to one block per CU.  Channel counts above 128 (hourglass: 256) run as 128-wide
 // slices: dgrad accumulates over output-channel slices (its K), wgrad runs once per input-channel slice with the output channels
-// on gridDim.z.  pw_bwd_route (k_conv_pw.hip) has checked that every slice has an instance (lhn_pw_split_instance) and says which
-// kernel the data gradient takes: dy is formed in place, so nothing can be refused from here on.
+// on gridDim.z (lhn_pw_split_tiles, lhn_common.h).  pw_bwd_route (k_conv_pw.hip) has checked that every slice has an instance
+// (lhn_pw_split_instance) and says which kernel the data gradient takes: dy is formed in place, so nothing can be refused from here on.
 int lhn_pw_bwd_split(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate,
                      float* dw, float* dbias, int nrep, int64_t rep_stride, int dgrad, hipStream_t s) {
   const int Cin = x->C, Cout = y->C;
-  const int ntd = Cin >= 128 ? 4 : (Cin + 31) / 32;                  // dgrad: features per block = 32*ntd, the rest on gridDim.y
-  const int nto = Cout >= 128 ? 4 : (Cout + 31) / 32;
+  const LhnPwSplitTiles t = lhn_pw_split_tiles(Cin, Cout);
   launch_dy_inplace(y, gy, s, dbias, nrep, rep_stride);
   // K = 256 in one pass on the register-W kernel (dy as input, W transposed: no second K slice accumulating into dx), else <= 128
-  const int costep = dgrad == LHN_PW_DGRAD_WR256 ? 256 : 128;
-  for (int co0 = 0; dgrad != LHN_PW_DGRAD_NONE && co0 < Cout; co0 += costep) {
-    const int cc = Cout - co0 < costep ? Cout - co0 : costep;
+  const int cc = dgrad == LHN_PW_DGRAD_WR256 ? 256 : t.cc;
+  for (int co0 = 0; dgrad != LHN_PW_DGRAD_NONE && co0 < Cout; co0 += cc) {
     lhn_view yv = *y;
     yv.coff += co0;
     yv.C = cc;
     const float* wv = w + (size_t)co0 * Cin;
-    const int acc = dx_accumulate || co0 > 0, nsplit = (Cin + 32 * ntd - 1) / (32 * ntd);
+    const int acc = dx_accumulate || co0 > 0;
     int rc = 0;
     if (dgrad == LHN_PW_DGRAD_KXK) {
-      switch (cc * 10 + ntd) {
-#define PB(CO, NTV) case CO * 10 + NTV: rc = launch_kxk<CO, NTV, 1, 1, true>(x, wv, &yv, gy, nullptr, dx, acc, 1, x->C, s, nullptr, nsplit); break;
-        PB(64, 4) PB(128, 4) PB(128, 2) PB(64, 2) PB(128, 1) PB(32, 4)
-#undef PB
-        default: LHN_CHECK_ARG(false, "lhn_conv_pw_bwd: no one-tap dgrad instance for %d features", cc);
-      }
+      rc = kxk_launch({cc, t.ntd, 1, 1, true}, x, wv, &yv, gy, nullptr, dx, acc, 1, Cin, s, nullptr, t.nsplit, 0, nullptr);
     } else {      // the register-resident-weights 1x1 kernel (k_conv_pw.hip) run on dy with W transposed, <= 128 input channels per launch
       lhn_view dyv = yv, dxv = *x;
       dyv.data = const_cast<float*>(gy->dz);
@@ -708,27 +815,19 @@ int lhn_pw_bwd_split(const lhn_view* x, const float* w, const lhn_view* y, const
       dyv.table = dxv.table = nullptr;
       dyv.gate = dxv.gate = nullptr;
       dyv.pend = dxv.pend = nullptr;
-      for (int ci0 = 0; ci0 < Cin && !rc; ci0 += 128) {
+      dxv.C = t.kc;
+      for (int ci0 = 0; ci0 < Cin && !rc; ci0 += t.kc) {
         dxv.coff = x->coff + ci0;
-        dxv.C = Cin - ci0 < 128 ? Cin - ci0 : 128;
         rc = lhn_pw_dgrad_wr(&dyv, wv + ci0, &dxv, Cin, acc, s);
       }
     }
     if (rc) return rc;
   }
-  for (int k0 = 0; k0 < Cin; k0 += 128) {
-    const int kc = Cin - k0 < 128 ? Cin - k0 : 128;
+  for (int k0 = 0; k0 < Cin; k0 += t.kc) {
     lhn_view xv = *x;
     xv.coff += k0;
-    xv.C = kc;
-    const int cosplit = (Cout + 32 * nto - 1) / (32 * nto);
-    int rc = 0;
-    switch (kc * 10 + nto) {
-#define PW(CI, NTV) case CI * 10 + NTV: rc = launch_kxk_wgrad<CI, NTV, 1, true>(&xv, y, gy, dw + k0, 1, nrep, rep_stride, s, cosplit, Cin); break;
-      PW(64, 4) PW(128, 4) PW(128, 2) PW(64, 2) PW(128, 1) PW(32, 4)
-#undef PW
-      default: LHN_CHECK_ARG(false, "lhn_conv_pw_bwd: no one-tap wgrad instance for %d channels", kc);
-    }
+    xv.C = t.kc;
+    const int rc = kxk_wgrad_launch({t.kc, t.nto, KXK_WGRAD, 1, true}, &xv, y, gy, dw + k0, 1, nrep, rep_stride, s, t.cosplit, Cin, true);
     if (rc) return rc;
   }
   return 0;

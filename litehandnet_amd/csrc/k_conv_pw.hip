@@ -1380,11 +1380,11 @@ static inline int pw_bwd_cin_tile(int kc) { return kc <= 32 ? 32 : pw_cin_tile(k
 // The split path's instances: every slice must have one BEFORE anything is launched (dy is formed in place: no way back afterwards).
 // Slices are all alike: channel counts above 128 must be multiples of 128.
 static bool pw_split_route(const PwShape& s, unsigned sw, int* dgrad) {
-  const int ntd = s.Cin >= 128 ? 4 : (s.Cin + 31) / 32, nto = s.Cout >= 128 ? 4 : (s.Cout + 31) / 32;
-  const int cc = s.Cout < 128 ? s.Cout : 128, kc = s.Cin < 128 ? s.Cin : 128;
+  const LhnPwSplitTiles t = lhn_pw_split_tiles(s.Cin, s.Cout);
+  const int cc = t.cc, kc = t.kc;
   const bool dx = !(s.f & LHN_PW_F_NO_DX), regw = !(sw & LHN_PW_SW_LDSW);
   if ((s.Cin > 128 && s.Cin % 128 != 0) || (s.Cout > 128 && s.Cout % 128 != 0)) return false;
-  if ((dx && !lhn_pw_split_instance(cc, ntd)) || !lhn_pw_split_instance(kc, nto)) return false;
+  if ((dx && !lhn_pw_split_instance(cc, t.ntd)) || !lhn_pw_split_instance(kc, t.nto)) return false;
   *dgrad = !dx ? LHN_PW_DGRAD_NONE
            : (regw && s.Cout == 256 && pw_wr_instance(256, kc, false).ci) ? LHN_PW_DGRAD_WR256
            : (regw && (cc == 32 || cc == 64 || cc == 128) && pw_wr_instance(cc, kc, false).ci) ? LHN_PW_DGRAD_WR
@@ -1765,18 +1765,18 @@ extern "C" const char* lhn_conv_pw_route(int backward, int N, int H, int W, int 
       break;
     case PWB_SPLIT: {
       emit("k_dy_inplace");
-      const int ntd = Cin >= 128 ? 4 : (Cin + 31) / 32, nto = Cout >= 128 ? 4 : (Cout + 31) / 32, cc = Cout < 128 ? Cout : 128, kc = Cin < 128 ? Cin : 128;
-      const int nco = r.dgrad == LHN_PW_DGRAD_WR256 ? 1 : (Cout + 127) / 128, nk = (Cin + 127) / 128;
-      for (int j = 0; r.dgrad != LHN_PW_DGRAD_NONE && j < nco * (r.dgrad == LHN_PW_DGRAD_KXK ? 1 : nk); ++j) {
+      const LhnPwSplitTiles t = lhn_pw_split_tiles(Cin, Cout);      // what lhn_pw_bwd_split launches from
+      const int nco = r.dgrad == LHN_PW_DGRAD_WR256 ? 1 : t.nco;
+      for (int j = 0; r.dgrad != LHN_PW_DGRAD_NONE && j < nco * (r.dgrad == LHN_PW_DGRAD_KXK ? 1 : t.nk); ++j) {
         if (r.dgrad == LHN_PW_DGRAD_KXK) {
-          snprintf(cur, sizeof(cur), "k_kxk<%d, %d, 1, 1, true>", cc, ntd);
+          snprintf(cur, sizeof(cur), "k_kxk<%d, %d, 1, 1, true>", t.cc, t.ntd);
           emit(cur);
         } else {
-          fwd_name(pw_wr_instance(r.dgrad == LHN_PW_DGRAD_WR256 ? 256 : cc, kc, false));
+          fwd_name(pw_wr_instance(r.dgrad == LHN_PW_DGRAD_WR256 ? 256 : t.cc, t.kc, false));
         }
       }
-      snprintf(cur, sizeof(cur), "k_kxk_wgrad<%d, %d, 1, true>", kc, nto);
-      for (int j = 0; j < nk; ++j) emit(cur);
+      snprintf(cur, sizeof(cur), "k_kxk_wgrad<%d, %d, 1, true>", t.kc, t.nto);
+      for (int j = 0; j < t.nk; ++j) emit(cur);
       break;
     }
     default:

@@ -91,8 +91,27 @@ enum { LHN_PW_DGRAD_NONE = 0,      // dx is NULL
        LHN_PW_DGRAD_KXK };         // k_kxk with one tap
 int lhn_pw_bwd_split(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate,
                      float* dw, float* dbias, int nrep, int64_t rep_stride, int dgrad, hipStream_t s);
-// its one-tap instances of k_kxk and k_kxk_wgrad: k = the slice's K (output features / input channels), nt = 32-wide tiles per block
-static inline bool lhn_pw_split_instance(int k, int nt) { return (k == 64 && (nt == 4 || nt == 2)) || (k == 128 && (nt == 4 || nt == 2 || nt == 1)) || (k == 32 && nt == 4); }
+// Its one-tap instances of k_kxk and k_kxk_wgrad: (K of the slice = output features / input channels, 32-wide tiles per block), the
+// rest of the template arguments behind.  k_conv_kxk.hip instantiates exactly these; pw_split_route (k_conv_pw.hip) asks the predicate.
+#define LHN_KXK_ONETAP(X, ...) \
+  X(64, 4, __VA_ARGS__) X(128, 4, __VA_ARGS__) X(128, 2, __VA_ARGS__) X(64, 2, __VA_ARGS__) X(128, 1, __VA_ARGS__) X(32, 4, __VA_ARGS__)
+static inline bool lhn_pw_split_instance(int k, int nt) {
+#define LHN_X(K, NT, ...) || (k == K && nt == NT)
+  return false LHN_KXK_ONETAP(LHN_X, 0);
+#undef LHN_X
+}
+// Its tiles.  Slices are all alike (pw_split_route: channel counts above 128 are multiples of 128).  dgrad: 32 * ntd of the Cin
+// features per block, nsplit blocks on gridDim.y, K = cc of the Cout channels per launch (LHN_PW_DGRAD_WR256: all 256 at once);
+// wgrad: one launch per kc input channels (nk of them), 32 * nto output channels per block, cosplit groups on gridDim.z.
+struct LhnPwSplitTiles {
+  int ntd, nsplit, cc, nco;
+  int nto, cosplit, kc, nk;
+};
+static inline LhnPwSplitTiles lhn_pw_split_tiles(int Cin, int Cout) {
+  const int ntd = Cin >= 128 ? 4 : (Cin + 31) / 32, nto = Cout >= 128 ? 4 : (Cout + 31) / 32;
+  return {ntd, (Cin + 32 * ntd - 1) / (32 * ntd), Cout < 128 ? Cout : 128, (Cout + 127) / 128,
+          nto, (Cout + 32 * nto - 1) / (32 * nto), Cin < 128 ? Cin : 128, (Cin + 127) / 128};
+}
 // k_bottleneck.hip: lhn_bottleneck_fwd with the choice of skipping the tap-major copy of w2 (relayout = 0: wt_scratch holds it already)
 int lhn_bottleneck_fwd_impl(const lhn_view* x, int Cm, const float* w1, const float* b1, const float* t1, const float* w2, const float* t2,
                             const float* w3, const float* b3, const float* t3, float out_slope, const lhn_view* y, float* wt_scratch,

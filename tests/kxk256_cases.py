@@ -5,19 +5,10 @@ over them -- stay as they are.  Imported by tests/test_kxk256_gpu.py; as a scrip
     python tests/kxk256_cases.py OUT.npz REPEATS fwd:NAME bwd:NAME ...
     python tests/kxk256_cases.py --check-reference        (CPU only)
 
-What runs where.  K = 256 (forward: Cin; dgrad: Cout) is k_kxk<256, NT, MODE, 9>: two 128-channel slices per tap inside the tile loop,
-18 phases per tile.  256 features (forward: Cout; dgrad: Cin) are 8 tiles of 32: at most 4 per block, the rest on gridDim.y (2, 4 or
-8).  The wgrad runs k_kxk_wgrad<128, NTO, 9, true> once per 128-channel input slice; Cout = 256 is NTO = 1 with 8 groups on gridDim.z
-(the exclusive flush: nrep > 1, Cin >= 64, <= 16 * nrep tiles of 64 pixels) or NTO = 4 with 2 groups (the atomic flush).  Every case
-with a side of 256 is on the plain path (dz := dy in place first), whatever LHN_PLAIN says.
-"det" = the LHN_DETERMINISTIC=1 child (2 CUs reported), otherwise the default mode on 256 CUs:
-    k_kxk<256, NT, 0, 9> (forward, Cin = 256)
-      <256,1> pair_256_*, tiny, view, tail, s2_*, mt_256_* (gridDim.y = Cout / 32)    <256,2> mt_256_64 det
-      <256,4> mt_256_128 det, mt_256_256 det (gridDim.y = 2), big_256_256 (292 tiles on 256 x 2 workgroups: one per CU)
-    k_kxk<256, NT, 1, 9, true> (dgrad, Cout = 256)
-      <256,1> pair_*_256, rep1_*_256, tiny, s2_* (four parity classes), cosplit, nocosplit, full    <256,2> mt_64_256 det
-      <256,4> mt_128_256 det, mt_256_256 det (gridDim.y = 2), big_256_256
-    forward n -> 256 and dgrad 256 -> n with n < 256 run the <n, NT> instances they ran before, with gridDim.y up to 8.
+What runs where: profiles/kxk_instances.md (printed by `python tests/kxk_cases.py --instances` from kxk_cases.kernel_of, which serves the
+tables registered here too).  K = 256 runs as two 128-channel slices per tap inside k_kxk<256, NT, MODE, 9>, 256 features as blocks of at
+most 4 tiles of 32 on gridDim.y, the weight gradient once per 128-channel input slice; every case with a side of 256 is on the plain
+path (dz := dy in place first), whatever LHN_PLAIN says.
 The `fwd:fin_256_256` pseudo-case is pair-shaped with a fused BatchNorm finalize (run_fwd_fin).
 
 Is the bar max(2e-5, 3 * e32) meaningful at K = 2,304?  --check-reference prints e32 (torch's float32 CPU run against float64,

@@ -5,34 +5,9 @@ it writes the kernel outputs of the named cases to an .npz file:
     python tests/kxk_cases.py OUT.npz REPEATS fwd:NAME bwd:NAME ...
     python tests/kxk_cases.py --check-reference        (CPU only: every case's inputs and both references)
 
-Which case reaches which template instantiation (TAPS = 9), from the dispatch arithmetic of the two entry points on 256 CUs:
-kxk_nt_block keeps splitting the 32-feature tiles over gridDim.y while tiles * splits < 2 * CUs, so the 351-pixel `pair_*` cases
-(3 tiles) always run NT = 1 and `big_128_128` (517 tiles) runs NT = 4; under LHN_DETERMINISTIC=1 the library reports 2 CUs and
-the 1,800-pixel `mt_*` cases (15 tiles) run NT = Cout / 32 (forward) or Cin / 32 (dgrad).  PLAIN (dz := dy first) is
-Cin * Cout >= 4096 or a pooled gradient, unless LHN_PLAIN says otherwise.  The wgrad runs NTO = Cout / 32 tiles per block, or
-NTO = 1 with the 32-channel groups on gridDim.z ("cosplit": Cin >= 64, Cout 64 / 128, nrep > 1, <= 16 * nrep tiles of 64 pixels).
-"det" = the LHN_DETERMINISTIC=1 child, "P0" / "P1" = LHN_PLAIN=0 / 1 (on top of "det" where both are named).
-
-    k_kxk<KD = Cin, NT, 0, 9>  (forward)
-      <32,1> fwd:pair_32_32    <64,1> fwd:pair_64_32    <128,1> fwd:pair_128_32                      default
-      <32,2> fwd:mt_32_64      <64,2> fwd:mt_64_64      <128,2> fwd:mt_128_64                        det
-      <32,4> fwd:mt_32_128     <64,4> fwd:mt_64_128     <128,4> fwd:mt_128_128 det, fwd:big_128_128 default
-    k_kxk<KD = Cout, NT, 1, 9, PLAIN = true>  (dgrad of dy formed in place)
-      <32,1> bwd:pair_128_32   <64,1> bwd:pair_64_64    <128,1> bwd:pair_32_128                      default
-      <32,2> bwd:mt_64_32 det+P1    <64,2> bwd:mt_64_64 det      <128,2> bwd:mt_64_128 det
-      <32,4> bwd:mt_128_32 det      <64,4> bwd:mt_128_64 det     <128,4> bwd:mt_128_128 det, bwd:big_128_128 default
-    k_kxk<KD = Cout, NT, 1, 9, PLAIN = false>  (dgrad, dy on the fly)
-      <32,1> bwd:pair_32_32 default <64,1> bwd:pair_32_64 default   <128,1> bwd:pair_32_128 P0
-      <32,2> bwd:mt_64_32 det       <64,2> bwd:mt_64_64 det+P0      <128,2> bwd:mt_64_128 det+P0
-      <32,4> bwd:mt_128_32 det+P0   <64,4> bwd:mt_128_64 det+P0     <128,4> bwd:mt_128_128 det+P0
-    k_kxk_wgrad<CIN, NTO, 9, PLAIN = true>
-      <32,1> bwd:pair_32_32 P1      <32,2> bwd:pair_32_64 P1        <32,4> bwd:pair_32_128 default
-      <64,1> bwd:pair_64_64 default (cosplit)   <64,2> bwd:rep1_64_64 default    <64,4> bwd:rep1_64_128 default
-      <128,1> bwd:pair_128_32 default           <128,2> bwd:rep1_128_64 default  <128,4> bwd:rep1_128_128, bwd:big_128_128 default
-    k_kxk_wgrad<CIN, NTO, 9, PLAIN = false>
-      <32,1> bwd:pair_32_32 default (K-split 4) <32,2> bwd:pair_32_64 default (K-split 2)  <32,4> bwd:pair_32_128 P0
-      <64,1> bwd:pair_64_32 default (K-split 2) <64,2> bwd:rep1_64_64 P0                   <64,4> bwd:rep1_64_128 P0
-      <128,1> bwd:pair_128_32 P0                <128,2> bwd:rep1_128_64 P0                 <128,4> bwd:rep1_128_128 P0"""
+    python tests/kxk_cases.py --instances              (CPU only: prints profiles/kxk_instances.md)
+kernel_of(kind, name) asks the library which kernels a case launches (lhn_conv_kxk_route: host only); which case reaches which
+template instantiation, by default, in the deterministic child (2 CUs) and under LHN_PLAIN=0 / 1, is profiles/kxk_instances.md."""
 import ctypes as C
 import os
 import sys
@@ -131,9 +106,32 @@ def geometry(kind, name):
 
 def plain_path(c):
     """Whether lhn_conv_kxk_bwd turns dz into dy in place for this case, under this process's environment (as the library's
-    getenv sees it: a variable that is set but empty is set, and is not '1')."""
+    getenv sees it: a variable that is set but empty is set, and is not '1').  The harness's own statement of the rule;
+    tests/test_kxk_route_cpu.py holds it against the library's answer for every case and setting."""
     pe = os.environ.get("LHN_PLAIN")
-    return "dpool" in c["flags"] or (pe[:1] == "1" if pe is not None else c["cin"] * c["cout"] >= 64 * 64)
+    return ("dpool" in c["flags"] or max(c["cin"], c["cout"]) > 128 or
+            (pe[:1] == "1" if pe is not None else c["cin"] * c["cout"] >= 64 * 64))
+
+
+# LHN_KXK_F_* / LHN_KXK_SW_* (include/lhn.h)
+F_DX, F_DPOOL, F_WT = 1, 2, 4
+SW_PLAIN0, SW_PLAIN1 = 1, 2
+# the settings a table of profiles/kxk_instances.md is printed for: title, kernel_of keywords
+SETTINGS = (("default dispatch on 256 CUs", {}), ("`LHN_DETERMINISTIC=1` (2 CUs, 16 gradient replicas)", {"cus": 2}),
+            ("`LHN_PLAIN=0`", {"plain": 0}), ("`LHN_PLAIN=1`", {"plain": 1}))
+
+
+def kernel_of(kind, name, cus=256, plain=None, wt=True):
+    """The launches of lhn_conv_kxk_fwd / lhn_conv_kxk_bwd for a case (of this module or of kxk256_cases, once imported), in order,
+    asked of the library (lhn_conv_kxk_route: host only).  cus: the compute units the grids are sized for; 2 is deterministic mode,
+    in which run_bwd passes 16 gradient replicas (_nrep).  plain: LHN_PLAIN=0 / 1, None = unset.  None: no kernel for the case."""
+    c = _ALL[kind][name]
+    n, h, w = c["nhw"]
+    feat = F_WT * wt | (F_DX * ("nodx" not in c["flags"]) | F_DPOOL * ("dpool" in c["flags"]) if kind == "bwd" else 0)
+    sw = 0 if plain is None else (SW_PLAIN1 if int(plain) == 1 else SW_PLAIN0)
+    r = _lib.lib().lhn_conv_kxk_route(int(kind == "bwd"), n, h, w, c["cin"], c["cout"], c["stride"], 16 if cus == 2 else c.get("nrep", 4),
+                                      feat, cus, sw)
+    return r.decode() if r is not None else None
 
 
 def _gen(kind, name, seed):
@@ -327,7 +325,40 @@ def _check_reference():
     print(f"{sum(len(t) for t in TABLES.values())} cases, no activation kinks at seed 7, worst float32 error {worst:.2e}, {time.time() - t0:.1f} s")
 
 
+def _instances():
+    """profiles/kxk_instances.md: one table per direction and setting; under a switch only the cases that change their launches."""
+    import kxk256_cases  # noqa: F401  (registers its tables in _ALL)
+    tables = {k: list(TABLES[k]) + list(kxk256_cases.TABLES[k]) for k in TABLES}
+    print("# Dense 3x3 convolution kernels: which test case launches what\n")
+    print("The answers of `lhn_conv_kxk_route` (`include/lhn.h`: host only, the route functions `lhn_conv_kxk_fwd` / `lhn_conv_kxk_bwd` ask) for\n"
+          "`FWD` / `BWD` of `tests/kxk_cases.py` and `tests/kxk256_cases.py`, printed by `python tests/kxk_cases.py --instances`;\n"
+          "`tests/test_kxk_route_cpu.py` holds them as a literal table.  `k_kxk<KD, NT, MODE, TAPS, PLAIN>` (MODE 0 forward, 1 data gradient),\n"
+          "`k_kxk_wgrad<CIN, NTO, TAPS, PLAIN>`: names as a kernel trace prints them, launches in order, every case with the tap-major weight\n"
+          "scratch (`k_w_tapmajor`).  Behind a name: ` yN` N blocks of features on `gridDim.y`, ` par` the four pixel-parity classes of the\n"
+          "stride-2 data gradient, ` zN` N groups of output channels on `gridDim.z`, ` excl` / ` atomic` the weight gradient's flush, ` x 2` one\n"
+          "launch per 128-channel input slice.")
+    for kind, title in (("fwd", "Forward"), ("bwd", "Backward")):
+        base = {nm: kernel_of(kind, nm) for nm in tables[kind]}
+        for setting, kw in SETTINGS:
+            got = {nm: kernel_of(kind, nm, **kw) for nm in tables[kind]}
+            rows = {}
+            for nm, k in got.items():
+                if not kw or k != base[nm]:
+                    rows.setdefault(k, []).append(nm)
+            if not rows:
+                continue
+            print(f"\n## {title}, {setting}" + (": the cases that change their launches" if kw else "") + "\n\n| launches | cases |\n|---|---|")
+            for k, names in rows.items():
+                print(f"| `{k}` | {', '.join(names)} |")
+    print("\n## Refused for lack of a kernel (the query answers NULL)\n")
+    print(", ".join(f"{kind}:{nm}" for kind in ("fwd", "bwd") for nm in _ALL[kind] if nm not in tables[kind] and kernel_of(kind, nm) is None))
+
+
 if __name__ == "__main__":
+    if sys.argv[1] == "--instances":
+        import kxk_cases          # (kxk256_cases registers its tables in the imported module, not in __main__)
+        kxk_cases._instances()
+        sys.exit(0)
     if sys.argv[1] == "--check-reference":
         _check_reference()
         sys.exit(0)

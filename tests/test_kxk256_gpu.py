@@ -154,10 +154,8 @@ def test_kxk256_plain_switch_is_ignored(dev, tmp_path):
         kind, name = full.split(":")
         g, r64, e32 = _reference(kind, name)
         got = _of(res, full, 0)
-        # (the harness reads LHN_PLAIN the old way and reports `dz_unchanged_ok` = False: dz did change, to dy -- read it from dx / dw
-        # and the guard instead)
-        assert "dz_unchanged_ok" in got and not bool(got.pop("dz_unchanged_ok"))
-        _check(kind, name, got, {k: v for k, v in r64.items() if k != "dz"}, e32, "LHN_PLAIN=0/")
+        assert "dz" in got and "dz_unchanged_ok" not in got, f"{full}: the harness and the library disagree on the path"
+        _check(kind, name, got, r64, e32, "LHN_PLAIN=0/")
 
 
 @pytest.mark.parametrize("name", list(k2.FWD_REFUSE))

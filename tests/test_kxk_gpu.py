@@ -2,7 +2,7 @@
 against a float64 torch reference: every instantiation of the implicit-GEMM kernel (forward, dgrad of the in-place dy, dgrad with
 dy on the fly) and of the wgrad kernel (K-split, whole tiles per wave, cosplit with the exclusive flush, the atomic flush), the
 stride-2 dgrad by pixel parity, the tap-major weight scratch in both layouts, k_dy_inplace with a gate and a pooled gradient,
-channel-slice views, dx_accumulate, and persistent grids with more tiles than workgroups.  tests/kxk_cases.py lists which case
+channel-slice views, dx_accumulate, and persistent grids with more tiles than workgroups.  profiles/kxk_instances.md lists which case
 reaches which instantiation.  LHN_PLAIN=0 and LHN_PLAIN=1 must meet the same bar, deterministic mode must repeat its bits, and
 calls outside the supported set are refused without writing -- dz included."""
 import os
