@@ -391,8 +391,8 @@ int64_t lhn_msrb_round_scratch_bytes(int N, int H, int W, int C);   /* host-only
 int lhn_msrb_round_fwd(const lhn_view x[2], const lhn_view* extra /*[2] or NULL*/, const float* coef2 /*host, 2 floats, or NULL*/,
                        const float* w_d1 /*[C/2,1,3,3]*/, const float* w_d2 /*[C/2,1,3,3]*/, const lhn_view* y /*C channels*/,
                        float* pooled /*[N,OH,OW,C] or NULL*/, int OH, int OW, void* scratch, void* stream);
-/* Cout = 8, 16, .. 256 (a power of two times 8), k = 1, 3, 5 or 7.  3x3 -> 32 and 7x7 -> 64 run on MFMA kernels; every other shape
- * on the direct kernel, which keeps the weights and its reduction scratch in 3*k*k*Cout*4 + 16384 bytes of LDS: a shape that
+/* Cout = 8, 16, .. 256 (a power of two times 8) or 40 (the stem of mynet at input_channel = 160), k = 1, 3, 5 or 7.  3x3 -> 32 and
+ * 7x7 -> 64 run on MFMA kernels; every other shape on the direct kernel, which keeps the weights and its reduction scratch in 3*k*k*Cout*4 + 16384 bytes of LDS: a shape that
  * needs more than 65536 bytes (k = 7 with Cout >= 128, k = 5 with Cout = 256) returns the invalid-argument status before any
  * launch, with the byte count in the text, and writes nothing. */
 int lhn_conv_stem_fwd(const float* img /*[N,3,Hi,Wi]*/, const float* w /*[Cout,3,k,k]*/, const lhn_view* y,
@@ -401,7 +401,11 @@ int lhn_conv_stem_fwd(const float* img /*[N,3,Hi,Wi]*/, const float* w /*[Cout,3
  * (16-byte weight loads per tap instead of 36-byte-strided gathers).  NULL = read the OIHW tensor directly.
  * Cin in {32, 64, 128, 256}; Cout in {32, 64, 128, 256} (1, 2, 4 or 8 tiles of 32 features; a Cout whose tile count is one of
  * these may end in a partial tile, e.g. 40).  Cin = 256 runs as two 128-channel K slices per tap inside one launch, Cout = 256 as
- * blocks of at most 128 features on gridDim.y; statistics and the fused finalize (`fin`) see the complete sums either way.  Any
+ * blocks of at most 128 features on gridDim.y; statistics and the fused finalize (`fin`) see the complete sums either way.
+ * Width 160 (mynet's own convolutions, and no other pair with one of these sides): 160 -> 160 runs as five 32-channel K slices per tap
+ * with the five feature tiles in one block or one per block on gridDim.y = 5; 40 -> 40 runs on the 64-channel LDS images with
+ * channels [40, 64) zero (their lanes issue no x load; the MFMA loop stops after channel 39).  Five feature tiles exist for
+ * 160 alone: a Cout or Cin of 129 .. 159 is refused.  Any
  * other channel count returns the invalid-argument status ("unsupported channels") before the first launch and writes nothing,
  * the scratch included.  wt_scratch holds 9*Cout*Cin floats ([tap][Cout][Cin]; 589,824 floats = 2.25 MiB at 256 -> 256). */
 int lhn_conv_kxk_fwd(const lhn_view* x, const float* w /*[Cout,Cin,3,3]*/, const lhn_view* y, double* stats,
@@ -590,6 +594,7 @@ int lhn_conv_dw_bwd2(const lhn_view* x, const float* w, const lhn_view* y, const
 int lhn_conv_dw_bwd3(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx, int dx_accumulate,
                      float* dw, int k, int stride, int pad, int dil, int nrep, int64_t rep_stride, const float* dx_add0,
                      const float* dx_add1, void* stream);
+/* Cout: a power of two times 4 up to 256, or 40; k = 1, 3 or 7 (anything else: the invalid-argument status, nothing written). */
 int lhn_conv_stem_bwd(const float* img, const lhn_view* y, const lhn_gradview* gy, float* dw, int Hi, int Wi,
                       int k, int stride, int pad, int nrep, int64_t rep_stride, void* stream);
 /* NOTE: lhn_conv_kxk_bwd and the large-channel path of lhn_conv_pw_bwd CONSUME gy->dz (it is overwritten in place
@@ -597,9 +602,12 @@ int lhn_conv_stem_bwd(const float* img, const lhn_view* y, const lhn_gradview* g
  * lhn_conv_kxk_bwd: Cin, Cout in {32, 64, 128, 256} (3x3, pad 1, stride 1 or 2); anything else returns the invalid-argument status
  * ("unsupported channels") before the first launch: dz, dx, dw and the scratch are left as they were.  256 channels run as two
  * 128-channel slices: Cout = 256 inside the data-gradient kernel (dx is written once), Cin = 256 as one weight-gradient launch per
- * input slice.  wt_scratch: 9*Cout*Cin floats (589,824 at 256 -> 256), written [tap][Cin][Cout] by the call when dx != NULL, or NULL.
- * dz is consumed ("plain": k_dy_inplace in front) with a pooled gradient, with a side of 256, and otherwise when Cin * Cout >= 4096.
- * LHN_PLAIN=0 / 1 replaces that last size rule alone (never / always; it does not apply to a pooled gradient or a side of 256).  The
+ * input slice.  160 -> 160 and 40 -> 40 as in lhn_conv_kxk_fwd (and 64 -> 40 without dx, as before): 160 is always plain, its data
+ * gradient runs five 32-channel slices of Cout, its weight gradient a 128-channel and a 32-channel input slice with Cout on five or
+ * three groups; 40 -> 40 is below the size rule, so dy is formed on the fly unless LHN_PLAIN=1 or a pooled gradient says otherwise.
+ * wt_scratch: 9*Cout*Cin floats (589,824 at 256 -> 256), written [tap][Cin][Cout] by the call when dx != NULL, or NULL.
+ * dz is consumed ("plain": k_dy_inplace in front) with a pooled gradient, with a side above 128, and otherwise when Cin * Cout >= 4096.
+ * LHN_PLAIN=0 / 1 replaces that last size rule alone (never / always; it does not apply to a pooled gradient or a side above 128).  The
  * variable is read once, at the first dense 3x3 call or query of the process: set it before the process starts.
  * Which kernels a call launches is kxk_fwd_route / kxk_bwd_route's decision (csrc/k_conv_kxk.hip); lhn_conv_kxk_route below asks them. */
 int lhn_conv_kxk_bwd(const lhn_view* x, const float* w, const lhn_view* y, const lhn_gradview* gy, float* dx,
@@ -615,9 +623,9 @@ int lhn_conv_kxk_bwd(const lhn_view* x, const float* w, const lhn_view* y, const
  *   " par"   stride-2 data gradient: the four pixel-parity classes on gridDim.z
  *   " zN"    weight gradient: N groups of output channels on gridDim.z ("cosplit"), where N > 1
  *   " excl" / " atomic"   weight gradient: every block owns its slice of a gradient replica (read-add-write flush), or atomics
- *   " x 2"   weight gradient: one launch per 128-channel input slice (Cin = 256)
- * e.g. "k_dy_inplace + k_w_tapmajor + k_kxk<128, 1, 1, 9, true> y4 + k_kxk_wgrad<128, 1, 9, true> z4 excl"; profiles/kxk_instances.md is
- * printed from it.  NULL: no kernel instance (the call is refused with "unsupported channels" before any launch), or a stride other
+ *   " x 2"   weight gradient: one launch per 128-channel input slice (Cin = 256); Cin = 160 names its two launches, <128, ..> and <32, ..>
+ * e.g. "k_dy_inplace + k_w_tapmajor + k_kxk<128, 1, 1, 9, true> y4 + k_kxk_wgrad<128, 1, 9, true> z4 excl"; profiles/kxk_instances.md and
+ * profiles/kxk160_instances.md are printed from it.  NULL: no kernel instance (the call is refused with "unsupported channels" before any launch), or a stride other
  * than 1 or 2.  Arguments a call would refuse for another reason are not checked. */
 #define LHN_KXK_F_DX    1   /* backward: dx != NULL */
 #define LHN_KXK_F_DPOOL 2   /* backward: gy->dpool != NULL */

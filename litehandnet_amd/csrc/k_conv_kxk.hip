@@ -64,16 +64,26 @@ static void launch_dy_inplace(const lhn_view* y, const lhn_gradview* gy, hipStre
 // KD = 256 does not fit LDS whole (the A tile alone would be 133 KB): it runs as NSL = 2 slices of KW = 128 channels, a phase is
 // then (tap, slice) -- 18 per tile -- on the LDS images and the MFMA loop of the <128, NT> instance, into the same accumulators.
 // The per-thread channel offset and the pending transform belong to a slice: issue() sets them for the phase it loads.
+// KD = 160 (mynet at width 160) runs the same way as NSL = 5 slices of KW = 32 on the images of the <32, NT> instance: 45 phases.
+// KD = 40 (its quarter) is no multiple of 32: it runs on the 64-channel images with channels [40, 64) committed as zeros.  The
+// lanes of that tail issue no A load in the forward and the plain data gradient (dy on the fly: a load clamped to channel 0, value
+// discarded, which measured faster there); their table, gate, coefficient and tap-major weight loads are clamped to channel 0 and
+// the weights staged as zeros.  The MFMA loop stops at the last group of 8 channels that holds a real one (5 of 8 at K = 40).
+constexpr int kxk_kp(int kd) { return kd == 40 ? 64 : kd; }                                  // channels of the LDS images
+constexpr int kxk_kw(int kd) { return kd == 160 ? 32 : kd > 128 ? 128 : kxk_kp(kd); }        // K slice held in LDS
 template <int KD, int NT, int MODE, int TAPS, bool PLAIN = false>
 __global__ void __launch_bounds__(256) k_kxk(lhn_view x, const float* __restrict__ w, lhn_view y, lhn_gradview gy,
                                              double* __restrict__ stats, float* __restrict__ dx, int dx_acc, int stride,
                                              int nout, int Mhost, int ntiles, lhn_bnfin fin, const float* __restrict__ wt) {
-  constexpr int KW = KD > 128 ? 128 : KD, NSL = KD / KW;     // K slice held in LDS, slices per tap
+  constexpr int KW = kxk_kw(KD), NSL = (KD + KW - 1) / KW;   // K slice held in LDS, slices per tap
+  constexpr bool KPAD = NSL * KW != KD;                      // channels [KD, NSL * KW) of the (last slice's) images are zeros
+  static_assert(!KPAD || TAPS == 9, "padded K: 3x3 only");
   static_assert(NSL == 1 || (TAPS == 9 && (MODE == 0 || PLAIN)), "sliced K: 3x3 forward and plain dgrad only");
   constexpr int BM = 128, LDA = KW + 4;
   constexpr int C4 = KW / 4, RP = 256 / C4, PF = BM / RP;     // float4 per thread per phase
   constexpr int NW = 32 * NT * KW / 256;                      // weight scalars per thread per phase
-  constexpr int WCH = NW > 16 ? 16 : NW;                      // staged in chunks of <= 16 registers
+  constexpr int WCH = NW > 16 ? (NW % 16 ? 10 : 16) : NW;     // staged in chunks of <= 16 registers (NT = 5: 20 = 2 x 10)
+  static_assert(NW % WCH == 0, "whole chunks: a partial one would run past the W image");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* Ws = smem;                   // [32*NT][LDA]
   float* As = smem + 32 * NT * LDA;   // [128][LDA]
@@ -97,7 +107,7 @@ __global__ void __launch_bounds__(256) k_kxk(lhn_view x, const float* __restrict
     return (ph ? 2 * a : 1) * 3 + (pw2 ? 2 * b : 1);
   };
   const int cin_total = MODE == 0 ? KD : nout;
-  const int cabs0 = av.coff + 4 * c4;
+  const int cabs0 = av.coff + ((!KPAD || 4 * c4 < KD) ? 4 * c4 : 0);      // (a lane of the zero tail: channel 0, see issue())
   const Xf4 xf0 = lhn_load_xf(av, cabs0);
   int cabs_s = cabs0;               // NSL > 1: offset and transform of the slice whose loads are in flight
   Xf4 xf_s = xf0;
@@ -130,8 +140,10 @@ __global__ void __launch_bounds__(256) k_kxk(lhn_view x, const float* __restrict
   };
   auto issue = [&](int tap, int sl) __attribute__((always_inline)) {
     const int kh = TAPS == 1 ? 1 : tap / 3, kw = TAPS == 1 ? 1 : tap - (tap / 3) * 3;
+    // padded K: whether this lane's four channels exist in the slice; a lane of the zero tail issues no load and commits zeros
+    const bool cok = !KPAD || sl * KW + 4 * c4 < KD;
     if (NSL > 1) {       // the previous phase is committed: its offset and transform are dead
-      cabs_s = cabs0 + sl * KW;
+      cabs_s = KPAD ? av.coff + (cok ? sl * KW + 4 * c4 : 0) : cabs0 + sl * KW;
       if (MODE == 0) xf_s = lhn_load_xf(av, cabs_s);
     }
     if (LIN) {
@@ -146,6 +158,15 @@ __global__ void __launch_bounds__(256) k_kxk(lhn_view x, const float* __restrict
       }
       return;
     }
+    if (KPAD && (MODE == 0 || PLAIN) && !cok) {      // (at K = 40 that is 6 lanes of 16: a third of the A traffic)
+#pragma unroll
+      for (int p = 0; p < PF; ++p) {
+        pv[p] = false;
+        pa[p] = (f4){0.f, 0.f, 0.f, 0.f};
+        if (MODE == 1 && !PLAIN) pb[(MODE == 1 && !PLAIN) ? p : 0] = (f4){0.f, 0.f, 0.f, 0.f};
+      }
+      return;
+    }
 #pragma unroll
     for (int p = 0; p < PF; ++p) {
       // clamped, always-valid addresses: all loads of the phase issue back to back; validity is a select at commit
@@ -153,13 +174,13 @@ __global__ void __launch_bounds__(256) k_kxk(lhn_view x, const float* __restrict
       if (MODE == 0) {
         const int ih = rh[p] * stride - 1 + kh, iw = rw[p] * stride - 1 + kw;
         const int ihc = min(max(ih, 0), x.H - 1), iwc = min(max(iw, 0), x.W - 1);
-        pv[p] = rn[p] >= 0 && ih == ihc && iw == iwc;
+        pv[p] = cok && rn[p] >= 0 && ih == ihc && iw == iwc;
         pa[p] = *reinterpret_cast<const f4*>(x.data + ((size_t)(n * x.H + ihc) * x.W + iwc) * x.cstride + cabs);
       } else {
         const int hn = rh[p] + 1 - kh, wn2 = rw[p] + 1 - kw;
         const int ho = hn / stride, wo = wn2 / stride;     // hn, wn2 >= -1: trunc == floor where it matters (validity below)
         const int hoc = min(max(ho, 0), y.H - 1), woc = min(max(wo, 0), y.W - 1);
-        pv[p] = rn[p] >= 0 && hn >= 0 && wn2 >= 0 && ho * stride == hn && wo * stride == wn2 && ho == hoc && wo == woc;
+        pv[p] = cok && rn[p] >= 0 && hn >= 0 && wn2 >= 0 && ho * stride == hn && wo * stride == wn2 && ho == hoc && wo == woc;
         const size_t off = ((size_t)(n * y.H + hoc) * y.W + woc) * y.cstride + cabs;
         if (PLAIN) pa[p] = *reinterpret_cast<const f4*>(gy.dz + off);
         else {
@@ -180,19 +201,20 @@ __global__ void __launch_bounds__(256) k_kxk(lhn_view x, const float* __restrict
       // tid + 256 * j to (row, k4) the same way, and 32 * NT * K4 == 256 * NWV).  commit() always follows stage_w() before the
       // barrier, so the stray value is overwritten in program order by its own thread: in bounds (j - NWV < PF), no effect.
       // That holds only while the two mappings stay equal -- change either and this becomes an LDS write-write race
-      // between waves; bound the loop by NWV then.  (The sliced instances have KW = 128: NWV >= 4, nothing runs past.)
+      // between waves; bound the loop by NWV then.  (Slices of 128 have NWV >= 4: nothing runs past.  Slices of 32 and the padded
+      // 40 are the <32, NT> and <64, NT> images with their mappings.  NT = 5: NWV = 5, the second group of four runs three past.)
 #pragma unroll
       for (int j0 = 0; j0 < NWV; j0 += 4) {
         f4 t[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int i = tid + 256 * (j0 + j), nn = i / K4, k4 = i - nn * K4;
-          t[j] = *reinterpret_cast<const f4*>(wt + ((size_t)tap * nout + min(n0 + nn, nout - 1)) * KD + sl * KW + 4 * k4);
+          t[j] = *reinterpret_cast<const f4*>(wt + ((size_t)tap * nout + min(n0 + nn, nout - 1)) * KD + sl * KW + (KPAD && sl * KW + 4 * k4 >= KD ? 0 : 4 * k4));
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int i = tid + 256 * (j0 + j), nn = i / K4, k4 = i - nn * K4;
-          *reinterpret_cast<f4*>(Ws + nn * LDA + 4 * k4) = n0 + nn < nout ? t[j] : (f4){0.f, 0.f, 0.f, 0.f};
+          *reinterpret_cast<f4*>(Ws + nn * LDA + 4 * k4) = (n0 + nn < nout && (!KPAD || sl * KW + 4 * k4 < KD)) ? t[j] : (f4){0.f, 0.f, 0.f, 0.f};
         }
       }
       return;
@@ -206,7 +228,7 @@ __global__ void __launch_bounds__(256) k_kxk(lhn_view x, const float* __restrict
         float v = 0.f;
         if (MODE == 0 || TAPS > 1) {
           const int nn = i / KW, kk = i - nn * KW, ka = sl * KW + kk;
-          if (n0 + nn < nout) v = MODE == 0 ? w[((size_t)(n0 + nn) * cin_total + ka) * TAPS + tap] : w[((size_t)ka * cin_total + n0 + nn) * TAPS + tap];
+          if (n0 + nn < nout && (!KPAD || ka < KD)) v = MODE == 0 ? w[((size_t)(n0 + nn) * cin_total + ka) * TAPS + tap] : w[((size_t)ka * cin_total + n0 + nn) * TAPS + tap];
         } else {   // 1x1 dgrad: W[co = k][ci = n], coalesced along n
           const int kk = i / (32 * NT), nn = i - kk * (32 * NT);
           if (n0 + nn < nout) v = w[(size_t)kk * cin_total + n0 + nn];
@@ -275,7 +297,7 @@ __global__ void __launch_bounds__(256) k_kxk(lhn_view x, const float* __restrict
       const float* arow = As + (wave * 32 + l31) * LDA + 4 * lh;
       const float* brow = Ws + l31 * LDA + 4 * lh;
 #pragma unroll 4
-      for (int kc = 0; kc < KW / 8; ++kc) {
+      for (int kc = 0; kc < (KPAD && NSL == 1 ? (KD + 7) / 8 : KW / 8); ++kc) {
         const f4 a = *reinterpret_cast<const f4*>(arow + kc * 8);
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
@@ -358,7 +380,9 @@ __global__ void __launch_bounds__(256) k_kxk(lhn_view x, const float* __restrict
 template <int CIN, int NTO, int TAPS, bool PLAIN = false>
 __global__ void __launch_bounds__(256) k_kxk_wgrad(lhn_view x, lhn_view y, lhn_gradview gy, float* __restrict__ dw, int stride,
                                                    int cout, int M, int ntiles, int nrep, int64_t rep_stride, int wstride) {
-  constexpr int NTI = CIN / 32, COP = 32 * NTO, LDY = COP + 4, LDX = CIN + 4;
+  // CIN = 40: the 64-channel X image with channels [40, 64) zero (kxk_kp); their columns of dW are never flushed
+  constexpr int CINP = kxk_kp(CIN), NTI = CINP / 32, COP = 32 * NTO, LDY = COP + 4, LDX = CINP + 4;
+  constexpr bool XPAD = CINP != CIN;
   // fewer dW tiles than waves (32 -> 32: one tile): split the 64-pixel K range of a tile over the idle waves; the partial
   // tiles meet in LDS before the flush
   constexpr int T = NTO * NTI, KS = T < 4 ? 4 / T : 1;
@@ -368,9 +392,11 @@ __global__ void __launch_bounds__(256) k_kxk_wgrad(lhn_view x, lhn_view y, lhn_g
   float* Xs = dYs + 64 * LDY;      // [64][LDX]
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, lh = lane >> 5;
   const int tap = blockIdx.y, kh = TAPS == 1 ? 1 : tap / 3, kw = TAPS == 1 ? 1 : tap - (tap / 3) * 3;
-  constexpr int XC4 = CIN / 4, XRP = 256 / XC4, XPF = 64 / XRP;
+  constexpr int XC4 = CINP / 4, XRP = 256 / XC4, XPF = 64 / XRP;
   constexpr int YC4 = COP / 4, YRP = 256 / YC4, YPF = 64 / YRP;
-  const int xc4 = tid % XC4, xr0 = tid / XC4, xabs = x.coff + 4 * xc4;
+  const int xc4 = tid % XC4, xr0 = tid / XC4;
+  const bool xcok = !XPAD || 4 * xc4 < CIN;
+  const int xabs = x.coff + (xcok ? 4 * xc4 : 0);
   const int co0 = blockIdx.z * COP;
   const int yc4 = tid % YC4, yr0 = tid / YC4, yabs = y.coff + co0 + 4 * yc4;
   const Xf4 xxf = lhn_load_xf(x, xabs);
@@ -396,7 +422,7 @@ __global__ void __launch_bounds__(256) k_kxk_wgrad(lhn_view x, lhn_view y, lhn_g
       const int n = m / HoWo, r = m - n * HoWo, ho = r / y.W, wo = r - ho * y.W;
       const int ih = ho * stride - 1 + kh, iw = wo * stride - 1 + kw;
       const int ihc = min(max(ih, 0), x.H - 1), iwc = min(max(iw, 0), x.W - 1);
-      xok[p] = (tile * 64 + xr0 + p * XRP < M) && ih == ihc && iw == iwc;
+      xok[p] = xcok && (tile * 64 + xr0 + p * XRP < M) && ih == ihc && iw == iwc;
       xn[p] = n;
       xraw[p] = *reinterpret_cast<const f4*>(x.data + ((size_t)(n * x.H + ihc) * x.W + iwc) * x.cstride + xabs);
     }
@@ -505,7 +531,7 @@ __global__ void __launch_bounds__(256) k_kxk_wgrad(lhn_view x, lhn_view y, lhn_g
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int co = co0 + 32 * it + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (co < cout) {
+        if (co < cout && (!XPAD || 32 * jt + l31 < CIN)) {
           float* o = dw + ((size_t)co * wstride + 32 * jt + l31) * TAPS + tap;     // wstride = input channels of the WHOLE weight
           if (exclusive) *o += accw[t][r];
           else atomicAdd(o, accw[t][r]);
@@ -537,7 +563,7 @@ static int launch_kxk(const lhn_view* x, const float* w, const lhn_view* y, cons
   if (finp && stats) fin = *finp; else fin.counter = nullptr;
   const lhn_view* ov = MODE == 0 ? y : x;
   const int M = parity ? ov->N * ((ov->H + 1) / 2) * ((ov->W + 1) / 2) : ov->N * ov->H * ov->W, ntiles = (M + 127) / 128;
-  constexpr int KW = KD > 128 ? 128 : KD;       // the K slice that is resident in LDS
+  constexpr int KW = kxk_kw(KD);                // the K slice that is resident in LDS
   const size_t lds = (size_t)((32 * NT + 128) * (KW + 4) + 4 * 32 * NT * 2) * sizeof(float);
   static LhnKernelCfg cfg;
   int per_cu = 1;
@@ -566,7 +592,7 @@ static int launch_kxk_wgrad(const lhn_view* x, const lhn_view* y, const lhn_grad
                             int64_t rep_stride, hipStream_t s, int cosplit = 1, int wstride = CIN, bool chunked = true) {
   const int M = y->N * y->H * y->W, ntiles = (M + 63) / 64;
   constexpr int COP = 32 * NTO;
-  const size_t lds = (size_t)(64 * (COP + 4) + 64 * (CIN + 4)) * sizeof(float);
+  const size_t lds = (size_t)(64 * (COP + 4) + 64 * (kxk_kp(CIN) + 4)) * sizeof(float);
   static LhnKernelCfg cfg;
   int per_cu = 1;
   if (!lhn_kernel_cfg(cfg, &k_kxk_wgrad<CIN, NTO, TAPS, PLAIN>, lds, 3, &per_cu)) {
@@ -586,16 +612,22 @@ static int launch_kxk_wgrad(const lhn_view* x, const lhn_view* y, const lhn_grad
 // from them and nothing else states the set.  K = 32, 64 or 128 channels exactly, 1, 2 or 4 tiles of 32 per block; K = 256 is two
 // 128-channel slices: inside k_kxk (forward and plain dgrad only), and one k_kxk_wgrad<128, ...> launch per slice.  The one-tap
 // pairs are those of lhn_pw_bwd_split (LHN_KXK_ONETAP, lhn_common.h).
+// Width 160 (kxk_pair_ok: 160 -> 160 and 40 -> 40 only): K = 160 is five 32-channel slices inside k_kxk with five feature tiles in
+// one block or one per block (forward and plain dgrad), K = 40 the padded 64-channel image with one or two tiles; the weight
+// gradient of a 160-channel x is a k_kxk_wgrad<128, ...> launch and a <32, ...> launch, of a 40-channel x one <40, 2, ...>.
 #define KXK_NT(X, K, ...) X(K, 1, __VA_ARGS__) X(K, 2, __VA_ARGS__) X(K, 4, __VA_ARGS__)
+#define KXK_NT40(X, ...) X(40, 1, __VA_ARGS__) X(40, 2, __VA_ARGS__)
+#define KXK_NT160(X, ...) X(160, 1, __VA_ARGS__) X(160, 5, __VA_ARGS__)
 // k_kxk<KD, NT, MODE, TAPS, PLAIN>: forward; dgrad of the in-place dy; dgrad with dy on the fly; one tap
 #define KXK_INSTANCES(X)                                                                                                \
   KXK_NT(X, 32, 0, 9, false) KXK_NT(X, 64, 0, 9, false) KXK_NT(X, 128, 0, 9, false) KXK_NT(X, 256, 0, 9, false)         \
   KXK_NT(X, 32, 1, 9, true) KXK_NT(X, 64, 1, 9, true) KXK_NT(X, 128, 1, 9, true) KXK_NT(X, 256, 1, 9, true)             \
-  KXK_NT(X, 32, 1, 9, false) KXK_NT(X, 64, 1, 9, false) KXK_NT(X, 128, 1, 9, false) LHN_KXK_ONETAP(X, 1, 1, true)
+  KXK_NT(X, 32, 1, 9, false) KXK_NT(X, 64, 1, 9, false) KXK_NT(X, 128, 1, 9, false) LHN_KXK_ONETAP(X, 1, 1, true)       \
+  KXK_NT40(X, 0, 9, false) KXK_NT40(X, 1, 9, true) KXK_NT40(X, 1, 9, false) KXK_NT160(X, 0, 9, false) KXK_NT160(X, 1, 9, true)
 // k_kxk_wgrad<CIN, NTO, TAPS, PLAIN>
 #define KXK_WGRAD_INSTANCES(X)                                                                                          \
   KXK_NT(X, 32, 9, true) KXK_NT(X, 64, 9, true) KXK_NT(X, 128, 9, true) KXK_NT(X, 32, 9, false) KXK_NT(X, 64, 9, false) \
-  KXK_NT(X, 128, 9, false) LHN_KXK_ONETAP(X, 1, true)
+  KXK_NT(X, 128, 9, false) LHN_KXK_ONETAP(X, 1, true) X(40, 2, 9, true) X(40, 2, 9, false)
 
 constexpr int KXK_WGRAD = 2;      // KxkInst::mode of a k_kxk_wgrad instance (0 forward, 1 dgrad: k_kxk's MODE)
 struct KxkInst {
@@ -654,6 +686,7 @@ struct KxkRoute {
   KxkInst conv;                   // the forward or the data gradient (k = 0: dx is NULL, no dgrad and none needed)
   int nsplit, par;                //   blocks of 32 * nt features on gridDim.y;  stride-2 dgrad: four pixel-parity classes on gridDim.z
   KxkInst wgrad;                  // backward: the weight gradient, one launch per slice of wgrad.k input channels
+  KxkInst wtail;                  //   (Cin = 160: k = 32) one more launch for the channels past the last whole slice; k = 0: none
   int nslices, cosplit;           //   (Cin = 256: two);  groups of 32 * nt output channels on gridDim.z
   bool chunked, exclusive;        //   pixel chunks = gradient replicas;  the flush is a plain read-add-write (gridDim.x <= nrep)
 };
@@ -668,17 +701,31 @@ static int kxk_out_pixels(const KxkShape& s) { return s.N * ((s.H - 1) / s.strid
 
 // Small maps give few 128-pixel tiles (8x8 maps at batch 64: 32 tiles for 256 CUs): split the `nt` 32-feature tiles of the GEMM's N
 // over gridDim.y so that about two workgroups per CU exist.  Returns the per-block tile count (1, 2 or 4 -> nt / splits blocks).
-// nt = 8 (256 features) starts from two splits: a block holds at most four accumulator tiles.  0: not 1, 2, 4 or 8 tiles.
+// nt = 8 (256 features) starts from two splits: a block holds at most four accumulator tiles.  0: not 1, 2, 4, 5 or 8 tiles.
+// nt = 5 (160 features) has no halves: all five tiles in one block (the A tile is staged once) where that alone gives two workgroups
+// per CU, else one tile per block on gridDim.y = 5.
 static int kxk_nt_block(int M, int nt, int cus) {
-  if (nt > 8 || (nt & (nt - 1))) return 0;
   const int ntiles = (M + 127) / 128;
+  if (nt == 5) return ntiles >= 2 * cus ? 5 : 1;
+  if (nt > 8 || (nt & (nt - 1))) return 0;
   int splits = nt > 4 ? nt / 4 : 1;
   while (splits < nt && ntiles * splits < 2 * cus) splits *= 2;
   return nt / splits;
 }
 
+// Width 160 serves mynet's own convolutions: 160 -> 160 and 40 -> 40.  Every other pair with a side of 160, and every other pair that
+// would need the padded K = 40 (Cin = 40; the data gradient of Cout = 40), is refused.  64 -> 40 and 256 -> 40 forward are older than
+// this rule and need no K = 40: they stay.
+static bool kxk_pair_ok(const KxkShape& s, bool backward) {
+  // five feature tiles (kxk_nt_block, the weight gradient's groups) exist for 160 alone: 129 .. 159 channels stay refused
+  if (((s.Cout + 31) / 32 == 5 && s.Cout != 160) || ((s.Cin + 31) / 32 == 5 && s.Cin != 160)) return false;
+  if (s.Cin == 160 || s.Cout == 160 || s.Cin == 40) return s.Cin == s.Cout;
+  return !(backward && s.dx && s.Cout == 40);
+}
+
 static KxkRoute kxk_fwd_route(const KxkShape& s, int cus, int) {
   KxkRoute r = {};
+  if (!kxk_pair_ok(s, false)) return r;
   const int ntot = (s.Cout + 31) / 32, nt = kxk_nt_block(kxk_out_pixels(s), ntot, cus);      // GEMM N = Cout, K = Cin
   r.conv = {s.Cin, nt, 0, 9, false};
   r.nsplit = nt ? ntot / nt : 0;
@@ -688,6 +735,7 @@ static KxkRoute kxk_fwd_route(const KxkShape& s, int cus, int) {
 
 static KxkRoute kxk_bwd_route(const KxkShape& s, int cus, int sw) {
   KxkRoute r = {};
+  if (!kxk_pair_ok(s, true)) return r;
   // Large channel counts: turn dz into dy in place, then stream it plain (LHN_PLAIN=0/1 overrides the size rule).  A channel-attention
   // pooled gradient always takes this path: lhn_dy_fast has no pooled term.  So does a side of 256 channels: the sliced dgrad has no
   // dy-on-the-fly instance (a second set of y-transform and coefficient registers per slice), and by the size rule it is plain anyway.
@@ -704,12 +752,16 @@ static KxkRoute kxk_bwd_route(const KxkShape& s, int cus, int sw) {
   // way, or two groups of four tiles (a block holds at most four) with the atomic flush.
   const int wtot = (s.Cout + 31) / 32, wtiles = (kxk_out_pixels(s) + 63) / 64;
   r.chunked = s.Cin >= 64 && s.nrep > 1 && wtiles <= 16 * s.nrep;
-  r.cosplit = wtot == 8 ? (r.chunked ? 8 : 2) : ((wtot == 2 || wtot == 4) && r.chunked ? wtot : 1);
-  // Cin = 256: once per 128-channel input slice (disjoint columns of dW)
-  r.nslices = s.Cin > 128 ? 2 : 1;
-  r.wgrad = {s.Cin / r.nslices, wtot / r.cosplit, KXK_WGRAD, 9, r.plain};
+  // Cout = 160: five groups of one tile the same way, or three groups of two tiles (the last group's second tile is past Cout: its
+  // dy columns are zeros) with the atomic flush.
+  r.cosplit = wtot == 8 ? (r.chunked ? 8 : 2) : wtot == 5 ? (r.chunked ? 5 : 3) : ((wtot == 2 || wtot == 4) && r.chunked ? wtot : 1);
+  // Cin = 256: once per 128-channel input slice (disjoint columns of dW).  Cin = 160: a 128-channel slice and a 32-channel one.
+  r.nslices = s.Cin == 256 ? 2 : 1;
+  const int nto = (wtot + r.cosplit - 1) / r.cosplit;
+  r.wgrad = {s.Cin == 160 ? 128 : s.Cin / r.nslices, nto, KXK_WGRAD, 9, r.plain};
+  if (s.Cin == 160) r.wtail = {32, nto, KXK_WGRAD, 9, r.plain};
   r.exclusive = kxk_wgrad_grid(cus, wtiles, s.nrep, r.cosplit, r.chunked) <= s.nrep;
-  r.ok = (!s.dx || kxk_name(r.conv)) && kxk_name(r.wgrad) && s.Cin % r.nslices == 0;
+  r.ok = (!s.dx || kxk_name(r.conv)) && kxk_name(r.wgrad) && (!r.wtail.k || kxk_name(r.wtail)) && s.Cin % r.nslices == 0;
   return r;
 }
 
@@ -749,12 +801,14 @@ extern "C" int lhn_conv_kxk_bwd(const lhn_view* x, const float* w, const lhn_vie
     const int rc = kxk_launch(r.conv, x, w, y, gy, nullptr, dx, dx_accumulate, stride, x->C, s, nullptr, r.nsplit, r.par, wt_scratch);
     if (rc) return rc;
   }
-  for (int k0 = 0; k0 < x->C; k0 += r.wgrad.k) {      // row length of dW = Cin (wstride), the slice starts 9 * k0 in
+  for (int k0 = 0; k0 < x->C;) {      // row length of dW = Cin (wstride), the slice starts 9 * k0 in
+    const KxkInst& wi = x->C - k0 >= r.wgrad.k ? r.wgrad : r.wtail;
     lhn_view xv = *x;
     xv.coff += k0;
-    xv.C = r.wgrad.k;
-    const int rc = kxk_wgrad_launch(r.wgrad, &xv, y, gy, dw + (size_t)9 * k0, stride, nrep, rep_stride, s, r.cosplit, x->C, r.chunked);
+    xv.C = wi.k;
+    const int rc = kxk_wgrad_launch(wi, &xv, y, gy, dw + (size_t)9 * k0, stride, nrep, rep_stride, s, r.cosplit, x->C, r.chunked);
     if (rc) return rc;
+    k0 += wi.k;
   }
   LHN_CHECK_LAUNCH("lhn_conv_kxk_bwd");
   return 0;
@@ -767,9 +821,9 @@ extern "C" const char* lhn_conv_kxk_route(int backward, int N, int H, int W, int
   const KxkShape sh = {N, H, W, Cin, Cout, stride, nrep < 1 ? 1 : nrep, (features & LHN_KXK_F_DX) != 0, (features & LHN_KXK_F_DPOOL) != 0};
   const KxkRoute r = (backward ? kxk_bwd_route : kxk_fwd_route)(sh, cus > 0 ? cus : lhn_num_cus(), switches < 0 ? kxk_switches() : switches);
   if (!r.ok) return nullptr;
-  static thread_local char buf[256];
+  static thread_local char buf[320];
   size_t len = 0;
-  auto put = [&](const char* fmt, auto... a) { len += snprintf(buf + len, sizeof(buf) - len, fmt, a...); };      // (the longest answer is 110 characters)
+  auto put = [&](const char* fmt, auto... a) { len += snprintf(buf + len, sizeof(buf) - len, fmt, a...); };      // (the longest answer is 163 characters)
   auto launch = [&](const char* name) { put(len ? " + %s" : "%s", name); };
   if (r.plain) launch("k_dy_inplace");
   if (r.conv.k) {
@@ -783,6 +837,11 @@ extern "C" const char* lhn_conv_kxk_route(int backward, int N, int H, int W, int
     if (r.cosplit > 1) put(" z%d", r.cosplit);
     put(" %s", r.exclusive ? "excl" : "atomic");
     if (r.nslices > 1) put(" x %d", r.nslices);
+    if (r.wtail.k) {
+      launch(kxk_name(r.wtail));
+      if (r.cosplit > 1) put(" z%d", r.cosplit);
+      put(" %s", r.exclusive ? "excl" : "atomic");
+    }
   }
   return buf;
 }

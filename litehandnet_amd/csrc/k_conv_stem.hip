@@ -4,7 +4,8 @@
 #include "lhn_common.h"
 
 // ------------------------------------------------------------------ stem forward (NCHW 3-channel image -> NHWC)
-// thread = (output pixel, group of 8 output channels)
+// thread = (output pixel, group of 8 output channels).  Cout = 40 (mynet at width 160) has five groups: 51 pixel lanes, and thread
+// 255 is left over -- it takes no pixel and only joins the barriers.
 __global__ void __launch_bounds__(256) k_stem_fwd(const float* __restrict__ img, const float* __restrict__ w, lhn_view y,
                                                   double* __restrict__ stats, int Hi, int Wi, int K, int stride, int pad,
                                                   lhn_bnfin fin) {
@@ -23,7 +24,7 @@ __global__ void __launch_bounds__(256) k_stem_fwd(const float* __restrict__ img,
   float s[8], q[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) s[j] = q[j] = 0.f;
-  for (int64_t pix = (int64_t)blockIdx.x * PL + pl; pix < total; pix += (int64_t)gridDim.x * PL) {
+  for (int64_t pix = pl < PL ? (int64_t)blockIdx.x * PL + pl : total; pix < total; pix += (int64_t)gridDim.x * PL) {
     const int wo = (int)(pix % y.W);
     const int64_t t = pix / y.W;
     const int ho = (int)(t % y.H), n = (int)(t / y.H);
@@ -286,7 +287,8 @@ extern "C" int lhn_conv_stem_fwd(const float* img, const float* w, const lhn_vie
   lhn_bnfin fin;
   if (finp && stats) fin = *finp; else fin.counter = nullptr;
   LHN_CHECK_ARG(img && w && lhn_view_ok(y), "lhn_conv_stem_fwd: bad view / null pointer");
-  LHN_CHECK_ARG(y->C % 8 == 0 && pow2(y->C / 8) && y->C <= 256, "lhn_conv_stem_fwd: Cout=%d", y->C);
+  // (40 = 160 / 4 is admitted by name: the direct kernel's pixel lanes then do not fill the block, see k_stem_fwd)
+  LHN_CHECK_ARG(((y->C % 8 == 0 && pow2(y->C / 8)) || y->C == 40) && y->C <= 256, "lhn_conv_stem_fwd: Cout=%d", y->C);
   LHN_CHECK_ARG((k == 1 || k == 3 || k == 5 || k == 7) && stride >= 1, "lhn_conv_stem_fwd: k=%d", k);
   const int Ho = (Hi + 2 * pad - k) / stride + 1, Wo = (Wi + 2 * pad - k) / stride + 1;
   LHN_CHECK_ARG(y->H == Ho && y->W == Wo, "lhn_conv_stem_fwd: output %dx%d, expected %dx%d", y->H, y->W, Ho, Wo);
@@ -346,7 +348,8 @@ __global__ void __launch_bounds__(256) k_stem_bwd(const float* __restrict__ img,
 #pragma unroll
   for (int i = 0; i < T; ++i) acc[i] = (f4){0.f, 0.f, 0.f, 0.f};
   const int64_t total = (int64_t)y.N * y.H * y.W;
-  for (int64_t pix = (int64_t)blockIdx.x * PL + pl; pix < total; pix += (int64_t)gridDim.x * PL) {
+  // (Cout = 40: ten channel groups, 25 pixel lanes, threads 250..255 take no pixel and add zeros)
+  for (int64_t pix = pl < PL ? (int64_t)blockIdx.x * PL + pl : total; pix < total; pix += (int64_t)gridDim.x * PL) {
     const int wo = (int)(pix % y.W);
     const int64_t t = pix / y.W;
     const int ho = (int)(t % y.H), n = (int)(t / y.H);
@@ -588,7 +591,7 @@ extern "C" int lhn_conv_stem_bwd(const float* img, const lhn_view* y, const lhn_
                                  int stride, int pad, int nrep, int64_t rep_stride, void* stream) {
   if (nrep < 1) nrep = 1;
   LHN_CHECK_ARG(img && lhn_view_ok(y) && gy && gy->dz && dw, "lhn_conv_stem_bwd: bad view / null pointer");
-  LHN_CHECK_ARG(pow2(y->C / 4) && y->C <= 256 && (k == 1 || k == 3 || k == 7), "lhn_conv_stem_bwd: Cout=%d k=%d", y->C, k);
+  LHN_CHECK_ARG((pow2(y->C / 4) || y->C == 40) && y->C <= 256 && (k == 1 || k == 3 || k == 7), "lhn_conv_stem_bwd: Cout=%d k=%d", y->C, k);
   const int PL = 256 / (y->C / 4);
   const int g = grid_for((int64_t)y->N * y->H * y->W, PL, 4);
   if (k == 7 && y->C == 64 && !lhn_dw_force_gather()) {
